@@ -12,13 +12,15 @@ region so the graph size stays at the quoted ~64 nodes).  All inputs are residen
 Multi-GPU: one process per GPU (torch.distributed / RCCL), independent environments per rank, no
 data-path collective in the belief step (weak scaling); time = max over ranks.  `--gpus N` without a launcher
 re-executes itself under `torch.distributed.run` with N ranks; under a launcher WORLD_SIZE must equal --gpus.
-The only exchange of the path is the policy gradient: the `train_allreduce` section of the same line times the
+The only exchange of the path is the policy gradient: the `train_allreduce` section of the --full line times the
 64-graph DQN step with the flat gradient all-reduce (RCCL over xGMI), the collective alone, and the belief steps
 sustained while that training runs on a second stream (BASELINE.json configs[3]).
 
-Output: ONE JSON line on rank 0 (see the driver contract), with `roofline` for the time-dominant
-kernel (per-kernel HIP-event timing on the engine stream), `kernels` for all three and
-`cpu_baseline` = the CPU oracle ("port") timed single-threaded on the same box.
+Output: ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times --steps steps and
+prints the headline figure (`value`, `ms_per_step`).  `--full` adds, after the timed steps, `roofline` for the
+time-dominant kernel (per-kernel HIP-event timing on the engine stream), `kernels` for all three, the
+`train_allreduce` section, the secondary sections and `cpu_baseline` = the CPU oracle ("port") timed
+single-threaded on the same box.  `--dump-outputs DIR` writes the belief the last timed step computed (float64 .npy).
 """
 import argparse
 import json
@@ -609,6 +611,185 @@ def train_allreduce_bench(eng, dev, dist, world, iters=20, env_steps_per_iter=8)
             "train_steps_per_sec": world / t_ov}
 
 
+def dump_outputs(eng, outdir):
+    """`--dump-outputs DIR`: the belief every env holds after the last timed step (snapshot restore + one update) - what a caller
+    of SS2D.simulate reads back - as float64 .npy files (under 30 MB for 256 envs).  Per-env lists of different lengths are padded
+    to the longest with zeros (landmark keys with -1), so every value is finite; `counts` holds each env's poses, landmarks
+    and factors.  Inputs are seeded: two builds given the same arguments can be compared file by file."""
+    os.makedirs(outdir, exist_ok=True)
+    n = eng.n_envs
+    arrays = {"utility": eng.utility(), "metrics": eng.metrics(), "counts": eng.counts_dev()[:, :3]}
+    arrays["cov_length"], arrays["cov_angle"] = eng.cov_array()
+    arrays = {k: v.double().cpu().numpy() for k, v in arrays.items()}
+    per_env = {k: [] for k in ("pose_xyt", "pose_info", "landmark_keys", "landmark_xy", "landmark_info", "landmark_cov_trace",
+                               "pose_cov_trace", "vm_prob", "vm_info", "vm_cov_trace")}
+    for i in range(n):
+        xyt, info = eng.poses(i)
+        keys, xy, linfo = eng.landmarks(i)
+        lm_tr, ps_tr = eng.cov_traces(i)
+        prob, vinfo, vtr, _ = eng.virtual_map(i)
+        for k, v in zip(per_env, (xyt, info, keys, xy, linfo, lm_tr, ps_tr, prob, vinfo, vtr)):
+            per_env[k].append(np.asarray(v, dtype=np.float64))
+    for k, vs in per_env.items():
+        a = np.full((n, max(len(v) for v in vs)) + vs[0].shape[1:], -1.0 if k == "landmark_keys" else 0.0)
+        for i, v in enumerate(vs):
+            a[i, :len(v)] = v
+        arrays[k] = a
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
+def full_measurements(args, eng, dev, dist, world, local_rank, one_step, P, L, M, out):
+    """`--full`: everything the headline figure does not need, on the same engine after its timed steps - the steps again
+    with HIP events around every launch (fused kernel, then the three stage kernels: per-kernel times and rooflines), the
+    SLAM path split, the DQN-update / gradient all-reduce section (all ranks: it holds collectives), and on one GPU the
+    decision-path, scale and trainer-loop sections and the CPU baselines.  Adds their keys to rank 0's line `out`."""
+    # second pass: the same steps with HIP events on the engine stream around every launch (fused belief-step kernel)
+    eng.timing_enable(True)
+    eng.timing_read()
+    for _ in range(args.steps):
+        one_step()
+    tm_fused = eng.timing_read()
+    # third pass: the belief step launched as its three stage kernels, for the per-stage breakdown
+    eng.timing_enable(2)
+    for _ in range(args.steps):
+        one_step()
+    tm = eng.timing_read()
+    eng.timing_enable(False)
+    inc_split = eng.inc_stats(reset=True)  # (all launches so far were the headline update)
+    train = None
+    if not args.no_train:  # every rank takes part: the section contains collectives
+        train = train_allreduce_bench(eng, dev, dist, world)
+    if out is None:
+        return
+    V = eng.rows * eng.cols
+    ab = algorithmic_bytes(P + 1, L, M, V)
+    kernels = {}
+    # an empty event pair is recorded once per step: its duration is the measurement overhead of a span
+    ev_over_us = tm["t7"][0] / max(tm["t7"][1], 1) * 1e3
+    for name in ("sim", "slam", "map", "copy"):
+        ms, n = tm[name]
+        if n == 0:
+            continue
+        avg_us = ms / n * 1e3 - ev_over_us
+        b = ab.get(name)
+        ent = {"avg_us_per_launch": avg_us, "launches": int(n)}
+        if b is not None:
+            ent["algorithmic_bytes_per_launch"] = b * N_ENVS
+            ent["achieved_GBs"] = b * N_ENVS / (avg_us * 1e-6) / 1e9
+            ent["frac_hbm_peak"] = ent["achieved_GBs"] / HBM_PEAK_GBS
+        kernels[name] = ent
+    # the dominant kernel of the timed region is the fused belief step (simulate + SLAM + map of one instance per
+    # workgroup); its algorithmic bytes are the sum of the three stages'
+    ev2 = tm_fused["t7"][0] / max(tm_fused["t7"][1], 1) * 1e3
+    if tm_fused["step"][1] > 0:
+        dom = "step"
+        step_us = tm_fused["step"][0] / tm_fused["step"][1] * 1e3 - ev2
+        step_bytes = (ab["sim"] + ab["slam"] + ab["map"]) * N_ENVS
+        kernels["step"] = {"avg_us_per_launch": step_us, "launches": int(tm_fused["step"][1]),
+                           "algorithmic_bytes_per_launch": step_bytes, "achieved_GBs": step_bytes / (step_us * 1e-6) / 1e9,
+                           "frac_hbm_peak": step_bytes / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                           "note": "fused kernel used by drlgx_step; sim/slam/map entries are the same work launched as three kernels"}
+        if tm_fused["copy"][1] > 0:
+            kernels["copy"]["avg_us_per_launch"] = tm_fused["copy"][0] / tm_fused["copy"][1] * 1e3 - ev2
+    else:  # capacities beyond the fused kernel
+        dom = max(("sim", "slam", "map"), key=lambda k: kernels[k]["avg_us_per_launch"])
+    roofline = {"kernel": {"sim": "k_sim_step", "slam": "k_slam", "map": "k_map", "step": "k_step"}[dom], "bound": "hbm",
+                "achieved": kernels[dom]["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": kernels[dom]["frac_hbm_peak"], "traffic": None,
+                "avg_us_per_launch": kernels[dom]["avg_us_per_launch"]}
+    # HBM traffic per launch comes from separate rocprofv3 --pmc passes over this same command (counters cannot be
+    # read in-process): profiles/pmc_traffic.json holds the corrected per-kernel figures (scripts/rocpd_pmc.py) and
+    # the digest of the kernel sources they were measured on - traffic is reported only when that is THIS tree
+    roofline["algorithmic_bytes_per_launch"] = kernels[dom]["algorithmic_bytes_per_launch"]
+    try:
+        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+            pmc = json.load(f)
+        if pmc.get("csrc_sha1") == csrc_digest():
+            roofline["traffic"] = pmc["kernels"][roofline["kernel"]]["hbm_traffic_bytes_per_launch"]
+            roofline["traffic_source"] = ("profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, bytes/launch), "
+                                          "measured on kernel sources sha1 %s = this tree" % pmc["csrc_sha1"][:12])
+        else:
+            roofline["traffic_source"] = "profiles/pmc_traffic.json is from other kernel sources (sha1 %s): not reported" % str(pmc.get("csrc_sha1"))[:12]
+    except (OSError, KeyError, ValueError):
+        pass
+    # second roofline entry, for the bound the SQ counters support: the belief step is neither an HBM nor an MFMA
+    # kernel - its waves spend most of their cycles parked on waitcnt / barriers of dependent fp64 chains - so the
+    # closest throughput ceiling is VALU instruction issue (one wave64 instruction per SIMD per 4 cycles).  Counters
+    # come from profiles/sq_counters.json (scripts/collect_profiles.sh), quoted only for THIS tree's kernel sources
+    roofline_issue = None
+    try:
+        with open(os.path.join(ROOT, "profiles", "sq_counters.json")) as f:
+            sq = json.load(f)
+        if sq.get("csrc_sha1") == csrc_digest():
+            c = sq["kernels"][roofline["kernel"]]
+            peak = 256 * 4 * 2.4e9 / 4.0 / 1e9  # G wave64 VALU instructions/s: 1024 SIMDs, 4 cycles each
+            ach = c["SQ_INSTS_VALU"] / (roofline["avg_us_per_launch"] * 1e-6) / 1e9
+            wc = c["SQ_WAVE_CYCLES"]
+            roofline_issue = {
+                "kernel": roofline["kernel"], "bound": "valu-issue", "achieved": ach, "peak": peak,
+                "unit": "G wave64 VALU instructions/s", "frac": ach / peak,
+                "wave_cycle_shares": {"issuing_any": c["SQ_ACTIVE_INST_ANY"] / wc, "issuing_valu": c["SQ_ACTIVE_INST_VALU"] / wc,
+                                      "parked_on_waitcnt_or_barrier": c["SQ_WAIT_ANY"] / wc,
+                                      "issue_stalled": c["SQ_WAIT_INST_ANY"] / wc},
+                "mfma_f64_pipe_busy": c["SQ_VALU_MFMA_BUSY_CYCLES"] / (1024.0 * c["GRBM_GUI_ACTIVE"] / 8.0),
+                "valu_instructions_per_wave": c["SQ_INSTS_VALU"] / c["SQ_WAVES"],
+                "note": "peak assumes 4 cycles per wave64 VALU instruction, which holds for fp64 only (fp32 / integer "
+                        "instructions issue in 2): frac is an upper bound of the issue utilisation",
+                "source": "profiles/sq_counters.json (rocprofv3 --pmc SQ_*), kernel sources sha1 %s = this tree" % sq["csrc_sha1"][:12]}
+    except (OSError, KeyError, ValueError, ZeroDivisionError):
+        pass
+    # ... and the same bound for the kernel the north star sets a target for (the covariance-propagation kernel k_map, stand-alone
+    # form, 256 instances): its VALU instruction count per launch against the issue rate of 1 024 SIMDs
+    roofline_issue_map = None
+    try:
+        if sq.get("csrc_sha1") == csrc_digest() and "k_map" in sq["kernels"] and "map" in kernels:
+            c = sq["kernels"]["k_map"]
+            peak = 256 * 4 * 2.4e9 / 4.0 / 1e9
+            us = kernels["map"]["avg_us_per_launch"]
+            roofline_issue_map = {
+                "kernel": "k_map", "bound": "valu-issue", "achieved": c["SQ_INSTS_VALU"] / (us * 1e-6) / 1e9, "peak": peak,
+                "unit": "G wave64 VALU instructions/s", "frac": c["SQ_INSTS_VALU"] / (us * 1e-6) / 1e9 / peak,
+                "valu_instructions_per_instance": c["SQ_INSTS_VALU"] / N_ENVS,
+                "us_of_pure_fp64_issue_per_cu": c["SQ_INSTS_VALU"] / N_ENVS / 4.0 * 4.0 / 2.4e3,
+                "avg_us_per_launch": us, "frac_hbm_peak": kernels["map"]["frac_hbm_peak"],
+                "wave_cycle_shares": {"issuing_valu": c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
+                                      "parked_on_waitcnt_or_barrier": c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"]},
+                "note": "one workgroup (8 waves, 4 SIMDs) per CU: an instance's VALU instructions / 4 SIMDs x 4 cycles is the time its CU "
+                        "needs to ISSUE them if they were all fp64 - the floor of the launch under this instruction count",
+                "source": "profiles/sq_counters.json, kernel sources sha1 %s = this tree" % sq["csrc_sha1"][:12]}
+    except (NameError, KeyError, ValueError, ZeroDivisionError):
+        pass
+    out.update({
+        "roofline": roofline, "roofline_issue": roofline_issue, "roofline_issue_k_map": roofline_issue_map, "kernels": kernels,
+        "event_pair_overhead_us": ev_over_us,
+        "slam_path": {"incremental_updates": inc_split[0], "full_solves": inc_split[1],
+                      "note": "belief updates served by the rank-k covariance update (csrc/k_inc.hip) / by the full solve since the "
+                              "engine was created (warm-up script included); the timed update is #37 of the iSAM2 counter: "
+                              "incremental (the full solve runs on the 10th updates that relinearise - update_cycle below)"},
+    })
+    if train is not None:
+        out["train_allreduce"] = train
+    # the secondary sections and the CPU baselines belong to the N = 1 line only (driver contract)
+    if not args.no_policy and world == 1:
+        out["policy_path"] = policy_bench(eng, dev)
+        out["config5_scale"] = config5_bench(local_rank)
+        out["full_fill"] = full_fill_bench(local_rank)
+        out["update_cycle"] = update_cycle_bench(local_rank)
+        # what a trajectory pays on average (nine rank-k updates and the relinearising tenth, no restore in the timed region):
+        # reported beside the headline, whose timed update is always a non-relinearising one
+        out["value_trajectory_average"] = {"value": out["update_cycle"]["env_steps_per_sec"], "unit": "env-steps/sec",
+                                           "what": "update_cycle: ten consecutive belief updates (37 -> 46 poses) incl. the 10th, relinearising one"}
+        out["capacity_256"] = capacity_bench(local_rank)
+        out["capacity_256"]["vs_headline"] = out["capacity_256"]["env_steps_per_sec"] / (out["value"] / world)
+        out["dqn_loop"] = dqn_loop_bench(local_rank)
+        out["a2c_loop"] = a2c_loop_bench(local_rank)
+    if not args.no_cpu_baseline and world == 1:
+        out["cpu_baseline"] = cpu_baseline()
+        out["gpu_over_cpu_thread"] = (out["value"] / world) / out["cpu_baseline"]["value"]
+        out["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
+
+
 def main():
     if len(sys.argv) == 4 and sys.argv[1] == "--cpu-worker":  # child of cpu_baseline_all_cores
         n, t = _cpu_worker((int(sys.argv[2]), float(sys.argv[3])))
@@ -618,13 +799,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-policy", action="store_true", help="skip the secondary decision-path / GCN measurements")
-    ap.add_argument("--no-train", action="store_true", help="skip the DQN-update / gradient all-reduce section")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also measure everything else: per-kernel event passes and rooflines, the SLAM "
+                         "path split, the DQN-update / gradient all-reduce section, the decision-path / loop / scale sections and "
+                         "the CPU baselines (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's envs) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-policy", action="store_true", help="with --full: skip the secondary decision-path / GCN measurements")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the DQN-update / gradient all-reduce section")
     ap.add_argument("--print-launch", action="store_true", help="print the multi-rank launch command and exit")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.print_launch):
         # no launcher around us: become one (one rank per GPU, the command the driver uses for N > 1)
         cmd = spawn_command([a for a in sys.argv[1:] if a != "--print-launch"], args.gpus)
@@ -688,161 +877,24 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # second pass: the same steps with HIP events on the engine stream around every launch (fused belief-step kernel)
-    eng.timing_enable(True)
-    eng.timing_read()
-    for _ in range(args.steps):
-        one_step()
-    tm_fused = eng.timing_read()
-    # third pass: the belief step launched as its three stage kernels, for the per-stage breakdown
-    eng.timing_enable(2)
-    for _ in range(args.steps):
-        one_step()
-    tm = eng.timing_read()
-    eng.timing_enable(False)
-    inc_split = eng.inc_stats(reset=True)  # (all launches so far were the headline update)
-    train = None
-    if not args.no_train:  # every rank takes part: the section contains collectives
-        train = train_allreduce_bench(eng, dev, dist, world)
-
+    total_steps = args.steps * N_ENVS * world
+    out = None if rank != 0 else {
+        "metric": "env-steps/sec (256 parallel envs, ~64-node graphs)", "value": total_steps / elapsed,
+        "unit": "env-steps/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "configs[1]: 256 envs/GPU, 40x40 map (V=1600), 100 landmarks, belief update at "
+                               "~%.0f-node graphs (P=%.1f poses, L=%.1f landmarks, M=%.0f factors) from a device snapshot"
+                               % (P + 1 + L, P + 1, L, M),
+                   "envs_per_gpu": N_ENVS, "map_size": MAP, "num_landmarks": NUM_LM, "parallelism": "env-sharded x%d" % world},
+        "ranks_in_process_group": (dist.get_world_size() if dist is not None else 1),
+        "collective_backend": (dist.get_backend() if dist is not None else "none"),
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    if args.full:
+        full_measurements(args, eng, dev, dist, world, local_rank, one_step, P, L, M, out)
     if rank == 0:
-        V = eng.rows * eng.cols
-        ab = algorithmic_bytes(P + 1, L, M, V)
-        kernels = {}
-        # an empty event pair is recorded once per step: its duration is the measurement overhead of a span
-        ev_over_us = tm["t7"][0] / max(tm["t7"][1], 1) * 1e3
-        for name in ("sim", "slam", "map", "copy"):
-            ms, n = tm[name]
-            if n == 0:
-                continue
-            avg_us = ms / n * 1e3 - ev_over_us
-            b = ab.get(name)
-            ent = {"avg_us_per_launch": avg_us, "launches": int(n)}
-            if b is not None:
-                ent["algorithmic_bytes_per_launch"] = b * N_ENVS
-                ent["achieved_GBs"] = b * N_ENVS / (avg_us * 1e-6) / 1e9
-                ent["frac_hbm_peak"] = ent["achieved_GBs"] / HBM_PEAK_GBS
-            kernels[name] = ent
-        # the dominant kernel of the timed region is the fused belief step (simulate + SLAM + map of one instance per
-        # workgroup); its algorithmic bytes are the sum of the three stages'
-        ev2 = tm_fused["t7"][0] / max(tm_fused["t7"][1], 1) * 1e3
-        if tm_fused["step"][1] > 0:
-            dom = "step"
-            step_us = tm_fused["step"][0] / tm_fused["step"][1] * 1e3 - ev2
-            step_bytes = (ab["sim"] + ab["slam"] + ab["map"]) * N_ENVS
-            kernels["step"] = {"avg_us_per_launch": step_us, "launches": int(tm_fused["step"][1]),
-                               "algorithmic_bytes_per_launch": step_bytes, "achieved_GBs": step_bytes / (step_us * 1e-6) / 1e9,
-                               "frac_hbm_peak": step_bytes / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                               "note": "fused kernel used by drlgx_step; sim/slam/map entries are the same work launched as three kernels"}
-            if tm_fused["copy"][1] > 0:
-                kernels["copy"]["avg_us_per_launch"] = tm_fused["copy"][0] / tm_fused["copy"][1] * 1e3 - ev2
-        else:  # capacities beyond the fused kernel
-            dom = max(("sim", "slam", "map"), key=lambda k: kernels[k]["avg_us_per_launch"])
-        roofline = {"kernel": {"sim": "k_sim_step", "slam": "k_slam", "map": "k_map", "step": "k_step"}[dom], "bound": "hbm",
-                    "achieved": kernels[dom]["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": kernels[dom]["frac_hbm_peak"], "traffic": None,
-                    "avg_us_per_launch": kernels[dom]["avg_us_per_launch"]}
-        # HBM traffic per launch comes from separate rocprofv3 --pmc passes over this same command (counters cannot be
-        # read in-process): profiles/pmc_traffic.json holds the corrected per-kernel figures (scripts/rocpd_pmc.py) and
-        # the digest of the kernel sources they were measured on - traffic is reported only when that is THIS tree
-        roofline["algorithmic_bytes_per_launch"] = kernels[dom]["algorithmic_bytes_per_launch"]
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-                pmc = json.load(f)
-            if pmc.get("csrc_sha1") == csrc_digest():
-                roofline["traffic"] = pmc["kernels"][roofline["kernel"]]["hbm_traffic_bytes_per_launch"]
-                roofline["traffic_source"] = ("profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, bytes/launch), "
-                                              "measured on kernel sources sha1 %s = this tree" % pmc["csrc_sha1"][:12])
-            else:
-                roofline["traffic_source"] = "profiles/pmc_traffic.json is from other kernel sources (sha1 %s): not reported" % str(pmc.get("csrc_sha1"))[:12]
-        except (OSError, KeyError, ValueError):
-            pass
-        # second roofline entry, for the bound the SQ counters support: the belief step is neither an HBM nor an MFMA
-        # kernel - its waves spend most of their cycles parked on waitcnt / barriers of dependent fp64 chains - so the
-        # closest throughput ceiling is VALU instruction issue (one wave64 instruction per SIMD per 4 cycles).  Counters
-        # come from profiles/sq_counters.json (scripts/collect_profiles.sh), quoted only for THIS tree's kernel sources
-        roofline_issue = None
-        try:
-            with open(os.path.join(ROOT, "profiles", "sq_counters.json")) as f:
-                sq = json.load(f)
-            if sq.get("csrc_sha1") == csrc_digest():
-                c = sq["kernels"][roofline["kernel"]]
-                peak = 256 * 4 * 2.4e9 / 4.0 / 1e9  # G wave64 VALU instructions/s: 1024 SIMDs, 4 cycles each
-                ach = c["SQ_INSTS_VALU"] / (roofline["avg_us_per_launch"] * 1e-6) / 1e9
-                wc = c["SQ_WAVE_CYCLES"]
-                roofline_issue = {
-                    "kernel": roofline["kernel"], "bound": "valu-issue", "achieved": ach, "peak": peak,
-                    "unit": "G wave64 VALU instructions/s", "frac": ach / peak,
-                    "wave_cycle_shares": {"issuing_any": c["SQ_ACTIVE_INST_ANY"] / wc, "issuing_valu": c["SQ_ACTIVE_INST_VALU"] / wc,
-                                          "parked_on_waitcnt_or_barrier": c["SQ_WAIT_ANY"] / wc,
-                                          "issue_stalled": c["SQ_WAIT_INST_ANY"] / wc},
-                    "mfma_f64_pipe_busy": c["SQ_VALU_MFMA_BUSY_CYCLES"] / (1024.0 * c["GRBM_GUI_ACTIVE"] / 8.0),
-                    "valu_instructions_per_wave": c["SQ_INSTS_VALU"] / c["SQ_WAVES"],
-                    "note": "peak assumes 4 cycles per wave64 VALU instruction, which holds for fp64 only (fp32 / integer "
-                            "instructions issue in 2): frac is an upper bound of the issue utilisation",
-                    "source": "profiles/sq_counters.json (rocprofv3 --pmc SQ_*), kernel sources sha1 %s = this tree" % sq["csrc_sha1"][:12]}
-        except (OSError, KeyError, ValueError, ZeroDivisionError):
-            pass
-        # ... and the same bound for the kernel the north star sets a target for (the covariance-propagation kernel k_map, stand-alone
-        # form, 256 instances): its VALU instruction count per launch against the issue rate of 1 024 SIMDs
-        roofline_issue_map = None
-        try:
-            if sq.get("csrc_sha1") == csrc_digest() and "k_map" in sq["kernels"] and "map" in kernels:
-                c = sq["kernels"]["k_map"]
-                peak = 256 * 4 * 2.4e9 / 4.0 / 1e9
-                us = kernels["map"]["avg_us_per_launch"]
-                roofline_issue_map = {
-                    "kernel": "k_map", "bound": "valu-issue", "achieved": c["SQ_INSTS_VALU"] / (us * 1e-6) / 1e9, "peak": peak,
-                    "unit": "G wave64 VALU instructions/s", "frac": c["SQ_INSTS_VALU"] / (us * 1e-6) / 1e9 / peak,
-                    "valu_instructions_per_instance": c["SQ_INSTS_VALU"] / N_ENVS,
-                    "us_of_pure_fp64_issue_per_cu": c["SQ_INSTS_VALU"] / N_ENVS / 4.0 * 4.0 / 2.4e3,
-                    "avg_us_per_launch": us, "frac_hbm_peak": kernels["map"]["frac_hbm_peak"],
-                    "wave_cycle_shares": {"issuing_valu": c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
-                                          "parked_on_waitcnt_or_barrier": c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"]},
-                    "note": "one workgroup (8 waves, 4 SIMDs) per CU: an instance's VALU instructions / 4 SIMDs x 4 cycles is the time its CU "
-                            "needs to ISSUE them if they were all fp64 - the floor of the launch under this instruction count",
-                    "source": "profiles/sq_counters.json, kernel sources sha1 %s = this tree" % sq["csrc_sha1"][:12]}
-        except (NameError, KeyError, ValueError, ZeroDivisionError):
-            pass
-        total_steps = args.steps * N_ENVS * world
-        out = {
-            "metric": "env-steps/sec (256 parallel envs, ~64-node graphs)", "value": total_steps / elapsed,
-            "unit": "env-steps/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "configs[1]: 256 envs/GPU, 40x40 map (V=1600), 100 landmarks, belief update at "
-                                   "~%.0f-node graphs (P=%.1f poses, L=%.1f landmarks, M=%.0f factors) from a device snapshot"
-                                   % (P + 1 + L, P + 1, L, M),
-                       "envs_per_gpu": N_ENVS, "map_size": MAP, "num_landmarks": NUM_LM, "parallelism": "env-sharded x%d" % world},
-            "roofline": roofline, "roofline_issue": roofline_issue, "roofline_issue_k_map": roofline_issue_map, "kernels": kernels,
-            "event_pair_overhead_us": ev_over_us,
-            "slam_path": {"incremental_updates": inc_split[0], "full_solves": inc_split[1],
-                          "note": "belief updates served by the rank-k covariance update (csrc/k_inc.hip) / by the full solve since the "
-                                  "engine was created (warm-up script included); the timed update is #37 of the iSAM2 counter: "
-                                  "incremental (the full solve runs on the 10th updates that relinearise - update_cycle below)"},
-            "ranks_in_process_group": (dist.get_world_size() if dist is not None else 1),
-            "collective_backend": (dist.get_backend() if dist is not None else "none"),
-        }
-        if train is not None:
-            out["train_allreduce"] = train
-        # the secondary sections and the CPU baselines belong to the N = 1 line only (driver contract)
-        if not args.no_policy and world == 1:
-            out["policy_path"] = policy_bench(eng, dev)
-            out["config5_scale"] = config5_bench(local_rank)
-            out["full_fill"] = full_fill_bench(local_rank)
-            out["update_cycle"] = update_cycle_bench(local_rank)
-            # what a trajectory pays on average (nine rank-k updates and the relinearising tenth, no restore in the timed region):
-            # reported beside the headline, whose timed update is always a non-relinearising one
-            out["value_trajectory_average"] = {"value": out["update_cycle"]["env_steps_per_sec"], "unit": "env-steps/sec",
-                                               "what": "update_cycle: ten consecutive belief updates (37 -> 46 poses) incl. the 10th, relinearising one"}
-            out["capacity_256"] = capacity_bench(local_rank)
-            out["capacity_256"]["vs_headline"] = out["capacity_256"]["env_steps_per_sec"] / (out["value"] / world)
-            out["dqn_loop"] = dqn_loop_bench(local_rank)
-            out["a2c_loop"] = a2c_loop_bench(local_rank)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline()
-            out["gpu_over_cpu_thread"] = (out["value"] / world) / out["cpu_baseline"]["value"]
-            out["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
         print(json.dumps(out))
     eng.close()
     if dist is not None:

@@ -9,7 +9,7 @@ tag=${1:-r02}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-policy --no-train"
+BENCH="python bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-policy --no-train"
 db() { find "$1" -name '*_results.db' | head -1; }
 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats -- $BENCH > $out/bench_under_rocprof.json 2> $out/rocprof_stats.err
 python scripts/rocpd_summary.py "$(db /tmp/prof_stats)" > $out/kernel_stats.csv
@@ -27,8 +27,8 @@ ls -la $out
 [ -s $out/pmc_traffic.json ] && cp $out/pmc_traffic.json profiles/pmc_traffic.json
 [ -s $out/sq_counters.json ] && cp $out/sq_counters.json profiles/sq_counters.json
 # the bench line itself, the 2-rank control flow on one device (gloo), and the step-vs-trajectory-length tables
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err
-DRLGX_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 50 --warmup 5 > $out/bench_2ranks_gloo.json 2> $out/bench_2ranks_gloo.err
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err
+DRLGX_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 50 --warmup 5 --full > $out/bench_2ranks_gloo.json 2> $out/bench_2ranks_gloo.err
 PP_SAMPLE=39,49 timeout 300 python scripts/bench_vs_poses.py 206 100 phases > $out/vs_poses_100lm.txt 2>&1
 timeout 300 python scripts/bench_vs_poses.py 206 8 phases > $out/vs_poses_8lm.txt 2>&1
 # the look-ahead workload: kernel stats and HBM traffic of its kernels (k_step_loop: a candidate's whole action list per launch)

@@ -58,6 +58,6 @@ if json_out:
     import bench  # noqa: E402  (csrc_digest)
     with open(json_out, "w") as f:
         json.dump({"csrc_sha1": bench.csrc_digest(),
-                   "source": "rocprofv3 --pmc SQ_* (two passes of 8 SQ counters + GRBM_GUI_ACTIVE) on `python bench.py --steps 50 "
+                   "source": "rocprofv3 --pmc SQ_* (two passes of 8 SQ counters + GRBM_GUI_ACTIVE) on `python bench.py --steps 50 --full "
                              "--warmup 5 --no-cpu-baseline --no-policy --no-train`; averages per dispatch",
                    "kernels": {k: {c: v[1] for c, v in by[k].items()} for k in by}}, f, indent=1)

@@ -142,7 +142,7 @@ def test_bench_two_gpus_over_rccl():
     """`bench.py --gpus 2` launched the way the driver launches it (torch.distributed.run, one rank per GPU): one JSON line from
     rank 0, two ranks in the group, backend nccl, a measured gradient all-reduce."""
     import json
-    out = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-policy"])
+    out = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-policy"])
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
