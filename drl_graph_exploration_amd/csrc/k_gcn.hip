@@ -1321,6 +1321,15 @@ __global__ __launch_bounds__(256) void k_linear_out(int N, int hidden, int out_d
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + wave;
   if (n >= N) return;
+  if ((reinterpret_cast<uintptr_t>(Wf) | reinterpret_cast<uintptr_t>(H2m)) & 15) {  // (the C ABI takes any Wf: one column per lane)
+    for (int o = 0; o < out_dim; ++o) {
+      float s = 0.f;
+      for (int c = lane; c < hidden; c += 64) s += H2m[(size_t)n * hidden + c] * Wf[(size_t)o * hidden + c];
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+      if (lane == 0) out[(size_t)n * out_dim + o] = s + bf[o];
+    }
+    return;
+  }
   const float4 *h = reinterpret_cast<const float4 *>(H2m + (size_t)n * hidden);
   const int h4 = hidden >> 2;
   for (int o = 0; o < out_dim; ++o) {

@@ -612,3 +612,127 @@ def test_a2c_update_without_synchronisations_equals_the_masked_select_form(tmp_p
     assert abs(l0 - l1) <= 1e-6 * max(1.0, abs(l1)) and abs(e0 - e1) <= 1e-6 * max(1.0, abs(e1)), (l0, l1, e0, e1)
     for a, b in zip(p0, p1):
         assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- edges of the trunk's dispatch
+def graph_of(n_nodes, seed, dev):
+    """One random graph of exactly n_nodes nodes (a single node has no edge), both directions of every edge."""
+    g = torch.Generator().manual_seed(seed)
+    m = 0 if n_nodes == 1 else int(torch.randint(n_nodes, 3 * n_nodes, (1,), generator=g))
+    src, dst = torch.randint(0, n_nodes, (m,), generator=g), torch.randint(0, n_nodes, (m,), generator=g)
+    keep = src != dst
+    src, dst = src[keep], dst[keep]
+    w = torch.rand(src.shape[0], generator=g) * 5.9 + 0.1
+    x = torch.randn(n_nodes, 5, generator=g)
+    x[:, 4] = torch.randint(-1, 2, (n_nodes,), generator=g).float()
+    return x.to(dev), torch.stack([torch.cat([src, dst]), torch.cat([dst, src])]).to(dev), torch.cat([w, w]).to(dev)
+
+
+def at_4_bytes(t):
+    """A copy of t that starts 4 bytes past a 16-byte boundary (a view into a larger allocation)."""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def check_trunk_against_float64(x, ei, ea, out_dim, with_mask, unaligned=False, seed=0):
+    """gcn_forward_raw / gcn_backward_raw against gcn_ref in float64, under the rule of
+    test_gcn_forward_backward_matches_torch_reference.  unaligned: x, Wf and the dropout mask are passed as views at a
+    4-byte offset (the trunk's unvectorised branches: k_dz2's scalar loop and thin_tn for read-outs of <= 8 outputs, the
+    unvectorised k_gemm for the wider read-out, the 64 x 64 fallback of gemm_wide for the masked layer-2 product)."""
+    from drl_graph_exploration_amd.networks import gcn_backward_raw, gcn_forward_raw
+    dev = x.device
+    N = x.shape[0]
+    P = make_params(dev, out_dim, seed)
+    mask = None
+    if with_mask:
+        mask = (torch.rand(N, 1000, device=dev, generator=torch.Generator(device=dev).manual_seed(11 + N)) >= 0.5).float() * 2.0
+    names = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fully_con1.weight", "fully_con1.bias")
+    params = [P[n].detach() for n in names]
+    xk, mk = x, mask
+    if unaligned:
+        xk, params[4] = at_4_bytes(x), at_4_bytes(params[4])
+        mk = at_4_bytes(mask) if mask is not None else None
+    out, saved = gcn_forward_raw(xk, ei, ea, params, mk)
+    wgt = torch.randn(N, out_dim, device=dev, generator=torch.Generator(device=dev).manual_seed(3 + N))
+    grads = [torch.full_like(p, float("nan")) for p in params]
+    gcn_backward_raw(saved, wgt, grads)
+    torch.cuda.synchronize()
+    ref_params = {k: v.detach().double().clone().requires_grad_(True) for k, v in P.items()}
+    ref = gcn_ref.gcn_forward(ref_params, x.double(), ei, ea.double(), None if mask is None else mask.double())
+    assert out.shape == ref.shape == (N, out_dim)
+    assert rel_err(out.double(), ref.detach()) < 1e-5
+    with torch.no_grad():
+        ref32 = gcn_ref.gcn_forward({k: v.detach() for k, v in P.items()}, x, ei, ea, mask)
+    assert rel_err(out, ref32) < 2e-4
+    (ref * wgt.double()).sum().backward()
+    p32 = {k: v.detach().clone().requires_grad_(True) for k, v in P.items()}
+    (gcn_ref.gcn_forward(p32, x, ei, ea, mask) * wgt).sum().backward()
+    for name, g in zip(names, grads):
+        g, r = g.double(), ref_params[name].grad
+        assert torch.isfinite(g).all(), name
+        e_ours = float((g - r).norm() / r.norm())
+        e_torch32 = float((p32[name].grad.double() - r).norm() / r.norm())
+        m_ours, m_torch32 = rel_err(g, r), rel_err(p32[name].grad.double(), r)
+        assert m_ours < max(2e-3, 3.0 * m_torch32), (name, m_ours, m_torch32)
+        assert e_ours < max(1e-4, 3.0 * e_torch32), (name, e_ours, e_torch32)
+
+
+@pytest.mark.parametrize("n_nodes,out_dim,with_mask", [(150, 1, True), (150, 8, True), (150, 100, True), (1903, 1, True), (1903, 8, False),
+                                                       (1903, 100, True)])
+def test_trunk_with_unaligned_operands(n_nodes, out_dim, with_mask):
+    """The C ABI takes any pointer: x, Wf and the dropout mask 4 bytes off a 16-byte boundary (1 903 nodes: the tall-tile
+    batches, whose aligned products take k_gemm_wide)."""
+    dev = torch.device("cuda", 0)
+    x, ei, ea = batch_of_about(n_nodes, 500 + n_nodes, dev)
+    check_trunk_against_float64(x, ei, ea, out_dim, with_mask, unaligned=True, seed=out_dim)
+
+
+@pytest.mark.parametrize("out_dim", [9, 12, 16, 17])
+def test_trunk_read_out_widths(out_dim):
+    """Widths just above the one-pass kernels' 8 outputs, and K = out_dim below / at / just above one 16-wide K slice of the
+    dZ2 product."""
+    dev = torch.device("cuda", 0)
+    x, ei, ea = batch_of_about(300, 600 + out_dim, dev)
+    check_trunk_against_float64(x, ei, ea, out_dim, True, seed=out_dim)
+
+
+@pytest.mark.parametrize("n_nodes", [1, 2, 3, 5, 63, 64, 65, 129])
+@pytest.mark.parametrize("out_dim", [1, 100])
+def test_trunk_tiny_batches(n_nodes, out_dim):
+    """A single node without edges, and node counts around the 64-row tiles."""
+    dev = torch.device("cuda", 0)
+    x, ei, ea = graph_of(n_nodes, 700 + n_nodes, dev)
+    assert (ei.shape[1] == 0) == (n_nodes == 1)
+    check_trunk_against_float64(x, ei, ea, out_dim, n_nodes % 2 == 1, seed=n_nodes)
+
+
+_SWITCH_CHILD = """
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+import test_gpu_gcn as T
+dev = torch.device("cuda", 0)
+for n, out_dim in ((65, 1), (129, 100), (1101, 1), (1903, 100), (3050, 1)):
+    x, ei, ea = T.batch_of_about(n, 900 + n, dev)
+    T.check_trunk_against_float64(x, ei, ea, out_dim, True, seed=n)
+"""
+
+
+def test_gemm_development_switches_compute_the_same_trunk():
+    """DRLGX_GEMM_DL=0, DRLGX_GEMM_TILE=1, DRLGX_GEMM_WIDE=0 and DRLGX_GEMM_WIDE=6..10 (read once per process) each in a
+    fresh process, one after the other: the trunk against float64 at node counts on the 64-row and the tall tiles' edges.
+    Stops at the first child that fails, times out or dies by a signal."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    for name, value in [("DRLGX_GEMM_DL", "0"), ("DRLGX_GEMM_TILE", "1"), ("DRLGX_GEMM_WIDE", "0")] + \
+                       [("DRLGX_GEMM_WIDE", str(v)) for v in range(6, 11)]:
+        env = dict(os.environ, **{name: value})
+        try:
+            r = subprocess.run([sys.executable, "-c", _SWITCH_CHILD, here], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        except subprocess.TimeoutExpired:
+            pytest.fail("%s=%s: the child process timed out" % (name, value))
+        assert r.returncode == 0, "%s=%s: exit status %d\n%s" % (name, value, r.returncode, (r.stdout + r.stderr)[-3000:])
