@@ -196,6 +196,11 @@ struct LaunchSel {
   const unsigned char *simlog = nullptr;
   size_t simlog_roll = 0;
   int simlog_act = 0;
+  // >= 0: a lazy restore (drlgx_restore) left the virtual-map planes of instance base + i in instance vm_from + i (its
+  // snapshot).  The map stage rebuilds every cell of an accepted move without reading them; where it does not rebuild (an
+  // instance switched off, a rejected move, a capacity error) it copies them over, so that after the launch every selected
+  // instance holds its planes again.
+  int vm_from = -1;
   __host__ __device__ __forceinline__ int cap(int P_max) const { return pcap > 0 && pcap < P_max ? pcap : P_max; }
   __device__ __forceinline__ bool map_on(int i) const {
     return !(map_last_only && n_act) || act_idx == n_act[i] - 1;
@@ -712,7 +717,8 @@ bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound);
 void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t st, int n, const int32_t *src,
                        const int32_t *dst, int src_off, int dst_off, int skip_mask,  // skip fields with cls & mask
                        const int *cnt = nullptr,  // S.cnt: copy the live part of per-pose / -landmark / -factor fields only
-                       const DrlgxState *panel = nullptr);  // &S: the same launch copies the instances' covariance panels too
+                       const DrlgxState *panel = nullptr,  // &S: the same launch copies the instances' covariance panels too
+                       int only_cls = -1);  // >= 0: the fields of this class only (a class-0 field cannot be skipped by the mask)
 void drlgx_launch_rebase(const DrlgxState &S, hipStream_t st, int base0, int n);
 // head of a packed status read: the status word + n_envs pose counts, rounded up to 16 bytes (k_fetch_pack)
 inline size_t drlgx_fetch_head_bytes(int n_envs) { return ((size_t)(n_envs + 1) * sizeof(int) + 15) & ~(size_t)15; }

@@ -82,19 +82,32 @@ struct drlgx_engine {
   int *fm2_iscratch = nullptr;
   int32_t *fm2_slot = nullptr;
   size_t fm2_sig_stride = 0, fm2_scratch_stride = 0;
+  // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
+  // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
+  // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
+  int owed_slot = -1;
+  bool restore_eager = false;
 };
 
-// every entry point makes the engine's device current (a process may drive several engines on several devices)
-#define DRLGX_ENTER(e)                          \
+// every entry point makes the engine's device current (a process may drive several engines on several devices) and - all but
+// those that neither read nor write instance state, and drlgx_restore / drlgx_step themselves (DRLGX_ENTER_OWING) - settles
+// what a lazy restore still owes, so that no entry point can see an env without its planes
+#define DRLGX_ENTER_OWING(e)                    \
   do {                                          \
     if (e) {                                    \
       (void)hipSetDevice((e)->device);          \
       state_sync(e);                            \
     }                                           \
   } while (0)
+#define DRLGX_ENTER(e)                          \
+  do {                                          \
+    DRLGX_ENTER_OWING(e);                       \
+    if (e) settle(e);                           \
+  } while (0)
 
 struct drlgx_engine;
 static void state_sync(drlgx_engine *e);
+static void settle(drlgx_engine *e);
 
 namespace {
 
@@ -218,6 +231,8 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
     e->la_presim = !(lp && lp[0] == '0');
     const char *ll = getenv("DRLGX_LOOKAHEAD_LOOP");  // 0: one launch per action index (the A/B of the look-ahead tests)
     e->la_loop = !(ll && ll[0] == '0');
+    const char *re = getenv("DRLGX_RESTORE_EAGER");  // 1: a restore copies the virtual-map planes too (the A/B of the lazy restore)
+    e->restore_eager = re && re[0] == '1';
   }
   e->snap_pbound.assign(cfg->max_snapshots > 0 ? cfg->max_snapshots : 0, std::vector<int>(n_envs, cfg->max_poses));
   S.P_max = cfg->max_poses;
@@ -505,8 +520,19 @@ static void state_sync(drlgx_engine *e) {
   memcpy(e->state_shadow, &e->S, sizeof(DrlgxState));
 }
 
+// snapshot instance of env 0 in slot `slot`
+static int snapshot_base(const drlgx_engine *e, int slot) { return 2 * e->S.n_envs + e->S.n_roll + slot * e->S.n_envs; }
+
+// what a lazy restore still owes: the planes of every env from the restored slot, in one copy
+static void settle(drlgx_engine *e) {
+  if (e->owed_slot < 0) return;
+  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, e->S.n_envs, nullptr, nullptr, snapshot_base(e, e->owed_slot), 0, 0,
+                    nullptr, nullptr, 1);
+  e->owed_slot = -1;
+}
+
 int drlgx_destroy(drlgx_engine *e) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
   hipSetDevice(e->device);
   hipDeviceSynchronize();
@@ -525,7 +551,7 @@ int drlgx_destroy(drlgx_engine *e) {
 }
 
 int drlgx_set_stream(drlgx_engine *e, void *hip_stream) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);  // (callers re-bind before a restore and a step: the debt follows the engine onto the new stream)
   if (!e) return DRLGX_E_INVALID;
   hipStream_t s = (hip_stream == reinterpret_cast<void *>(-1)) ? e->own_stream : reinterpret_cast<hipStream_t>(hip_stream);
   if (s == e->stream) return DRLGX_OK;  // cheap when nothing changes: callers re-bind before every call
@@ -535,7 +561,7 @@ int drlgx_set_stream(drlgx_engine *e, void *hip_stream) {
 }
 
 int drlgx_synchronize(drlgx_engine *e) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return DRLGX_OK;
@@ -592,13 +618,13 @@ static int status_fetch(drlgx_engine *e, const void *src_dev, size_t bytes, void
 }
 
 int drlgx_status_host(drlgx_engine *e) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
   return status_fetch(e, nullptr, 0, nullptr);
 }
 
 int drlgx_status_fetch_host(drlgx_engine *e, const void *src_dev, size_t bytes, void *dst_host) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e || (bytes > 0 && (!src_dev || !dst_host))) return DRLGX_E_INVALID;
   // the caller's bytes ride on the status read's synchronisation (a vector step of a trainer needs a handful of small device
   // results on the host: every separate read drains the stream again)
@@ -633,9 +659,12 @@ int drlgx_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const uint3
 }
 
 int drlgx_step(drlgx_engine *e, const double *odom_dev, const uint8_t *active_dev) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e || !odom_dev) return DRLGX_E_INVALID;
   LaunchSel sel{0, e->S.n_envs, active_dev, nullptr, 0};
+  // every form below runs the map stage (kmap::map_body) for every env: it takes over what a lazy restore owes
+  if (e->owed_slot >= 0) sel.vm_from = snapshot_base(e, e->owed_slot);
+  e->owed_slot = -1;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
   sel.pcap = pb;  // (the kernels size their per-pose LDS tables with the launch's bound, not with the capacity)
   for (int &v : e->pbound) v = std::min(v + 1, e->S.P_max);
@@ -1318,12 +1347,15 @@ int drlgx_snapshot(drlgx_engine *e, int slot) {
 }
 
 int drlgx_restore(drlgx_engine *e, int slot) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);  // (a debt of an earlier restore is void: this one replaces every plane it covered)
   if (!e || slot < 0 || slot >= e->S.cfg.max_snapshots) return DRLGX_E_INVALID;
   const DrlgxState &S = e->S;
   ScopedTimer t(e, 3);
-  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr,
-                    2 * S.n_envs + S.n_roll + slot * S.n_envs, 0, 0, e->S.cnt, &S);
+  // lazy: everything but the virtual-map planes (43 % of an instance's live bytes at the bench state), which the next belief step
+  // rebuilds without reading them - or settle() copies before anything else touches the envs
+  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, snapshot_base(e, slot), 0,
+                    e->restore_eager ? 0 : 1, e->S.cnt, &S);
+  e->owed_slot = e->restore_eager ? -1 : slot;
   e->pbound = e->snap_pbound[slot];
   return check_launch(e);
 }
@@ -1353,7 +1385,7 @@ int drlgx_debug_phase_clocks_host(drlgx_engine *e, int arm, int64_t out[64]) {
 
 // ---- incremental belief update: how many SLAM updates took the rank-k path / the full solve ------------------
 int drlgx_inc_stats_host(drlgx_engine *e, int64_t out[2], int reset) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e || !out) return DRLGX_E_INVALID;
   out[0] = out[1] = -1;  // -1: the incremental path is disabled (DRLGX_INCREMENTAL=0 or the panels exceed the memory budget)
   if (!e->S.inc_stats) return DRLGX_OK;
@@ -1368,7 +1400,7 @@ int drlgx_inc_stats_host(drlgx_engine *e, int64_t out[2], int reset) {
 
 // ---- timing ------------------------------------------------------------------------------------
 int drlgx_timing_enable(drlgx_engine *e, int on) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
   e->timing = on != 0;
   e->per_stage = on == 2;
@@ -1376,7 +1408,7 @@ int drlgx_timing_enable(drlgx_engine *e, int on) {
 }
 
 int drlgx_timing_read_host(drlgx_engine *e, double ms[DRLGX_N_TIMERS], int64_t launches[DRLGX_N_TIMERS]) {
-  DRLGX_ENTER(e);
+  DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
   HIPCHK(e, hipStreamSynchronize(e->stream));
   for (auto &sp : e->spans) {

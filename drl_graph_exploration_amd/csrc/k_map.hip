@@ -193,17 +193,37 @@ struct LadderEntry {
 #endif
 constexpr int kPairsPerPose = 40;  // in-range cells per pose the compact stage has room for (the disc of radius max_range
                                    // holds ~28 cell centres of the 7 x 7 window, never more than 32)
+// the planes of instance s -> d, by the whole workgroup (LaunchSel::vm_from: an instance whose planes this launch does not rebuild)
+__device__ __forceinline__ void copy_planes(const DrlgxState &S, int s, int d) {
+  const size_t V = S.V, Vu4 = (size_t)S.Vu / 4;
+  for (size_t v = drlgx_tid(); v < V; v += kThreads) {
+    S.vm_prob[(size_t)d * V + v] = S.vm_prob[(size_t)s * V + v];
+    S.vm_tr[(size_t)d * V + v] = S.vm_tr[(size_t)s * V + v];
+  }
+  for (size_t v = drlgx_tid(); v < 3 * V; v += kThreads) S.vm_info[(size_t)d * 3 * V + v] = S.vm_info[(size_t)s * 3 * V + v];
+  const uint32_t *us = reinterpret_cast<const uint32_t *>(S.vm_upd + (size_t)s * S.Vu);  // (Vu: a multiple of 4 bytes)
+  uint32_t *ud = reinterpret_cast<uint32_t *>(S.vm_upd + (size_t)d * S.Vu);
+  for (size_t v = drlgx_tid(); v < Vu4; v += kThreads) ud[v] = us[v];
+}
 template <bool kCompact = false>
 __device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &sel, int rebuild, int chunk, bool handed = false,
                                          const double *lm_lds = nullptr, LadderEntry lo = LadderEntry{false, 0.0, 0u, -1, 0, 0}) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6;
   const int bi = drlgx_bid();
-  if (!sel.on(bi) || !sel.map_on(bi)) return;
   const int inst = sel.base + bi;
+  // (a lazy restore left the planes in the snapshot: every exit below that does not rebuild them copies them over)
+  const int owed_from = sel.vm_from >= 0 ? sel.vm_from + bi : -1;
+  if (!sel.on(bi) || !sel.map_on(bi)) {
+    if (owed_from >= 0) copy_planes(S, owed_from, inst);
+    return;
+  }
   const int *cnt = S.cnt + (size_t)inst * DRLGX_CNT_STRIDE;
   // a rejected move leaves the belief as it was: nothing to rebuild, unless this is the one rebuild of a rollout
-  if ((lo.P >= 0 ? lo.flag : cnt[C_FLAG]) && !sel.map_last_only) return;
+  if ((lo.P >= 0 ? lo.flag : cnt[C_FLAG]) && !sel.map_last_only) {
+    if (owed_from >= 0) copy_planes(S, owed_from, inst);
+    return;
+  }
   const drlgx_config &cfg = S.cfg;
   const int P = lo.P >= 0 ? lo.P : cnt[C_P], L = lo.P >= 0 ? lo.L : cnt[C_L];
   const int V = S.V, cols = S.cols, rows = S.rows, W = S.win;
@@ -211,6 +231,7 @@ __device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &s
   const int pc = sel.cap(S.P_max);
   if (rebuild && P > pc) {  // (the host's bound was wrong: flag it, touch nothing)
     if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+    if (owed_from >= 0) copy_planes(S, owed_from, inst);
     return;
   }
   double *sp = smem;                   // [pc][4]
@@ -663,6 +684,10 @@ __device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &s
     }
   } else {
     // reductions only (after reset): the cells are read back
+    if (owed_from >= 0) {
+      copy_planes(S, owed_from, inst);
+      __syncthreads();
+    }
     const int extg = 20;
     for (int v = tid; v < V; v += kThreads) {
       const int row = v / cols, col = v - row * cols;

@@ -9,8 +9,9 @@ namespace {
 
 // the incremental update's covariance panel (csrc/k_inc.hip) of instance s -> d: the live rows / columns only.  Block
 // `part` of kCopySplit copies every kCopySplit-th group of 8 rows, 32 threads x 16 bytes per row, four rows' loads in
-// flight per thread
-constexpr int kCopySplit = 4;
+// flight per thread.  (Eight parts since the lazy restore leaves the virtual-map planes to the step: the panels are then two thirds
+// of a restore's bytes - 11.9 against 12.3 us per restore with four parts, 13.2 with sixteen; profiles/lazy_restore_ab.txt)
+constexpr int kCopySplit = 8;
 __device__ __forceinline__ void copy_panel_part(const DrlgxState &S, int s, int d, int part) {
   const int *ms = S.jc_meta + (size_t)s * 4;
   int *md = S.jc_meta + (size_t)d * 4;
@@ -39,11 +40,11 @@ __device__ __forceinline__ void copy_panel_part(const DrlgxState &S, int s, int 
     for (int e = threadIdx.x; e < 6 * P; e += 256) S.jd[(size_t)d * S.P_max * 6 + e] = S.jd[(size_t)s * S.P_max * 6 + e];
 }
 
-// copy every field of instance src[i] to dst[i] whose class is not in skip_mask and - panel != 0 - its covariance panel:
-// one launch for everything an instance copy (snapshot / restore, env -> base -> rollout) moves
+// copy every field of instance src[i] to dst[i] whose class is not in skip_mask (and is only_cls, if that is >= 0) and - panel
+// != 0 - its covariance panel: one launch for everything an instance copy (snapshot / restore, env -> base -> rollout) moves
 __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields, int n_fields, const int32_t *src,
-                                                        const int32_t *dst, int src_off, int dst_off, int skip_mask, const int *cnt,
-                                                        DrlgxState S, int panel) {
+                                                        const int32_t *dst, int src_off, int dst_off, int skip_mask, int only_cls,
+                                                        const int *cnt, DrlgxState S, int panel) {
   // grid = (instances, fields [+ kCopySplit]): every (instance, field) slice is streamed by its own workgroup with
   // 16-byte accesses when the slice is 16-byte aligned (all large fields are)
   // (x = field, y = instance: consecutive workgroups stream slices of DIFFERENT arrays - with x = instance the workgroups in flight
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields
     return;
   }
   // (one workgroup for ALL the fields of a few bytes per instance was measured: 21.4 against 17.8 us - seven dependent round trips)
-  if (fields[f].cls & skip_mask) return;
+  if ((fields[f].cls & skip_mask) || (only_cls >= 0 && fields[f].cls != only_cls)) return;
   const size_t stride = fields[f].stride;
   const char *sb = fields[f].base + (size_t)s * stride;
   char *db = fields[f].base + (size_t)d * stride;
@@ -304,12 +305,13 @@ void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length,
   hipLaunchKernelGGL(k_cov_array, dim3((S.V + 255) / 256, S.n_envs), dim3(256), 0, st, S, length, angle);
 }
 void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t st, int n, const int32_t *src,
-                       const int32_t *dst, int src_off, int dst_off, int skip_mask, const int *cnt, const DrlgxState *panel) {
+                       const int32_t *dst, int src_off, int dst_off, int skip_mask, const int *cnt, const DrlgxState *panel,
+                       int only_cls) {
   if (n <= 0) return;
   const bool with_panel = panel && panel->jc;
   const dim3 cgrid(n_fields + (with_panel ? kCopySplit : 0), n);
   hipLaunchKernelGGL(k_copy_instances, cgrid, dim3(256), 0, st, fields_dev, n_fields, src, dst,
-                     src_off, dst_off, skip_mask, cnt, with_panel ? *panel : DrlgxState{}, with_panel ? 1 : 0);
+                     src_off, dst_off, skip_mask, only_cls, cnt, with_panel ? *panel : DrlgxState{}, with_panel ? 1 : 0);
 }
 void drlgx_launch_fetch_pack(const DrlgxState &S, hipStream_t st, const void *src, size_t bytes, void *out) {
   const size_t head = drlgx_fetch_head_bytes(S.n_envs);
