@@ -138,16 +138,11 @@ __device__ __forceinline__ void drlgx_warm_state(DrlgxStateConst Sp) {
 }
 
 // How the belief kernels of the unity build receive the state: DRLGX_KS_PARAM in the signature, `const DrlgxState &S = DRLGX_KS_REF;`
-// as the first line, DRLGX_KS_ARG(S) at the launch.  -DDRLGX_STATE_BY_VALUE builds the by-value form (the A/B of profiles/r06_ab_state_const.txt).
-#ifdef DRLGX_STATE_BY_VALUE
-#define DRLGX_KS_PARAM DrlgxState S_
-#define DRLGX_KS_REF S_
-#define DRLGX_KS_ARG(S) (S)
-#else
+// as the first line, DRLGX_KS_ARG(S) at the launch: a pointer to the struct's device copy (the struct by value was slower,
+// profiles/r06_ab_state_const.txt; k_step alone keeps a by-value twin for that A/B, DRLGX_STATE_PTR=0).
 #define DRLGX_KS_PARAM DrlgxStateConst S_
 #define DRLGX_KS_REF (*(const DrlgxState *)S_)
 #define DRLGX_KS_ARG(S) ((DrlgxStateConst)(S).self_dev)
-#endif
 
 // phase stamp (100 MHz constant clock) — only block 0 / thread 0, only when profiling is armed
 #define DRLGX_PROF(S, slot)                                                        \
@@ -712,7 +707,8 @@ void drlgx_launch_step(const DrlgxState &S, hipStream_t st, LaunchSel sel, const
 // range (action a runs with sel.pcap + a - sel.act_idx); requires drlgx_step_fusable for the bound of the LAST one
 void drlgx_launch_step_loop(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end);
 void drlgx_launch_step_arrow_loop(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end);  // requires drlgx_step_arrow_fusable
-void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel);  // sel.act_idx == -2: reductions only
+// rebuild 0: the reductions only, over the map as it stands (after a reset: the untouched map)
+void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel, int rebuild);
 bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound);
 void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t st, int n, const int32_t *src,
                        const int32_t *dst, int src_off, int dst_off, int skip_mask,  // skip fields with cls & mask

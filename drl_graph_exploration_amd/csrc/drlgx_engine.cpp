@@ -171,24 +171,15 @@ int check_launch(drlgx_engine *e) {
 
 }  // namespace
 
-extern "C" {
+// ---- drlgx_create in parts: each returns an error code, drlgx_create destroys the half-built engine on any of them ----------
+#define TRY(x)             \
+  do {                     \
+    int r_ = (x);          \
+    if (r_) return r_;     \
+  } while (0)
 
-const char *drlgx_strerror(int code) {
-  switch (code) {
-    case DRLGX_OK: return "ok";
-    case DRLGX_E_INVALID: return "invalid argument";
-    case DRLGX_E_NODEVICE: return "no HIP device";
-    case DRLGX_E_CAPACITY: return "instance capacity exceeded (max_poses / max_landmarks / max_factors / max_actions)";
-    case DRLGX_E_HIP: return "HIP runtime error";
-    case DRLGX_E_NUMERIC: return "indeterminate linear system in the SLAM solve";
-    default: return "unknown error";
-  }
-}
-
-const char *drlgx_last_error(const drlgx_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
-
-int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device, drlgx_engine **out) {
-  if (!cfg || !out || n_envs <= 0 || n_rollouts < 0) return DRLGX_E_INVALID;
+static int check_config(const drlgx_config *cfg, int n_envs, int n_rollouts) {
+  if (!cfg || n_envs <= 0 || n_rollouts < 0) return DRLGX_E_INVALID;
   if (cfg->max_poses < 2 || cfg->max_landmarks < 1 || cfg->max_factors < 1 || cfg->num_landmarks < 0 ||
       cfg->max_actions < 1 || cfg->num_samples < 1 || !(cfg->resolution > 0))
     return DRLGX_E_INVALID;
@@ -196,45 +187,31 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
   // must fit the LDS (its landmark system is streamed from the workspace beyond 127 landmarks)
   if (cfg->max_poses > 65535 || cfg->max_landmarks > 65535 || cfg->max_factors > 65534) return DRLGX_E_INVALID;
   if (!drlgx_slam_capacity_ok(cfg->max_poses, cfg->max_landmarks, cfg->max_factors)) return DRLGX_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return DRLGX_E_NODEVICE;
-  drlgx_engine *e = new drlgx_engine();
-  e->device = device;
-  if (hipSetDevice(device) != hipSuccess) {
-    delete e;
-    return DRLGX_E_NODEVICE;
-  }
-  if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    delete e;
-    return DRLGX_E_NODEVICE;
-  }
-  e->stream = e->own_stream;
+  return DRLGX_OK;
+}
+
+// a switch of the environment: its first character decides ('0' turns a default-on switch off, '1' a default-off one on)
+static bool env_flag(const char *name, bool dflt) {
+  const char *v = getenv(name);
+  if (!v) return dflt;
+  return dflt ? v[0] != '0' : v[0] == '1';
+}
+
+static void read_env_switches(drlgx_engine *e) {
+  e->by_capacity = env_flag("DRLGX_VARIANT_BY_CAPACITY", false);
+  e->spin_sync = env_flag("DRLGX_SYNC_SPIN", true);
+  e->la_presim = env_flag("DRLGX_LOOKAHEAD_PRESIM", true);  // 0: every rollout action simulates inside its belief step (the A/B of the parity test)
+  e->la_loop = env_flag("DRLGX_LOOKAHEAD_LOOP", true);  // 0: one launch per action index (the A/B of the look-ahead tests)
+  e->restore_eager = env_flag("DRLGX_RESTORE_EAGER", false);  // 1: a restore copies the virtual-map planes too (the A/B of the lazy restore)
+}
+
+static double p2l(double p) { return std::log(p / (1.0 - p)); }
+static double l2p(double l) { return std::exp(l) / (1.0 + std::exp(l)); }
+
+// capacities, map geometry and the log-odds / noise constants
+static int set_map_constants(drlgx_engine *e) {
   DrlgxState &S = e->S;
-  S.cfg = *cfg;
-  S.n_envs = n_envs;
-  S.n_roll = n_rollouts;
-  if (cfg->max_snapshots < 0 || cfg->max_snapshots > 16) {
-    drlgx_destroy(e);
-    return DRLGX_E_INVALID;
-  }
-  // instances: [0,n) live envs | [n,2n) look-ahead bases | rollouts | max_snapshots x n snapshot copies
-  S.n_inst = 2 * n_envs + n_rollouts + cfg->max_snapshots * n_envs;
-  e->pbound.assign(n_envs, cfg->max_poses);  // unknown until the first reset
-  {
-    const char *v = getenv("DRLGX_VARIANT_BY_CAPACITY");
-    e->by_capacity = v && v[0] == '1';
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-    const char *ss = getenv("DRLGX_SYNC_SPIN");
-    e->spin_sync = !(ss && ss[0] == '0');
-    const char *lp = getenv("DRLGX_LOOKAHEAD_PRESIM");  // 0: every rollout action simulates inside its belief step (the A/B of the parity test)
-    e->la_presim = !(lp && lp[0] == '0');
-    const char *ll = getenv("DRLGX_LOOKAHEAD_LOOP");  // 0: one launch per action index (the A/B of the look-ahead tests)
-    e->la_loop = !(ll && ll[0] == '0');
-    const char *re = getenv("DRLGX_RESTORE_EAGER");  // 1: a restore copies the virtual-map planes too (the A/B of the lazy restore)
-    e->restore_eager = re && re[0] == '1';
-  }
-  e->snap_pbound.assign(cfg->max_snapshots > 0 ? cfg->max_snapshots : 0, std::vector<int>(n_envs, cfg->max_poses));
+  const drlgx_config *cfg = &S.cfg;
   S.P_max = cfg->max_poses;
   S.L_max = cfg->max_landmarks;
   S.M_max = cfg->max_factors;
@@ -253,18 +230,14 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
   if ((int)std::ceil((cfg->map_max_x - cfg->map_min_x) / cfg->resolution) != S.cols ||
       (int)std::ceil((cfg->map_max_y - cfg->map_min_y) / cfg->resolution) != S.rows || S.V <= 0) {
     e->last_error = "map extent must be a multiple of the resolution";
-    drlgx_destroy(e);
     return DRLGX_E_INVALID;
   }
   S.win = (int)std::ceil(2.0 * cfg->max_range / cfg->resolution) + 1;
   if (S.win * S.win > 64) {
     e->last_error = "max_range / resolution too large for the 64-lane cell window";
-    drlgx_destroy(e);
     return DRLGX_E_INVALID;
   }
   // log-odds constants (OccupancyMap.h:10-19) evaluated with the HOST libm: exact ladder values
-  auto p2l = [](double p) { return std::log(p / (1.0 - p)); };
-  auto l2p = [](double l) { return std::exp(l) / (1.0 + std::exp(l)); };
   S.lo_free = p2l(0.3);
   S.lo_occ = p2l(0.7);
   S.lo_min = p2l(0.05);
@@ -275,125 +248,114 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
   S.w_rot = 1.0 / (cfg->rotation_noise * cfg->rotation_noise);
   S.w_bear = 1.0 / (cfg->bearing_noise * cfg->bearing_noise);
   S.w_range = 1.0 / (cfg->range_noise * cfg->range_noise);
+  return DRLGX_OK;
+}
+
+// occupancy ladder closure (see DrlgxState::lo_tr): the packed nibble tables into S, the value and transition tables for the upload
+static void build_ladder(DrlgxState &S, std::vector<double> &lo_pv, std::vector<uint8_t> &lo_tr) {
+  const drlgx_config *cfg = &S.cfg;
   S.lo_tocc = S.lo_tfree = 0ull;
   S.lo_tflag = 0u;
-  // occupancy ladder closure (see DrlgxState::lo_tr)
-  std::vector<double> lo_val{0.0}, lo_pv;
-  std::vector<uint8_t> lo_tr;
-  {
-    auto clampl = [&](double l) { return std::fmin(S.lo_max, std::fmax(S.lo_min, l)); };
-    auto find_or_add = [&](double l) -> int {
-      for (size_t i = 0; i < lo_val.size(); ++i)
-        if (lo_val[i] == l) return (int)i;
-      lo_val.push_back(l);
-      return (int)lo_val.size() - 1;
-    };
-    // Only the transitions the update rules can take are followed (OccupancyMap.cpp:55-138): the landmark pre-updates
-    // apply `occupied` along the chain 0 -> occ(0) -> ...; a pose update leaves a cell at the minimum alone, adds
-    // `occupied` above the threshold and `free` otherwise.  (Following both successors of every state does not close:
-    // lo_occ and lo_free are not exact negatives of each other in floating point, so the values drift by ulps.)
-    bool closed = true;
-    std::vector<int> is_chain{1};  // states reachable by landmark pre-updates alone
-    for (size_t i = 0; i < lo_val.size(); ++i) {
-      if (lo_val.size() > DRLGX_LO_TAB) {
-        closed = false;
-        break;
-      }
-      const double l = lo_val[i];
-      const bool frozen = std::fabs(l - S.lo_min) < 1e-5, above = l > S.occ_thresh + 1e-8;
-      int o = (int)i, f = (int)i;
-      if (above || is_chain[i]) {
-        o = find_or_add(clampl(l + S.lo_occ));
-        if ((size_t)o >= is_chain.size()) is_chain.push_back(0);
-        if (is_chain[i]) is_chain[o] = 1;
-      }
-      if (!above && !frozen) {
-        f = find_or_add(clampl(l + S.lo_free));
-        if ((size_t)f >= is_chain.size()) is_chain.push_back(0);
-      }
-      const uint8_t flags = (uint8_t)((frozen ? 1 : 0) | (above ? 2 : 0));
-      lo_tr.push_back((uint8_t)o); lo_tr.push_back((uint8_t)f); lo_tr.push_back(flags); lo_tr.push_back(0);
+  std::vector<double> lo_val{0.0};
+  auto clampl = [&](double l) { return std::fmin(S.lo_max, std::fmax(S.lo_min, l)); };
+  auto find_or_add = [&](double l) -> int {
+    for (size_t i = 0; i < lo_val.size(); ++i)
+      if (lo_val[i] == l) return (int)i;
+    lo_val.push_back(l);
+    return (int)lo_val.size() - 1;
+  };
+  // Only the transitions the update rules can take are followed (OccupancyMap.cpp:55-138): the landmark pre-updates
+  // apply `occupied` along the chain 0 -> occ(0) -> ...; a pose update leaves a cell at the minimum alone, adds
+  // `occupied` above the threshold and `free` otherwise.  (Following both successors of every state does not close:
+  // lo_occ and lo_free are not exact negatives of each other in floating point, so the values drift by ulps.)
+  bool closed = true;
+  std::vector<int> is_chain{1};  // states reachable by landmark pre-updates alone
+  for (size_t i = 0; i < lo_val.size(); ++i) {
+    if (lo_val.size() > DRLGX_LO_TAB) {
+      closed = false;
+      break;
     }
-    if (closed && lo_val.size() <= DRLGX_LO_TAB) {
-      for (double l : lo_val) {  // OccupancyMap LOGODDS2PROB + VirtualMap::updateProbability (num_samples identical maps)
-        const double pv1 = l2p(l);
-        double acc = 0.0;
-        for (int s2 = 0; s2 < cfg->num_samples; ++s2) acc += pv1 / cfg->num_samples;
-        lo_pv.push_back(acc);
-      }
-      S.lo_ntab = (int)lo_val.size();
-      if (S.lo_ntab <= 16)
-        for (int i = 0; i < S.lo_ntab; ++i) {
-          S.lo_tocc |= (unsigned long long)(lo_tr[4 * i] & 15) << (4 * i);
-          S.lo_tfree |= (unsigned long long)(lo_tr[4 * i + 1] & 15) << (4 * i);
-          S.lo_tflag |= (unsigned int)(lo_tr[4 * i + 2] & 3) << (2 * i);
-        }
-    } else {
-      S.lo_ntab = 0;
-      lo_pv.assign(1, 0.5);
-      lo_tr.assign(4, 0);
+    const double l = lo_val[i];
+    const bool frozen = std::fabs(l - S.lo_min) < 1e-5, above = l > S.occ_thresh + 1e-8;
+    int o = (int)i, f = (int)i;
+    if (above || is_chain[i]) {
+      o = find_or_add(clampl(l + S.lo_occ));
+      if ((size_t)o >= is_chain.size()) is_chain.push_back(0);
+      if (is_chain[i]) is_chain[o] = 1;
     }
+    if (!above && !frozen) {
+      f = find_or_add(clampl(l + S.lo_free));
+      if ((size_t)f >= is_chain.size()) is_chain.push_back(0);
+    }
+    const uint8_t flags = (uint8_t)((frozen ? 1 : 0) | (above ? 2 : 0));
+    lo_tr.push_back((uint8_t)o); lo_tr.push_back((uint8_t)f); lo_tr.push_back(flags); lo_tr.push_back(0);
   }
-  // sector-sweep table (OccupancyMap.cpp:86): b accumulates in double exactly as the reference loop
+  if (closed && lo_val.size() <= DRLGX_LO_TAB) {
+    for (double l : lo_val) {  // OccupancyMap LOGODDS2PROB + VirtualMap::updateProbability (num_samples identical maps)
+      const double pv1 = l2p(l);
+      double acc = 0.0;
+      for (int s2 = 0; s2 < cfg->num_samples; ++s2) acc += pv1 / cfg->num_samples;
+      lo_pv.push_back(acc);
+    }
+    S.lo_ntab = (int)lo_val.size();
+    if (S.lo_ntab <= 16)
+      for (int i = 0; i < S.lo_ntab; ++i) {
+        S.lo_tocc |= (unsigned long long)(lo_tr[4 * i] & 15) << (4 * i);
+        S.lo_tfree |= (unsigned long long)(lo_tr[4 * i + 1] & 15) << (4 * i);
+        S.lo_tflag |= (unsigned int)(lo_tr[4 * i + 2] & 3) << (2 * i);
+      }
+  } else {
+    S.lo_ntab = 0;
+    lo_pv.assign(1, 0.5);
+    lo_tr.assign(4, 0);
+  }
+}
+
+// sector-sweep table (OccupancyMap.cpp:86) and what follows from the sensor's sector and range: bbox_noop, fov_*, r2_*
+static std::vector<double> set_sensor_constants(DrlgxState &S) {
+  const drlgx_config *cfg = &S.cfg;
+  // b accumulates in double exactly as the reference loop
   std::vector<double> sweep;
   for (double b = cfg->min_bearing; b < cfg->max_bearing + 1e-5; b += 3 * 0.01745329251994329575) sweep.push_back(b);
   S.n_sweep = (int)sweep.size();
-  {
-    // The bbox only prunes work if an in-range cell can fall outside it.  A cell centre within max_range of the
-    // pose lies at most (max_range - res/2) past the pose's own cell boundary, so the box contains it as soon as
-    // some sweep sample is within acos(1 - res / (2 max_range)) of each axis direction (k_map).
-    const double two_pi = 6.283185307179586476925286766559;
-    double max_gap = 3 * 0.01745329251994329575;
-    if (!sweep.empty()) max_gap = std::max(max_gap, two_pi - (sweep.back() - sweep.front()));
-    const double need = std::acos(std::max(-1.0, 1.0 - cfg->resolution / (2.0 * cfg->max_range)));
-    S.bbox_noop = (0.5 * max_gap + 1e-6 <= need) ? 1 : 0;
-    // field of view: blind half-angle around the backwards ray
-    const double pi = 3.14159265358979323846;
-    const double blind = std::max(pi - cfg->max_bearing, pi + cfg->min_bearing);
-    S.fov_fast = (cfg->max_bearing > 1.7 && cfg->min_bearing < -1.7 && blind >= 0 && blind + 1e-3 < 1.4) ? 1 : 0;
-    S.fov_tan = S.fov_fast ? std::tan(blind + 1e-3) : 0.0;
-    // smallest x with sqrt(x) >= max_range, largest x with sqrt(x) <= min_range (sqrt is correctly rounded
-    // and monotone on both host and device, so the squared comparisons are EXACTLY the reference's tests)
-    double t = cfg->max_range * cfg->max_range;
-    while (std::sqrt(std::nextafter(t, 0.0)) >= cfg->max_range) t = std::nextafter(t, 0.0);
-    while (std::sqrt(t) < cfg->max_range) t = std::nextafter(t, INFINITY);
-    S.r2_max_lt = t;
-    t = cfg->min_range * cfg->min_range;
-    while (std::sqrt(std::nextafter(t, INFINITY)) <= cfg->min_range) t = std::nextafter(t, INFINITY);
-    while (t > 0 && std::sqrt(t) > cfg->min_range) t = std::nextafter(t, 0.0);
-    S.r2_min_gt = t;
-  }
-  // libstdc++ iteration order of unordered_map<unsigned, ...> filled with keys 0..n-1 (Simulator2D.cpp:331-344)
-  {
-    std::unordered_map<unsigned, int> m;
-    for (int i = 0; i < cfg->num_landmarks; ++i) m.emplace((unsigned)i, i);
-    for (const auto &kv : m) e->lm_order.push_back((int)kv.first);
-    if (e->lm_order.empty()) e->lm_order.push_back(0);
-  }
-  int r = DRLGX_OK;
-  double *sweep_dev = nullptr;
-  int *order_dev = nullptr;
-#define TRY(x)            \
-  if ((r = (x)) != 0) {   \
-    drlgx_destroy(e);     \
-    return r;             \
-  }
-  TRY(dev_alloc(e, &sweep_dev, sweep.size()));
-  TRY(dev_alloc(e, &order_dev, e->lm_order.size()));
-  hipMemcpyAsync(sweep_dev, sweep.data(), sweep.size() * sizeof(double), hipMemcpyHostToDevice, e->stream);
-  hipMemcpyAsync(order_dev, e->lm_order.data(), e->lm_order.size() * sizeof(int), hipMemcpyHostToDevice, e->stream);
-  S.sweep_b = sweep_dev;
-  S.lm_order = order_dev;
-  {
-    double *pv_dev = nullptr;
-    uint8_t *tr_dev = nullptr;
-    TRY(dev_alloc(e, &pv_dev, lo_pv.size()));
-    TRY(dev_alloc(e, &tr_dev, lo_tr.size()));
-    HIPCHK(e, hipMemcpyAsync(pv_dev, lo_pv.data(), lo_pv.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(tr_dev, lo_tr.data(), lo_tr.size(), hipMemcpyHostToDevice, e->stream));
-    S.lo_pv = pv_dev;
-    S.lo_tr = tr_dev;
-  }
+  // The bbox only prunes work if an in-range cell can fall outside it.  A cell centre within max_range of the
+  // pose lies at most (max_range - res/2) past the pose's own cell boundary, so the box contains it as soon as
+  // some sweep sample is within acos(1 - res / (2 max_range)) of each axis direction (k_map).
+  const double two_pi = 6.283185307179586476925286766559;
+  double max_gap = 3 * 0.01745329251994329575;
+  if (!sweep.empty()) max_gap = std::max(max_gap, two_pi - (sweep.back() - sweep.front()));
+  const double need = std::acos(std::max(-1.0, 1.0 - cfg->resolution / (2.0 * cfg->max_range)));
+  S.bbox_noop = (0.5 * max_gap + 1e-6 <= need) ? 1 : 0;
+  // field of view: blind half-angle around the backwards ray
+  const double pi = 3.14159265358979323846;
+  const double blind = std::max(pi - cfg->max_bearing, pi + cfg->min_bearing);
+  S.fov_fast = (cfg->max_bearing > 1.7 && cfg->min_bearing < -1.7 && blind >= 0 && blind + 1e-3 < 1.4) ? 1 : 0;
+  S.fov_tan = S.fov_fast ? std::tan(blind + 1e-3) : 0.0;
+  // smallest x with sqrt(x) >= max_range, largest x with sqrt(x) <= min_range (sqrt is correctly rounded
+  // and monotone on both host and device, so the squared comparisons are EXACTLY the reference's tests)
+  double t = cfg->max_range * cfg->max_range;
+  while (std::sqrt(std::nextafter(t, 0.0)) >= cfg->max_range) t = std::nextafter(t, 0.0);
+  while (std::sqrt(t) < cfg->max_range) t = std::nextafter(t, INFINITY);
+  S.r2_max_lt = t;
+  t = cfg->min_range * cfg->min_range;
+  while (std::sqrt(std::nextafter(t, INFINITY)) <= cfg->min_range) t = std::nextafter(t, INFINITY);
+  while (t > 0 && std::sqrt(t) > cfg->min_range) t = std::nextafter(t, 0.0);
+  S.r2_min_gt = t;
+  return sweep;
+}
+
+template <typename T>
+static int upload_table(drlgx_engine *e, const T **out, const std::vector<T> &host) {
+  T *dev = nullptr;
+  TRY(dev_alloc(e, &dev, host.size()));
+  HIPCHK(e, hipMemcpyAsync(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
+  *out = dev;
+  return DRLGX_OK;
+}
+
+// the per-instance fields, in the order the copy table is built from (drlgx_create sorts it stably afterwards)
+static int alloc_fields(drlgx_engine *e) {
+  DrlgxState &S = e->S;
   const size_t P = S.P_max, L = S.L_max, M = S.M_max, V = S.V;
   TRY(field_alloc(e, &S.gt_pose, 4));
   TRY(field_alloc(e, &S.parent, 1));
@@ -421,7 +383,6 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
   TRY(field_alloc(e, &S.red, DRLGX_RED_STRIDE));
   TRY(field_alloc(e, &S.vm_prob, V, 1));
   TRY(field_alloc(e, &S.vm_info, 3 * V, 1));
-#ifndef COPY_EXP_NOSPLIT
   {
     // the three planes of the information as three entries of the copy table (same stride, a third of the bytes each): the 38 KB slice
     // was the copy kernel's longest workgroup by far
@@ -434,77 +395,153 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
       e->fields.push_back(g);
     }
   }
-#endif
   TRY(field_alloc(e, &S.vm_upd, (size_t)S.Vu, 1));
   TRY(field_alloc(e, &S.vm_tr, V, 1));
   TRY(field_alloc(e, &S.gt_lm, (size_t)S.LG * 2, 2));  // rollouts read their parent's landmarks
-  // SLAM workspace (not copied between instances)
-  {
-    // k_slam workspace (k_slam.hip: drlgx_slam_ws_doubles)
-    S.slam_ws_stride = drlgx_slam_ws_doubles(S.P_max, S.L_max, S.M_max);
-    S.slam_iws_stride = 2;
-    TRY(dev_alloc(e, &S.slam_ws, S.slam_ws_stride * (size_t)S.n_inst));
-    TRY(dev_alloc(e, &S.slam_iws, S.slam_iws_stride * (size_t)S.n_inst));
+  return DRLGX_OK;
+}
+
+// Covariance panel of the incremental belief update (k_inc.hip): on unless DRLGX_INCREMENTAL=0 or the panels of all
+// instances would not fit the budget (DRLGX_INC_MAX_GB; default: 60 % of the memory that is free on the device now) or the
+// allocation fails - then every update is a full solve (the engine works either way; said once on stderr).
+static int alloc_panels(drlgx_engine *e) {
+  DrlgxState &S = e->S;
+  const char *g = getenv("DRLGX_INC_MAX_GB");
+  size_t free_b = 0, total_b = 0;
+  double max_gb = 32.0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) max_gb = 0.6 * (double)free_b / 1073741824.0;
+  if (g) max_gb = atof(g);
+  S.jc_ld = (3 + 2 * S.L_max + 31) & ~31;  // whole pairs of 16-column tiles, rows on 256-byte boundaries (k_inc.hip, B3)
+  S.jc_stride = (size_t)(3 * S.P_max + 2 * S.L_max + 16) * (size_t)S.jc_ld;  // (+ 16: the row tiles are written whole)
+  const double gb = (double)S.jc_stride * 8.0 * (double)S.n_inst / 1073741824.0;
+  if (!env_flag("DRLGX_INCREMENTAL", true)) return DRLGX_OK;
+  const size_t n_before = e->allocs.size();
+  bool ok = gb <= max_gb;
+  if (ok) {
+    ok = dev_alloc(e, &S.jc, S.jc_stride * (size_t)S.n_inst) == DRLGX_OK && dev_alloc(e, &S.jd, (size_t)S.P_max * 6 * (size_t)S.n_inst) == DRLGX_OK &&
+         dev_alloc(e, &S.jc_meta, (size_t)4 * (size_t)S.n_inst) == DRLGX_OK && dev_alloc(e, &S.inc_stats, 2) == DRLGX_OK;
   }
-  // Covariance panel of the incremental belief update (k_inc.hip): on unless DRLGX_INCREMENTAL=0 or the panels of all
-  // instances would not fit the budget (DRLGX_INC_MAX_GB; default: 60 % of the memory that is free on the device now) or the
-  // allocation fails - then every update is a full solve (the engine works either way; said once on stderr).
-  {
-    const char *v = getenv("DRLGX_INCREMENTAL");
-    const char *g = getenv("DRLGX_INC_MAX_GB");
-    size_t free_b = 0, total_b = 0;
-    double max_gb = 32.0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) max_gb = 0.6 * (double)free_b / 1073741824.0;
-    if (g) max_gb = atof(g);
-    S.jc_ld = (3 + 2 * S.L_max + 31) & ~31;  // whole pairs of 16-column tiles, rows on 256-byte boundaries (k_inc.hip, B3)
-    S.jc_stride = (size_t)(3 * S.P_max + 2 * S.L_max + 16) * (size_t)S.jc_ld;  // (+ 16: the row tiles are written whole)
-    const double gb = (double)S.jc_stride * 8.0 * (double)S.n_inst / 1073741824.0;
-    if (!(v && v[0] == '0')) {
-      const size_t n_before = e->allocs.size();
-      bool ok = gb <= max_gb;
-      if (ok) {
-        ok = dev_alloc(e, &S.jc, S.jc_stride * (size_t)S.n_inst) == DRLGX_OK && dev_alloc(e, &S.jd, (size_t)S.P_max * 6 * (size_t)S.n_inst) == DRLGX_OK &&
-             dev_alloc(e, &S.jc_meta, (size_t)4 * (size_t)S.n_inst) == DRLGX_OK && dev_alloc(e, &S.inc_stats, 2) == DRLGX_OK;
-      }
-      if (!ok) {
-        (void)hipGetLastError();  // a failed hipMalloc is not this engine's error
-        while (e->allocs.size() > n_before) {
-          hipFree(e->allocs.back());
-          e->allocs.pop_back();
-        }
-        S.jc = nullptr;
-        S.jd = nullptr;
-        S.jc_meta = nullptr;
-        S.inc_stats = nullptr;
-        e->last_error.clear();
-        fprintf(stderr, "drlgx: covariance panels (%.1f GB) not allocated (budget %.1f GB): every belief update is a full solve\n", gb, max_gb);
-      }
+  if (!ok) {
+    (void)hipGetLastError();  // a failed hipMalloc is not this engine's error
+    while (e->allocs.size() > n_before) {
+      hipFree(e->allocs.back());
+      e->allocs.pop_back();
     }
+    S.jc = nullptr;
+    S.jd = nullptr;
+    S.jc_meta = nullptr;
+    S.inc_stats = nullptr;
+    e->last_error.clear();
+    fprintf(stderr, "drlgx: covariance panels (%.1f GB) not allocated (budget %.1f GB): every belief update is a full solve\n", gb, max_gb);
   }
+  return DRLGX_OK;
+}
+
+// status word, the copy table, staging buffers and the state struct's device copy
+static int alloc_staging(drlgx_engine *e) {
+  DrlgxState &S = e->S;
+  const int n_envs = S.n_envs;
   TRY(dev_alloc(e, &S.status, 1));
   // (the copy kernel deals a workgroup to every (instance, field): the largest slices first, so that none of them starts last)
   std::stable_sort(e->fields.begin(), e->fields.end(), [](const DrlgxField &a, const DrlgxField &b) {
     return (a.pad > 0 ? (size_t)a.pad : a.stride) > (b.pad > 0 ? (size_t)b.pad : b.stride);
   });
   TRY(dev_alloc(e, &e->fields_dev, e->fields.size()));
-  hipMemcpyAsync(e->fields_dev, e->fields.data(), e->fields.size() * sizeof(DrlgxField), hipMemcpyHostToDevice, e->stream);
+  HIPCHK(e, hipMemcpyAsync(e->fields_dev, e->fields.data(), e->fields.size() * sizeof(DrlgxField), hipMemcpyHostToDevice, e->stream));
   TRY(dev_alloc(e, &e->stage_i32, (size_t)n_envs));
   TRY(dev_alloc(e, &e->stage_u32, (size_t)n_envs));
   TRY(dev_alloc(e, &e->stage_f64, (size_t)n_envs * 3));
   TRY(dev_alloc(e, &e->stage_mask, (size_t)n_envs));
   e->graph_gi_stride = 4 * S.L_max + 8;
   TRY(dev_alloc(e, &e->graph_gi, (size_t)n_envs * e->graph_gi_stride));
+  // the struct's device copy: what the belief kernels read their state from (DrlgxStateConst; drlgx_dev.h)
+  unsigned char *raw = nullptr;
+  TRY(dev_alloc(e, &raw, sizeof(DrlgxState)));
+  e->state_dev = reinterpret_cast<DrlgxState *>(raw);
+  S.self_dev = e->state_dev;
+  return DRLGX_OK;
+}
+
+static int build_engine(drlgx_engine *e) {
+  DrlgxState &S = e->S;
+  const drlgx_config *cfg = &S.cfg;
+  if (cfg->max_snapshots < 0 || cfg->max_snapshots > 16) return DRLGX_E_INVALID;
+  // instances: [0,n) live envs | [n,2n) look-ahead bases | rollouts | max_snapshots x n snapshot copies
+  S.n_inst = 2 * S.n_envs + S.n_roll + cfg->max_snapshots * S.n_envs;
+  e->pbound.assign(S.n_envs, cfg->max_poses);  // unknown until the first reset
+  e->snap_pbound.assign(cfg->max_snapshots > 0 ? cfg->max_snapshots : 0, std::vector<int>(S.n_envs, cfg->max_poses));
+  read_env_switches(e);
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
+  TRY(set_map_constants(e));
+  std::vector<double> lo_pv;
+  std::vector<uint8_t> lo_tr;
+  build_ladder(S, lo_pv, lo_tr);
+  const std::vector<double> sweep = set_sensor_constants(S);
+  // libstdc++ iteration order of unordered_map<unsigned, ...> filled with keys 0..n-1 (Simulator2D.cpp:331-344)
   {
-    // the struct's device copy: what the belief kernels read their state from (DrlgxStateConst; drlgx_dev.h)
-    unsigned char *raw = nullptr;
-    TRY(dev_alloc(e, &raw, sizeof(DrlgxState)));
-    e->state_dev = reinterpret_cast<DrlgxState *>(raw);
-    S.self_dev = e->state_dev;
+    std::unordered_map<unsigned, int> m;
+    for (int i = 0; i < cfg->num_landmarks; ++i) m.emplace((unsigned)i, i);
+    for (const auto &kv : m) e->lm_order.push_back((int)kv.first);
+    if (e->lm_order.empty()) e->lm_order.push_back(0);
   }
+  TRY(upload_table(e, &S.sweep_b, sweep));
+  TRY(upload_table(e, &S.lm_order, e->lm_order));
+  TRY(upload_table(e, &S.lo_pv, lo_pv));
+  TRY(upload_table(e, &S.lo_tr, lo_tr));
+  TRY(alloc_fields(e));
+  // SLAM workspace (not copied between instances; k_slam.hip: drlgx_slam_ws_doubles)
+  S.slam_ws_stride = drlgx_slam_ws_doubles(S.P_max, S.L_max, S.M_max);
+  S.slam_iws_stride = 2;
+  TRY(dev_alloc(e, &S.slam_ws, S.slam_ws_stride * (size_t)S.n_inst));
+  TRY(dev_alloc(e, &S.slam_iws, S.slam_iws_stride * (size_t)S.n_inst));
+  TRY(alloc_panels(e));
+  TRY(alloc_staging(e));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return DRLGX_OK;
+}
 #undef TRY
-  if (hipStreamSynchronize(e->stream) != hipSuccess) {
+
+extern "C" {
+
+const char *drlgx_strerror(int code) {
+  switch (code) {
+    case DRLGX_OK: return "ok";
+    case DRLGX_E_INVALID: return "invalid argument";
+    case DRLGX_E_NODEVICE: return "no HIP device";
+    case DRLGX_E_CAPACITY: return "instance capacity exceeded (max_poses / max_landmarks / max_factors / max_actions)";
+    case DRLGX_E_HIP: return "HIP runtime error";
+    case DRLGX_E_NUMERIC: return "indeterminate linear system in the SLAM solve";
+    default: return "unknown error";
+  }
+}
+
+const char *drlgx_last_error(const drlgx_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
+
+int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device, drlgx_engine **out) {
+  if (!out) return DRLGX_E_INVALID;
+  int r = check_config(cfg, n_envs, n_rollouts);
+  if (r) return r;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return DRLGX_E_NODEVICE;
+  drlgx_engine *e = new drlgx_engine();
+  e->device = device;
+  if (hipSetDevice(device) != hipSuccess) {
+    delete e;
+    return DRLGX_E_NODEVICE;
+  }
+  if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    delete e;
+    return DRLGX_E_NODEVICE;
+  }
+  e->stream = e->own_stream;
+  DrlgxState &S = e->S;
+  S.cfg = *cfg;
+  S.n_envs = n_envs;
+  S.n_roll = n_rollouts;
+  if ((r = build_engine(e)) != DRLGX_OK) {
     drlgx_destroy(e);
-    return DRLGX_E_HIP;
+    return r;
   }
   state_sync(e);
   *out = e;
@@ -534,7 +571,6 @@ static void settle(drlgx_engine *e) {
 int drlgx_destroy(drlgx_engine *e) {
   DRLGX_ENTER_OWING(e);
   if (!e) return DRLGX_E_INVALID;
-  hipSetDevice(e->device);
   hipDeviceSynchronize();
   for (void *p : e->allocs) hipFree(p);
   for (auto &sp : e->spans) {
@@ -572,6 +608,11 @@ static int max_bound(const drlgx_engine *e) {
   int m = 1;
   for (int v : e->pbound) m = std::max(m, v);
   return m;
+}
+
+// every env may have gained k poses
+static void advance_pbound(drlgx_engine *e, int k) {
+  for (int &v : e->pbound) v = std::min(v + k, e->S.P_max);
 }
 
 // the stream drained, observed by polling (see drlgx_engine::spin_sync)
@@ -639,7 +680,6 @@ int drlgx_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const uint3
     if (env_ids[i] < 0 || env_ids[i] >= e->S.n_envs || mask[env_ids[i]]) return DRLGX_E_INVALID;
     mask[env_ids[i]] = 1;
   }
-  hipSetDevice(e->device);
   HIPCHK(e, hipMemcpyAsync(e->stage_i32, env_ids, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipMemcpyAsync(e->stage_u32, seeds, n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipMemcpyAsync(e->stage_f64, start, n * 3 * sizeof(double), hipMemcpyHostToDevice, e->stream));
@@ -649,54 +689,60 @@ int drlgx_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const uint3
   for (int i = 0; i < n; ++i) e->pbound[env_ids[i]] = 1;
   LaunchSel sel{0, e->S.n_envs, e->stage_mask, nullptr, 0};
   drlgx_launch_slam(e->S, e->stream, sel, e->by_capacity ? e->S.P_max : 1);
-  sel.act_idx = -2;  // reductions only: the virtual map is in its untouched state
   sel.pcap = max_bound(e);
-  drlgx_launch_map(e->S, e->stream, sel);
+  drlgx_launch_map(e->S, e->stream, sel, 0);  // reductions only: the virtual map is in its untouched state
   int r = check_launch(e);
   if (r) return r;
   HIPCHK(e, hipStreamSynchronize(e->stream));  // staging buffers are reused
   return DRLGX_OK;
 }
 
+// One belief step of a selection, in the form its pose bound pb allows: the fused kernel around the dense solver, the same
+// fusion around the pose-chain solver (longer trajectories), or the three stage kernels - also in timing mode 2, where each
+// stage gets its own span (timers 0-2; the fused forms: timer 5).  n_measure: the simulator's stream selector.
+static void launch_belief_step(drlgx_engine *e, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int pb, bool may_split) {
+  const DrlgxState &S = e->S;
+  sel.pcap = pb;  // (the kernels size their per-pose LDS tables with the launch's bound, not with the capacity)
+  if (drlgx_step_fusable(S, pb) && !e->per_stage) {
+    ScopedTimer t(e, 5);
+    // more instances than CUs: simulator + SLAM fused, the map as its own launch in the two-workgroups-per-CU form (k_map_c) - at one
+    // workgroup per CU the fused map stage cannot overlap anything, two map workgroups per CU cover each other's barriers
+    const bool split = may_split && sel.n > e->n_cu && drlgx_map_two_per_cu(S, pb);
+    sel.skip_map = split ? 1 : 0;
+    drlgx_launch_step(S, e->stream, sel, odom, odom_stride, n_measure);
+    if (split) {
+      sel.skip_map = 0;
+      drlgx_launch_map(S, e->stream, sel, 1);
+    }
+  } else if (drlgx_step_arrow_fusable(S) && !e->per_stage) {
+    ScopedTimer t(e, 5);
+    drlgx_launch_step_arrow(S, e->stream, sel, odom, odom_stride, n_measure);
+  } else {
+    {
+      ScopedTimer t(e, 0);
+      drlgx_launch_sim(S, e->stream, sel, odom, odom_stride, n_measure);
+    }
+    {
+      ScopedTimer t(e, 1);
+      drlgx_launch_slam(S, e->stream, sel, pb);
+    }
+    {
+      ScopedTimer t(e, 2);
+      drlgx_launch_map(S, e->stream, sel, 1);
+    }
+  }
+}
+
 int drlgx_step(drlgx_engine *e, const double *odom_dev, const uint8_t *active_dev) {
   DRLGX_ENTER_OWING(e);
   if (!e || !odom_dev) return DRLGX_E_INVALID;
   LaunchSel sel{0, e->S.n_envs, active_dev, nullptr, 0};
-  // every form below runs the map stage (kmap::map_body) for every env: it takes over what a lazy restore owes
+  // every form of the step runs the map stage (kmap::map_body) for every env: it takes over what a lazy restore owes
   if (e->owed_slot >= 0) sel.vm_from = snapshot_base(e, e->owed_slot);
   e->owed_slot = -1;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
-  sel.pcap = pb;  // (the kernels size their per-pose LDS tables with the launch's bound, not with the capacity)
-  for (int &v : e->pbound) v = std::min(v + 1, e->S.P_max);
-  if (drlgx_step_fusable(e->S, pb) && !e->per_stage) {
-    // one fused kernel per step (timer 5); timing mode 2 launches the stage kernels separately (timers 0-2)
-    ScopedTimer t(e, 5);
-    // more envs than CUs: simulator + SLAM fused, the map as its own launch in the two-workgroups-per-CU form (k_map_c) - at one
-    // workgroup per CU the fused map stage cannot overlap anything, two map workgroups per CU cover each other's barriers
-    const bool split = e->S.n_envs > e->n_cu && drlgx_map_two_per_cu(e->S, pb);
-    sel.skip_map = split ? 1 : 0;
-    drlgx_launch_step(e->S, e->stream, sel, odom_dev, 3, 2);
-    if (split) {
-      sel.skip_map = 0;
-      drlgx_launch_map(e->S, e->stream, sel);
-    }
-  } else if (drlgx_step_arrow_fusable(e->S) && !e->per_stage) {
-    ScopedTimer t(e, 5);  // longer trajectories: the same fusion around the pose-chain solver
-    drlgx_launch_step_arrow(e->S, e->stream, sel, odom_dev, 3, 2);
-  } else {
-    {
-      ScopedTimer t(e, 0);
-      drlgx_launch_sim(e->S, e->stream, sel, odom_dev, 3, 2);
-    }
-    {
-      ScopedTimer t(e, 1);
-      drlgx_launch_slam(e->S, e->stream, sel, pb);
-    }
-    {
-      ScopedTimer t(e, 2);
-      drlgx_launch_map(e->S, e->stream, sel);
-    }
-  }
+  advance_pbound(e, 1);
+  launch_belief_step(e, sel, odom_dev, 3, 2, pb, true);
   {
     ScopedTimer t(e, 7);  // empty span: the event-pair overhead, so that callers can subtract it
   }
@@ -713,30 +759,58 @@ int drlgx_step_plan(drlgx_engine *e, const double *actions_dev, const int32_t *n
   LaunchSel sel{0, e->S.n_envs, nullptr, n_actions_dev, action_index};
   sel.map_last_only = map_last_only ? 1 : 0;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
-  sel.pcap = pb;
-  for (int &v : e->pbound) v = std::min(v + 1, e->S.P_max);
-  const int stride = e->S.A_max * 3;
-  if (drlgx_step_fusable(e->S, pb) && !e->per_stage) {
-    ScopedTimer t(e, 5);
-    drlgx_launch_step(e->S, e->stream, sel, actions_dev, stride, 2);
-  } else if (drlgx_step_arrow_fusable(e->S) && !e->per_stage) {
-    ScopedTimer t(e, 5);
-    drlgx_launch_step_arrow(e->S, e->stream, sel, actions_dev, stride, 2);
-  } else {
-    {
-      ScopedTimer t(e, 0);
-      drlgx_launch_sim(e->S, e->stream, sel, actions_dev, stride, 2);
-    }
-    {
-      ScopedTimer t(e, 1);
-      drlgx_launch_slam(e->S, e->stream, sel, pb);
-    }
-    {
-      ScopedTimer t(e, 2);
-      drlgx_launch_map(e->S, e->stream, sel);
-    }
-  }
+  advance_pbound(e, 1);
+  launch_belief_step(e, sel, actions_dev, e->S.A_max * 3, 2, pb, false);
   return check_launch(e);
+}
+
+// The look-ahead's simulator log: the simulator of every selected rollout over its whole action list first (k_presim, one wave per
+// rollout; timer 0), replayed action by action by the steps that sel then launches.  No room for the log: the rollouts simulate
+// inside their steps, from now on.
+static void presimulate(drlgx_engine *e, LaunchSel &sel, const double *act, int n_measure, int max_n_actions) {
+  const DrlgxState &S = e->S;
+  const size_t entry = drlgx_simlog_entry_bytes(S), roll = entry * (size_t)S.A_max;
+  if (!e->simlog_dev && dev_alloc(e, &e->simlog_dev, roll * (size_t)S.n_roll) != DRLGX_OK) {
+    (void)hipGetLastError();
+    e->last_error.clear();
+    e->la_presim = false;
+    return;
+  }
+  ScopedTimer t(e, 0);
+  drlgx_launch_presim(S, e->stream, sel, act, S.A_max * 3, n_measure, max_n_actions, e->simlog_dev, roll, (int)entry);
+  sel.simlog = e->simlog_dev;
+  sel.simlog_roll = roll;
+  sel.simlog_act = (int)entry;
+}
+
+// The actions [0, max_n_actions) of a selection's action lists (act: [sel.n][A_max][3]) as whole ranges per launch (k_step_loop /
+// k_step_arrow_loop: a workgroup runs its instance's list); pbe: the pose bound before the first action.  Returns the first action
+// index that is still to be launched one by one (launch_belief_step) - 0 when nothing was launched here.
+// A launch per action index picks its kernel from the pose bound of THAT action (the fused dense-solver step while it serves the
+// bound, then the step around the pose-chain solver); the loop form keeps that choice action by action - the leading actions
+// [0, a_sw) in the dense loop kernel, the rest in the pose-chain one - because the two solvers round differently and the reference's
+// integer worlds hold cells at exactly max_range from a pose: one ulp of a pose decides them, and with them O(0.1) of a reward.
+// partial: when the pose-chain loop cannot take the rest, still run the dense loop for [0, a_sw) (else: nothing).
+// presim: pre-simulate the lists (only when EVERY action is replayed: k_presim leaves the ground truth and the streams of the LAST action).
+static int launch_action_range(drlgx_engine *e, LaunchSel sel, const double *act, int n_measure, int pbe, int max_n_actions, bool partial,
+                               bool presim) {
+  const DrlgxState &S = e->S;
+  int a_sw = 0;
+  while (a_sw < max_n_actions && drlgx_step_fusable(S, std::min(pbe + a_sw + 1, S.P_max))) ++a_sw;
+  const bool rest_loops = a_sw == max_n_actions || drlgx_step_arrow_fusable(S);
+  if (!e->la_loop || e->per_stage || !(rest_loops || (partial && a_sw > 0))) return 0;
+  if (presim && e->la_presim && rest_loops) presimulate(e, sel, act, n_measure, max_n_actions);
+  ScopedTimer t(e, 5);
+  if (a_sw > 0) {
+    sel.act_idx = 0;
+    sel.pcap = std::min(pbe + 1, S.P_max);
+    drlgx_launch_step_loop(S, e->stream, sel, act, S.A_max * 3, n_measure, a_sw);
+  }
+  if (a_sw == max_n_actions || !rest_loops) return a_sw;
+  sel.act_idx = a_sw;
+  sel.pcap = std::min(pbe + a_sw + 1, S.P_max);
+  drlgx_launch_step_arrow_loop(S, e->stream, sel, act, S.A_max * 3, n_measure, max_n_actions);
+  return max_n_actions;
 }
 
 // The whole loop `for a in actions: self._sim.simulate(a)` of every env (scripts/envs/exploration_env.py:98-105) in one call: env i
@@ -747,32 +821,13 @@ int drlgx_step_plans(drlgx_engine *e, const double *actions_dev, const int32_t *
   DRLGX_ENTER(e);
   if (!e || !actions_dev || !n_actions_dev || max_n_actions < 0 || max_n_actions > e->S.A_max) return DRLGX_E_INVALID;
   if (max_n_actions == 0) return DRLGX_OK;
-  const DrlgxState &S = e->S;
-  const int pbe = max_bound(e);
-  int a_sw = 0;  // the leading actions the fused dense-solver step serves (as one drlgx_step_plan per action index would choose)
-  while (a_sw < max_n_actions && drlgx_step_fusable(S, std::min(pbe + a_sw + 1, S.P_max))) ++a_sw;
-  const bool rest_loops = a_sw == max_n_actions || drlgx_step_arrow_fusable(S);
-  if (!e->la_loop || e->per_stage || !rest_loops) {
-    for (int a = 0; a < max_n_actions; ++a) {
-      const int r = drlgx_step_plan(e, actions_dev, n_actions_dev, a, map_last_only);
-      if (r) return r;
-    }
-    return DRLGX_OK;
-  }
-  LaunchSel sel{0, S.n_envs, nullptr, n_actions_dev, 0};
+  LaunchSel sel{0, e->S.n_envs, nullptr, n_actions_dev, 0};
   sel.map_last_only = map_last_only ? 1 : 0;
-  for (int &v : e->pbound) v = std::min(v + max_n_actions, S.P_max);
-  {
-    ScopedTimer t(e, 5);
-    if (a_sw > 0) {
-      sel.pcap = std::min(pbe + 1, S.P_max);
-      drlgx_launch_step_loop(S, e->stream, sel, actions_dev, S.A_max * 3, 2, a_sw);
-    }
-    if (a_sw < max_n_actions) {
-      sel.act_idx = a_sw;
-      sel.pcap = std::min(pbe + a_sw + 1, S.P_max);
-      drlgx_launch_step_arrow_loop(S, e->stream, sel, actions_dev, S.A_max * 3, 2, max_n_actions);
-    }
+  const int a_begin = launch_action_range(e, sel, actions_dev, 2, max_bound(e), max_n_actions, false, false);  // (all of them or none)
+  advance_pbound(e, a_begin);
+  for (int a = a_begin; a < max_n_actions; ++a) {
+    const int r = drlgx_step_plan(e, actions_dev, n_actions_dev, a, map_last_only);
+    if (r) return r;
   }
   return check_launch(e);
 }
@@ -797,7 +852,7 @@ int drlgx_stage_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const
 int drlgx_stage_move(drlgx_engine *e, const double *odom_dev, const uint8_t *active_dev) {
   DRLGX_ENTER(e);
   if (!e || !odom_dev) return DRLGX_E_INVALID;
-  for (int &v : e->pbound) v = std::min(v + 1, e->S.P_max);
+  advance_pbound(e, 1);
   drlgx_launch_sim_stage(e->S, e->stream, LaunchSel{0, e->S.n_envs, active_dev, nullptr, 0}, odom_dev, 0, nullptr, nullptr, nullptr);
   return check_launch(e);
 }
@@ -825,7 +880,7 @@ int drlgx_stage_optimize(drlgx_engine *e, const uint8_t *active_dev) {
 int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebuild) {
   DRLGX_ENTER(e);
   if (!e) return DRLGX_E_INVALID;
-  drlgx_launch_map(e->S, e->stream, LaunchSel{0, e->S.n_envs, active_dev, nullptr, rebuild ? 0 : -2});
+  drlgx_launch_map(e->S, e->stream, LaunchSel{0, e->S.n_envs, active_dev, nullptr, 0}, rebuild ? 1 : 0);
   return check_launch(e);
 }
 
@@ -962,7 +1017,6 @@ int drlgx_line_plan(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, co
 
 int drlgx_lookahead(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev,
                     const int32_t *n_actions_dev, double *rewards_dev) {
-  DRLGX_ENTER(e);
   if (!e) return DRLGX_E_INVALID;
   return drlgx_lookahead_bounded(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->S.A_max, rewards_dev);
 }
@@ -1000,74 +1054,13 @@ int drlgx_lookahead_bounded(drlgx_engine *e, int n_cand, const int32_t *cand_env
                         &S);  // (with the base solve's covariance panel)
       drlgx_launch_fix_rollouts(S, e->stream, nc, ce, roll0);
     }
-    // Whole action lists per launch (k_step_loop / k_step_arrow_loop).  A launch per action index picks its kernel from the pose
-    // bound of THAT action (the fused dense-solver step while it serves the bound, then the step around the pose-chain solver);
-    // the loop form keeps that choice action by action - the leading actions [0, a_sw) in the dense loop kernel, the rest in the
-    // pose-chain one - because the two solvers round differently and the reference's integer worlds hold cells at exactly
-    // max_range from a pose: one ulp of a pose decides them, and with them O(0.1) of a reward.
-    int a_sw = 0;
-    while (a_sw < max_n_actions && drlgx_step_fusable(S, std::min(pbe + a_sw + 1, S.P_max))) ++a_sw;
-    const bool rest_loops = a_sw == max_n_actions || drlgx_step_arrow_fusable(S);
-    int a_begin = 0;  // first action index still to be launched one by one
-    if (e->la_loop && !e->per_stage && (a_sw > 0 || rest_loops)) {
-      LaunchSel sel{roll0, nc, nullptr, na, 0};
-      sel.map_last_only = 1;
-      if (e->la_presim && rest_loops) {  // (only when EVERY action is replayed: k_presim leaves the ground truth and the streams of the LAST action)
-        // the simulator of every rollout for its whole list first (one wave per rollout), its log replayed action by action
-        const size_t entry = drlgx_simlog_entry_bytes(S), roll = entry * (size_t)S.A_max;
-        if (!e->simlog_dev && dev_alloc(e, &e->simlog_dev, roll * (size_t)S.n_roll) != DRLGX_OK) {
-          (void)hipGetLastError();
-          e->last_error.clear();
-          e->la_presim = false;  // (no room for the log: the rollouts simulate inside their steps)
-        } else {
-          ScopedTimer t(e, 0);
-          drlgx_launch_presim(S, e->stream, sel, act, S.A_max * 3, 1, max_n_actions, e->simlog_dev, roll, (int)entry);
-          sel.simlog = e->simlog_dev;
-          sel.simlog_roll = roll;
-          sel.simlog_act = (int)entry;
-        }
-      }
-      ScopedTimer t(e, 5);
-      if (a_sw > 0) {
-        sel.act_idx = 0;
-        sel.pcap = std::min(pbe + 1, S.P_max);
-        drlgx_launch_step_loop(S, e->stream, sel, act, S.A_max * 3, 1, a_sw);
-      }
-      a_begin = a_sw;
-      if (a_sw < max_n_actions && rest_loops) {
-        sel.act_idx = a_sw;
-        sel.pcap = std::min(pbe + a_sw + 1, S.P_max);
-        drlgx_launch_step_arrow_loop(S, e->stream, sel, act, S.A_max * 3, 1, max_n_actions);
-        a_begin = max_n_actions;
-      }
-    }
+    // whole action lists per launch where the loop kernels serve them, one launch per action index from a_begin on
+    LaunchSel sel{roll0, nc, nullptr, na, 0};
+    sel.map_last_only = 1;
+    const int a_begin = launch_action_range(e, sel, act, 1, pbe, max_n_actions, true, true);
     for (int a = a_begin; a < max_n_actions; ++a) {
-      LaunchSel sel{roll0, nc, nullptr, na, a};
-      sel.map_last_only = 1;
-      const int pb = std::min(pbe + a + 1, S.P_max);
-      sel.pcap = pb;
-      if (drlgx_step_fusable(S, pb) && !e->per_stage) {
-        ScopedTimer t(e, 5);
-        drlgx_launch_step(S, e->stream, sel, act, S.A_max * 3, 1);
-        continue;
-      }
-      if (drlgx_step_arrow_fusable(e->S) && !e->per_stage) {
-        ScopedTimer t(e, 5);
-        drlgx_launch_step_arrow(S, e->stream, sel, act, S.A_max * 3, 1);
-        continue;
-      }
-      {
-        ScopedTimer t(e, 0);
-        drlgx_launch_sim(S, e->stream, sel, act, S.A_max * 3, 1);
-      }
-      {
-        ScopedTimer t(e, 1);
-        drlgx_launch_slam(S, e->stream, sel, pb);
-      }
-      {
-        ScopedTimer t(e, 2);
-        drlgx_launch_map(S, e->stream, sel);
-      }
+      sel.act_idx = a;
+      launch_belief_step(e, sel, act, S.A_max * 3, 1, std::min(pbe + a + 1, S.P_max), false);
     }
     drlgx_launch_rewards(S, e->stream, nc, ce, roll0, rewards_dev + c0);
   }
@@ -1340,8 +1333,7 @@ int drlgx_snapshot(drlgx_engine *e, int slot) {
   if (!e || slot < 0 || slot >= e->S.cfg.max_snapshots) return DRLGX_E_INVALID;
   const DrlgxState &S = e->S;
   ScopedTimer t(e, 3);
-  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, 0,
-                    2 * S.n_envs + S.n_roll + slot * S.n_envs, 0, e->S.cnt, &S);
+  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, 0, snapshot_base(e, slot), 0, e->S.cnt, &S);
   e->snap_pbound[slot] = e->pbound;
   return check_launch(e);
 }

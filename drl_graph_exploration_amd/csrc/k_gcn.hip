@@ -1311,10 +1311,7 @@ __global__ void k_splitk_reduce(int n, int S, const float *part, float *out) {
 
 // read-out layers of up to this many outputs are served by the one-pass kernels below (k_linear_out, k_dz2_sums / k_dz2: H2 is
 // read once, HBM-bound); wider ones (the critic: 100) by the matrix-core products with the epilogues EPI 2 / 3
-#ifndef DRLGX_THIN_OUT
-#define DRLGX_THIN_OUT 8  // (-DDRLGX_THIN_OUT=128: the one-pass kernels for every width, A/B runs)
-#endif
-constexpr int kThinOut = DRLGX_THIN_OUT;
+constexpr int kThinOut = 8;
 // out[n][o] = sum_c H2m[n][c] Wf[o][c] + bf[o]    (Linear 1000 -> out_dim); one wave per (node, o-chunk)
 __global__ __launch_bounds__(256) void k_linear_out(int N, int hidden, int out_dim, const float *H2m, const float *Wf, const float *bf,
                                                     float *out) {
@@ -1595,11 +1592,9 @@ void gemm_tn_splitk(hipStream_t st, const GcnWs &w, int M, int N, int K, const f
     gemm<true, false, 0>(st, M, N, K, A, lda, B, ldb, C, N, nullptr, nullptr, 1);
     return;
   }
-#ifndef DRLGX_THIN_TN_WIDE  // (A/B: the tall tile for the thin product too)
-  if (max_splits > 8)  // thin M: 64 x 64 tiles
+  if (max_splits > 8)  // thin M: 64 x 64 tiles (the tall tile is slower here: profiles/r04_ab_gemm_tall_tiles.txt)
     gemm_tile<true, false, 0, 1, 1>(st, M, N, K, A, lda, B, ldb, w.part, N, nullptr, nullptr, kps);
   else
-#endif
     gemm<true, false, 0>(st, M, N, K, A, lda, B, ldb, w.part, N, nullptr, nullptr, S);
   hipLaunchKernelGGL(k_splitk_reduce, dim3((M * N + 255) / 256), dim3(256), 0, st, M * N, S, w.part, C);
 }

@@ -36,13 +36,8 @@
 
 constexpr int IYS = 18;  // row stride (doubles) of the Y / U' / W' images: 16 columns in ks16 order + 2 pad (144 B)
 constexpr int INF = 64;  // most bearing-range factors one step may add on this path
-#ifndef INC_STREAM_KB
-#define INC_STREAM_KB 512
-#endif
-#ifndef INC_ISNT
-#define INC_ISNT 4
-#endif
-constexpr int ISNT = INC_ISNT;  // the streamed form of the update (panel in HBM / L2): at most 8 ISNT re-observed landmarks per walk over the panel
+constexpr int kStreamKB = 512;  // a Y image (n1 x a0 doubles) beyond this many KB: the streamed form
+constexpr int ISNT = 4;  // the streamed form of the update (panel in HBM / L2): at most 8 ISNT re-observed landmarks per walk over the panel
 
 __device__ __forceinline__ int *inc_meta(const DrlgxState &S, int inst) { return S.jc_meta + (size_t)inst * 4; }
 
@@ -501,14 +496,9 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
         const int it = e / npr, pr = e - it * npr, I = wave + kWaves * it;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-#ifdef INC_EXP_NOLOAD
-          c0[r] = 0.0;
-          c1[r] = 0.0;
-#else
           const double *rw = rowp(16 * I + lr + 4 * r) + 32 * pr + lc;
           c0[r] = rw[0];
           c1[r] = rw[16];
-#endif
         }
       };
       auto unit = [&](int e, v4d &acc0, v4d &acc1) {
@@ -587,14 +577,12 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
               }
           }
         }
-#ifndef INC_EXP_NOSTORE
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           double *rw = rowp(16 * I + lr + 4 * r) + 32 * pr + lc;
           rw[0] = acc0[r];
           rw[16] = acc1[r];
         }
-#endif
       };
       // (straight-line body: every iteration issues the same loads - past the end a repeat of the last unit's tiles, never used -
       // so that the wait in front of a unit's products can count them.  With the loads under `if (e + 1 < nun)` the compiler
@@ -694,7 +682,6 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
     // S2. T = R + A Ya and v = -e - A delta by everybody (T as the register dumps of its NT x NT tiles, where the images of W' go
     // afterwards); W' = -T^-1 by one wave.  (Assembled in registers by that wave alone the compiler requested every operand of every
     // entry at once: 160 loads in flight at NT = 2, and every belief kernel of this translation unit spilled.)
-#ifndef INC_EXP_NO_S2
     {
       if (tid < 16 * NT) {
         double v = 0.0;
@@ -782,7 +769,6 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
           for (int r = 0; r < 4; ++r) o[r] = (16 * mt + lc < k && 16 * t + lr + 4 * r < k) ? T[t][mt][r] : 0.0;
         }
     }
-#endif
     __syncthreads();
     if (b0 == 0) DRLGX_PROF(S, 37);
     else DRLGX_PROF(S, 39);  // (a second batch: start of its walk)
@@ -796,27 +782,11 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
       const int q = 3 * P + 16 * (I - TP) + j;
       return q < n1 ? q : -1;
     };
-#ifndef INC_EXP_NO_S3
     if (wave < ntr) {
       const int nun = ((ntr - wave + kWaves - 1) / kWaves) * npr;
       const int nksl = (k - 16 * (NT - 1) + 3) >> 2;  // K steps with live columns in the last factor tile
       v4d aA0, aA1, aB0, aB1;
       double ua[NT][4];
-      // the operands of a row tile's Y^T entries, requested a whole row tile ahead: the first three columns of this lane's row and
-      // its entries in the columns of the batch's landmarks (lines the tile loads behind them want anyway)
-      double gp[3], gl0[NT][4], gl1[NT][4];
-      auto gather = [&](int I) {
-        const double *rw = rowp(max(rowq(I, lc), 0));
-        gp[0] = rw[0]; gp[1] = rw[1]; gp[2] = rw[2];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int ss = 0; ss < 4; ++ss) {
-            const int cl = reinterpret_cast<const int *>(jt + 8 * (16 * t + lr + 4 * ss) + 5)[0];
-            gl0[t][ss] = rw[cl];
-            gl1[t][ss] = rw[cl + 1];
-          }
-      };
       auto loads = [&](int e, v4d &c0, v4d &c1) {
         const int it = e / npr, pr = e - it * npr, I = wave + kWaves * it;
 #pragma unroll
@@ -927,7 +897,6 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
       }
       if (e < nun) unit(e, aA0, aA1);
     }
-#endif
     __syncthreads();
     if (b0 == 0) DRLGX_PROF(S, 38);
     else DRLGX_PROF(S, 47);  // (... and its end)
@@ -939,10 +908,9 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
   // 105 / 91 at 204, where the second half of Y no longer fits the LDS; profiles/r06_ab_streamed_update.txt).  One form per update:
   // Ya lies where the other form keeps Y.
   bool streamed = false;
-  if constexpr (!kLds && kSNT > 0)
-#ifndef INC_EXP_NOSTREAM
-    streamed = x.snt > 0 && (n_re > (x.wide ? 16 : 8) || (size_t)n1 * a0 * 8 > (size_t)(INC_STREAM_KB << 10));
-#endif
+  if constexpr (!kLds && kSNT > 0) {
+    streamed = x.snt > 0 && (n_re > (x.wide ? 16 : 8) || (size_t)n1 * a0 * 8 > (size_t)(kStreamKB << 10));
+  }
   // (a loop per form: in one loop the invariants of both forms were hoisted in front of it and lived side by side - 170 B of scratch)
   if (streamed) {
     if constexpr (!kLds && kSNT > 0) {

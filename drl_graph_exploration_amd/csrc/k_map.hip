@@ -188,9 +188,7 @@ struct LadderEntry {
 // then exactly the poses that see it, up to cells inside min_range - ONE mask per cell, those rare pairs carry a sentinel
 // in their stage entry) and keeps the stage compact: entry k of the in-range pair list instead of a slot per (pose, window
 // cell), found through a 16-bit index table.  Same arithmetic in the same order: bit-equal results.
-#ifndef KMAPC_WAVES
-#define KMAPC_WAVES 4
-#endif
+constexpr int kMapCWaves = 4;  // waves per SIMD k_map_c is compiled for (__launch_bounds__: <= 128 VGPRs)
 constexpr int kPairsPerPose = 40;  // in-range cells per pose the compact stage has room for (the disc of radius max_range
                                    // holds ~28 cell centres of the 7 x 7 window, never more than 32)
 // the planes of instance s -> d, by the whole workgroup (LaunchSel::vm_from: an instance whose planes this launch does not rebuild)
@@ -743,7 +741,7 @@ __global__ __launch_bounds__(kThreads) void k_map(DRLGX_KS_PARAM, LaunchSel sel,
 }
 // The multi-resident form: <= 128 VGPRs (four waves per SIMD) and, with the compact carve, <= 80 KB of LDS - two workgroups
 // per CU, each covering the other's dependent chains and barriers.  Launched when there are more instances than CUs.
-__global__ __launch_bounds__(kThreads, KMAPC_WAVES) void k_map_c(DRLGX_KS_PARAM, LaunchSel sel, int rebuild, int chunk) {
+__global__ __launch_bounds__(kThreads, kMapCWaves) void k_map_c(DRLGX_KS_PARAM, LaunchSel sel, int rebuild, int chunk) {
   const DrlgxState &S = DRLGX_KS_REF;
   map_body<true>(S, sel, rebuild, chunk);
 }
@@ -806,13 +804,7 @@ bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound) {
   return map_form() != 0 && map_lds_bytes_compact(S, p_bound, &cchunk) != 0;
 }
 
-void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel) {
-  // sel.act_idx == -2 encodes "reductions only" (used after reset)
-  int rebuild = 1;
-  if (sel.act_idx == -2) {
-    rebuild = 0;
-    sel.act_idx = 0;
-  }
+void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel, int rebuild) {
   int chunk = 0;
   const size_t lds = drlgx_map_lds_bytes(S, &chunk, sel.pcap);
   static bool attr_set[32] = {false};

@@ -1618,12 +1618,7 @@ struct SlamCtx {
     __syncthreads();
     DRLGX_PROF(S, 4);
     // ---- 5. sweep: one tile row per wave (sweep_packed_fast); 9 - 10 tile rows: the tiles dealt over seven waves ----
-#ifdef DRLGX_SWEEP_REGTILES  // (A/B: nine and ten tile rows as tiles dealt over seven waves, three barriers per block step)
-    if (Tn <= FT) sweep_packed_fast<FT>(S, A, np, N, Tn, bad, tid, pre_e0, e0);
-    else sweep_regtiles<true, 8>(A, A, np, N, Tn, Tn * (Tn + 1) / 2, bad, tid);
-#else
     sweep_packed_fast<FT>(S, A, np, N, Tn, bad, tid, pre_e0, e0);  // (nine / ten rows: two light rows share a wave)
-#endif
     __syncthreads();
     DRLGX_PROF(S, 5);
     for (int k = tid; k < np; k += kThreads) d_pose[k] = A[AT(np, k)];

@@ -253,49 +253,38 @@ bool drlgx_step_arrow_fusable(const DrlgxState &S) {
          (size_t)(2 * DRLGX_MT_STRIDE * 4 + (2 * S.LG + 2) * 8 + S.LG * 4) <= (size_t)kslam::kLdsBudget;
 }
 
-void drlgx_launch_step_arrow(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure) {
+// The host side of every fused-step launch: the map stage's chunk for the pose bound `pb`, the kernel's LDS attribute (one flag
+// array per instantiation, that is per kernel symbol) and the launch.  state: what the kernel takes first; tail: a_end of the loop forms.
+template <auto kKernel, typename State, typename... Tail>
+static void launch_fused(const DrlgxState &S, State state, hipStream_t st, const LaunchSel &sel, int pb, const double *odom, int odom_stride,
+                         int n_measure, Tail... tail) {
   int chunk = 0;
-  (void)drlgx_map_lds_bytes(S, &chunk, sel.pcap);
+  (void)drlgx_map_lds_bytes(S, &chunk, pb);
   static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kstep::k_step_arrow)};
+  const void *fns[] = {reinterpret_cast<const void *>(kKernel)};
   drlgx_ensure_lds_attr(attr_set, fns, 1, kslam::kLdsBudget);
-  hipLaunchKernelGGL(kstep::k_step_arrow, dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, odom, odom_stride, n_measure,
-                     kslam::kLdsBudget, chunk);
+  hipLaunchKernelGGL(kKernel, dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, state, sel, odom, odom_stride, n_measure,
+                     kslam::kLdsBudget, chunk, tail...);
+}
+// (the loop forms size the map stage for the range's last action)
+static int last_pcap(const DrlgxState &S, const LaunchSel &sel, int a_end) { return std::min(sel.pcap + (a_end - 1 - sel.act_idx), S.P_max); }
+
+void drlgx_launch_step_arrow(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure) {
+  launch_fused<&kstep::k_step_arrow>(S, DRLGX_KS_ARG(S), st, sel, sel.pcap, odom, odom_stride, n_measure);
 }
 
 void drlgx_launch_step_arrow_loop(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end) {
-  int chunk = 0;
-  (void)drlgx_map_lds_bytes(S, &chunk, std::min(sel.pcap + (a_end - 1 - sel.act_idx), S.P_max));  // (sized for the range's last action)
-  static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kstep::k_step_arrow_loop)};
-  drlgx_ensure_lds_attr(attr_set, fns, 1, kslam::kLdsBudget);
-  hipLaunchKernelGGL(kstep::k_step_arrow_loop, dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, odom, odom_stride, n_measure,
-                     kslam::kLdsBudget, chunk, a_end);
+  launch_fused<&kstep::k_step_arrow_loop>(S, DRLGX_KS_ARG(S), st, sel, last_pcap(S, sel, a_end), odom, odom_stride, n_measure, a_end);
 }
 
 void drlgx_launch_step_loop(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end) {
-  int chunk = 0;
-  (void)drlgx_map_lds_bytes(S, &chunk, std::min(sel.pcap + (a_end - 1 - sel.act_idx), S.P_max));  // (sized for the range's last action)
-  static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kstep::k_step_loop<kslam::kFastTiles>)};
-  drlgx_ensure_lds_attr(attr_set, fns, 1, kslam::kLdsBudget);
-  hipLaunchKernelGGL((kstep::k_step_loop<kslam::kFastTiles>), dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, odom,
-                     odom_stride, n_measure, kslam::kLdsBudget, chunk, a_end);
+  launch_fused<&kstep::k_step_loop<kslam::kFastTiles>>(S, DRLGX_KS_ARG(S), st, sel, last_pcap(S, sel, a_end), odom, odom_stride, n_measure, a_end);
 }
 
 void drlgx_launch_step(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure) {
-  int chunk = 0;
-  (void)drlgx_map_lds_bytes(S, &chunk, sel.pcap);
-  static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kstep::k_step<kslam::kFastTiles>),
-                       reinterpret_cast<const void *>(&kstep::k_step_ref<kslam::kFastTiles>)};
-  drlgx_ensure_lds_attr(attr_set, fns, 2, kslam::kLdsBudget);
   // (DRLGX_STATE_PTR=0: the struct by value, the A/B of profiles/r05_ab_state_pointer.txt / r06_ab_state_const.txt)
   static const bool by_value = [] { const char *sp = getenv("DRLGX_STATE_PTR"); return sp && sp[0] == '0'; }();
-  if (!by_value)
-    hipLaunchKernelGGL((kstep::k_step_ref<kslam::kFastTiles>), dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, (DrlgxStateConst)S.self_dev, sel,
-                       odom, odom_stride, n_measure, kslam::kLdsBudget, chunk);
-  else
-    hipLaunchKernelGGL((kstep::k_step<kslam::kFastTiles>), dim3(sel.n), dim3(kslam::kThreads), kslam::kLdsBudget, st, S, sel, odom,
-                       odom_stride, n_measure, kslam::kLdsBudget, chunk);
+  // (the by-value twin first: the code object holds the kernels in the order of their first use)
+  if (by_value) launch_fused<&kstep::k_step<kslam::kFastTiles>, const DrlgxState &>(S, S, st, sel, sel.pcap, odom, odom_stride, n_measure);
+  else launch_fused<&kstep::k_step_ref<kslam::kFastTiles>>(S, DRLGX_KS_ARG(S), st, sel, sel.pcap, odom, odom_stride, n_measure);
 }
