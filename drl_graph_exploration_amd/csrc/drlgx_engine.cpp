@@ -490,7 +490,7 @@ static int build_engine(drlgx_engine *e) {
   TRY(upload_table(e, &S.lo_pv, lo_pv));
   TRY(upload_table(e, &S.lo_tr, lo_tr));
   TRY(alloc_fields(e));
-  // SLAM workspace (not copied between instances; k_slam.hip: drlgx_slam_ws_doubles)
+  // SLAM workspace (not copied between instances; k_slam_host.hip: drlgx_slam_ws_doubles)
   S.slam_ws_stride = drlgx_slam_ws_doubles(S.P_max, S.L_max, S.M_max);
   S.slam_iws_stride = 2;
   TRY(dev_alloc(e, &S.slam_ws, S.slam_ws_stride * (size_t)S.n_inst));

@@ -1,7 +1,8 @@
 // SLAM belief update for long trajectories (any number of poses): the same linear system and outputs as slam_body
 // (k_slam.hip), solved in the fill-reducing order of this problem instead of densely on the poses.
 //
-// Included by k_slam.hip inside namespace kslam.  Restates SLAM2D::optimize / copy_optimize
+// Part of the unity build k_step.hip: arrow_body and the kernel k_slam_arrow; k_step_arrow (k_step.hip) runs arrow_body after
+// its simulator.  Restates SLAM2D::optimize / copy_optimize
 // (src/em_exploration/SLAM2D.cpp:374-488; gtsam ISAM2::update policy in SURVEY.md App. A.3) and the block marginals of
 // FastMarginals (src/em_exploration/FastMarginals.cpp:130-186).
 //
@@ -30,6 +31,11 @@
 // S_{r,i} = -(S_rl GL_i^T + S_rr GR_i^T), S_ii = E_i - GL_i S_{l,i} - GR_i S_{r,i}, where the cross block S_lr of the two
 // neighbours is the one stored by whichever of them is eliminated at the next level.
 
+#pragma once
+#include "k_inc.hip"
+#include "k_sweep_ws.hip"
+namespace kslam {
+#pragma clang fp contract(fast)
 // symmetric 3x3 (a00 a01 a02 a11 a12 a22) -> inverse in the same storage; returns the determinant's sign test
 __device__ __forceinline__ bool inv3s(const double *a, double *o) {
   const double c00 = a[3] * a[5] - a[4] * a[4], c01 = a[2] * a[4] - a[1] * a[5], c02 = a[1] * a[4] - a[2] * a[3];
@@ -783,8 +789,8 @@ __device__ __forceinline__ void arrow_body(const DrlgxState &S, const LaunchSel 
   if (c_lds)
     sweep_packed_fast<kFastTilesArrow>(S, A, np, N, Tn, bad, tid);
   else if constexpr (NTW > 0) {
-    if (c_reg) sweep_regtiles<false, NTW>(A, panels, np, N, Tn, ntiles, bad, tid);
-    else sweep_streamed(A, pws, panels, np, N, Tn, bad, tid);
+    if (c_reg) sweep_ws<NTW>(A, panels, panels + 16 * N, panels + 32 * N, np, N, Tn, bad, tid);
+    else sweep_ws<0>(A, pws, pws + 16 * (size_t)N, panels, np, N, Tn, bad, tid);
   }
   __syncthreads();
   DRLGX_PROF(S, 7);
@@ -1171,3 +1177,5 @@ __global__ __launch_bounds__(kThreads) void k_slam_arrow(DRLGX_KS_PARAM, LaunchS
   const DrlgxState &S = DRLGX_KS_REF;
   arrow_body<NTW>(S, sel, lds_bytes);
 }
+#pragma clang fp contract(off)
+}  // namespace kslam

@@ -12,12 +12,18 @@
 //
 // This translation unit is a unity build of the three stage files (their kernels stay available for the paths that use
 // them alone: reset, the look-ahead base solve, capacities beyond the LDS-resident SLAM kernel).  It is compiled with
-// -ffp-contract=off (simulator and map decisions must round like the CPU reference); k_slam.hip re-enables contraction
-// for its own functions.
+// -ffp-contract=off (simulator and map decisions must round like the CPU reference); the SLAM parts re-enable contraction
+// for their own functions.
 #include "drlgx_dev.h"
 
 #include "k_sim.hip"
-#include "k_slam.hip"
+// the SLAM stage, in the order its parts build on one another (each includes what it needs itself)
+#include "k_sweep.hip"        // block Gauss-Jordan primitives on the fp64 matrix cores, the sweep of a packed LDS system
+#include "k_slam_common.hip"  // capacities, factor linearisation and pose blocks, SubBarrier / SimBox
+#include "k_inc.hip"          // incremental (rank-k) update, inc_stage
+#include "k_slam.hip"         // dense solver: SlamCtx, slam_finish, k_slam
+#include "k_slam_arrow.hip"   // pose-chain solver: arrow_body, k_slam_arrow (+ k_sweep_ws.hip, its workspace sweep)
+#include "k_slam_host.hip"    // LDS / workspace sizing, drlgx_launch_slam
 #include "k_map.hip"
 
 namespace kstep {

@@ -1,5 +1,5 @@
 """Lane-level emulation (numpy) of the MFMA block-pivot 16 x 16 inversion used by k_slam's sweep (inv16_blk):
-checks the index algebra of the HIP code against numpy.linalg.inv.  Conventions = those of k_slam.hip:
+checks the index algebra of the HIP code against numpy.linalg.inv.  Conventions = those of k_sweep.hip:
 lane = 16 lr + lc; A operand lane -> A[i = lc][k = lr]; B operand lane -> B[k = lr][j = lc];
 accumulator reg r, lane -> C[lr + 4 r][lc]."""
 import numpy as np

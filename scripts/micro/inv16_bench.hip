@@ -1,6 +1,6 @@
 // Dev tool: time and check k_slam's in-wave 16 x 16 symmetric inversions (scalar pivots: inv16, 4 x 4 block pivots on the
 // matrix cores: inv16_blk) in isolation, warm (best of 20) and cold (first execution of the code by the kernel).
-#include "../../drl_graph_exploration_amd/csrc/k_slam.hip"
+#include "../../drl_graph_exploration_amd/csrc/k_sweep_ws.hip"  // inv16; brings k_sweep.hip (inv16_blk) with it
 #include <cstdio>
 #include <vector>
 #include <cmath>

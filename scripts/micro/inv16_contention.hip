@@ -1,6 +1,6 @@
 // Dev tool: does k_slam's in-register 16 x 16 inversion slow down when the other waves of the workgroup run LDS traffic /
 // fp64 MFMAs (as the U phase does)?  mode 0: alone, 1: others do LDS b128 reads, 2: others do fp64 MFMAs, 3: both.
-#include "../../drl_graph_exploration_amd/csrc/k_slam.hip"
+#include "../../drl_graph_exploration_amd/csrc/k_sweep_ws.hip"  // inv16; brings k_sweep.hip (inv16_blk) with it
 #include <cstdio>
 #include <vector>
 using namespace kslam;

@@ -1,5 +1,5 @@
 """Dev tool: in-kernel phases of a belief update that RELINEARISES (full dense solve + the covariance panel it leaves,
-csrc/k_slam.hip + k_inc.hip: panel_from_dense) at the bench workload: the envs are stepped from the snapshot until the next
+csrc/k_slam.hip: SlamCtx, panel_from_dense) at the bench workload: the envs are stepped from the snapshot until the next
 update is a 10th one, then that update is profiled per workgroup.   phase_profile_relin.py [workgroup ...]"""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
