@@ -6,7 +6,7 @@ batch=None)` and `state_dict` keys/shapes (`conv1.weight [5,1000]` i.e. [in,out]
 `MyModel.pt` files load unchanged (scripts/test.py:38-45, scripts/run_training.py:22-36).
 
 The trunk  H1 = relu(Â X W1 + b1), H2 = relu(Â H1 W2 + b2) * dropout_mask, out = H2 Wf^T + bf  runs in
-`drlgx_gcn_forward / drlgx_gcn_backward` (csrc/k_gcn.hip: CSR aggregation + fp32-MFMA GEMMs); torch supplies only
+`drlgx_gcn_forward / drlgx_gcn_backward` (csrc/k_gcn.hip and its parts k_gcn_csr / k_gcn_agg / k_gemm / k_gcn_thin.hip: CSR aggregation + fp32-MFMA GEMMs); torch supplies only
 device memory, the dropout mask (torch RNG) and the tiny heads (segment softmax / mean pool).
 `data` is duck-typed like a PyG `Data`/`Batch`: `.x [N,5] f32`, `.edge_index [2,E] i64`, `.edge_attr [E] f32`.
 There is no CPU fallback: tensors must live on a HIP device.

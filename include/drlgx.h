@@ -296,7 +296,7 @@ int drlgx_debug_phase_clocks_host(drlgx_engine *e, int arm, int64_t *out /* 64 v
 
 /* Development aid: the tile of C per workgroup the GCN's fp32 GEMM dispatcher picks for an m x n product computed in k_slices
  * K-slices (transpose_a: A is stored [K x M], the weight-gradient products), as 1000 * columns + rows: 64064 = the 64x64
- * kernels, 128096..128160 / 64096..64160 = the tall-tile kernel k_gemm_wide with 8 / 4 waves (csrc/k_gcn.hip).  The numerics
+ * kernels, 128096..128160 / 64096..64160 = the tall-tile kernel k_gemm_wide with 8 / 4 waves (csrc/k_gemm.hip).  The numerics
  * tests use it to prove that they cover every compiled tile. */
 int drlgx_debug_gemm_tile_rows(int m, int n, int k_slices, int transpose_a);
 

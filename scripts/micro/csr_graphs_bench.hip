@@ -1,6 +1,6 @@
-// k_csr_graphs (csrc/k_gcn.hip) alone over G synthetic graphs of ~68 nodes / ~470 edges: time against G.
+// k_csr_graphs (csrc/k_gcn_csr.hip) alone over G synthetic graphs of ~68 nodes / ~470 edges: time against G.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I drl_graph_exploration_amd/csrc -I include scripts/micro/csr_graphs_bench.hip -o /tmp/csrb
-#include "../../drl_graph_exploration_amd/csrc/k_gcn.hip"
+#include "../../drl_graph_exploration_amd/csrc/k_gcn_csr.hip"
 #include <cstdio>
 #include <vector>
 int main() {

@@ -1,6 +1,6 @@
-// Micro-benchmark (dev tool): the fp32 MFMA GEMM of k_gcn.hip on the shapes the GCN uses, without the rest of the layer.
+// Micro-benchmark (dev tool): the fp32 MFMA GEMM of csrc/k_gemm.hip on the shapes the GCN uses, without the rest of the layer.
 // build: hipcc -O3 --offload-arch=gfx950 -I include -I drl_graph_exploration_amd/csrc -o scripts/micro/gemm_bench.bin scripts/micro/gemm_bench.hip
-#include "../../drl_graph_exploration_amd/csrc/k_gcn.hip"
+#include "../../drl_graph_exploration_amd/csrc/k_gemm.hip"
 #include <cstdio>
 #include <vector>
 

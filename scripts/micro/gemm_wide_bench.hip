@@ -1,8 +1,8 @@
 // Experiment (dev tool): the three hidden x hidden products of a GCN train step (forward with epilogue, dZ2 W2^T, split-K
 // AH1^T dZ2) through the tall-tile kernel k_gemm_wide at every tile height, against the 64x64 direct-to-LDS kernel
-// (both in csrc/k_gcn.hip): result check and time.
+// (both in csrc/k_gemm.hip): result check and time.
 // build: hipcc -O3 --offload-arch=gfx950 -I include -I drl_graph_exploration_amd/csrc -o scripts/micro/gemm_wide_bench.bin scripts/micro/gemm_wide_bench.hip
-#include "../../drl_graph_exploration_amd/csrc/k_gcn.hip"
+#include "../../drl_graph_exploration_amd/csrc/k_gemm.hip"
 #include <cstdio>
 #include <vector>
 
