@@ -737,6 +737,7 @@ void drlgx_launch_line_plan(const DrlgxState &S, hipStream_t st, int n_cand, con
 bool drlgx_slam_in_lds(int P_max, int L_max, int M_max);       // the fused LDS-resident kernel serves up to P_max poses
 bool drlgx_slam_capacity_ok(int P_max, int L_max, int M_max);  // capacities the SLAM kernels can serve at all
 size_t drlgx_slam_ws_doubles(int P_max, int L_max, int M_max);  // HBM workspace per instance (doubles)
+bool drlgx_graph_capacity_ok(int P_max, int L_max, int V);     // the LDS tables of the graph export fit (checked by drlgx_create)
 void drlgx_launch_graph(const DrlgxState &S, hipStream_t st, int *gi, int gi_stride, int32_t *node_off, int32_t *edge_off,
                         float *x, int64_t *edge_index, float *edge_attr, int32_t *n_frontier, double *frontier_xy,
                         int32_t *nearest_node, int max_frontier);

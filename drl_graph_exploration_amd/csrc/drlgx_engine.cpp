@@ -178,15 +178,32 @@ int check_launch(drlgx_engine *e) {
     if (r_) return r_;     \
   } while (0)
 
+// why the last drlgx_create of this thread failed: what drlgx_last_error(NULL) returns, no engine being left to ask
+static thread_local std::string g_create_error;
+
 static int check_config(const drlgx_config *cfg, int n_envs, int n_rollouts) {
   if (!cfg || n_envs <= 0 || n_rollouts < 0) return DRLGX_E_INVALID;
   if (cfg->max_poses < 2 || cfg->max_landmarks < 1 || cfg->max_factors < 1 || cfg->num_landmarks < 0 ||
-      cfg->max_actions < 1 || cfg->num_samples < 1 || !(cfg->resolution > 0))
+      cfg->max_actions < 1 || cfg->num_samples < 1)
     return DRLGX_E_INVALID;
+  // the interior cell count divides by (int)resolution, as VirtualMap.cpp:341 does (set_map_constants): a resolution below 1
+  // (NaN included) is a division by zero there
+  if (!(cfg->resolution >= 1)) {
+    g_create_error = "resolution must be at least 1";
+    return DRLGX_E_INVALID;
+  }
   // kernel limits: 16-bit pose / landmark / factor indices in LDS tables; the per-pose / per-landmark tables of k_slam_arrow
   // must fit the LDS (its landmark system is streamed from the workspace beyond 127 landmarks)
   if (cfg->max_poses > 65535 || cfg->max_landmarks > 65535 || cfg->max_factors > 65534) return DRLGX_E_INVALID;
   if (!drlgx_slam_capacity_ok(cfg->max_poses, cfg->max_landmarks, cfg->max_factors)) return DRLGX_E_INVALID;
+  // the graph export keeps a frontier table per cell and an observation table per (landmark, pose) pair in LDS (k_graph.hip);
+  // drlgx_slam_capacity_ok does not bound that product (500 landmarks x 200 poses pass it and need 200 KB there)
+  const double cells = std::floor((cfg->map_max_x - cfg->map_min_x) / cfg->resolution) *
+                       std::floor((cfg->map_max_y - cfg->map_min_y) / cfg->resolution);  // (set_map_constants: S.V; it refuses V <= 0)
+  if (!(cells <= 65535.0) || !drlgx_graph_capacity_ok(cfg->max_poses, cfg->max_landmarks, (int)cells)) {
+    g_create_error = "max_landmarks x max_poses (or the cell count of the map) too large for the LDS tables of the graph export";
+    return DRLGX_E_INVALID;
+  }
   return DRLGX_OK;
 }
 
@@ -516,10 +533,14 @@ const char *drlgx_strerror(int code) {
   }
 }
 
-const char *drlgx_last_error(const drlgx_engine *e) { return e ? e->last_error.c_str() : "null engine"; }
+const char *drlgx_last_error(const drlgx_engine *e) {
+  if (e) return e->last_error.c_str();
+  return g_create_error.empty() ? "null engine" : g_create_error.c_str();
+}
 
 int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device, drlgx_engine **out) {
   if (!out) return DRLGX_E_INVALID;
+  g_create_error.clear();
   int r = check_config(cfg, n_envs, n_rollouts);
   if (r) return r;
   int ndev = 0;
@@ -540,6 +561,7 @@ int drlgx_create(const drlgx_config *cfg, int n_envs, int n_rollouts, int device
   S.n_envs = n_envs;
   S.n_roll = n_rollouts;
   if ((r = build_engine(e)) != DRLGX_OK) {
+    g_create_error = e->last_error;
     drlgx_destroy(e);
     return r;
   }

@@ -377,17 +377,32 @@ __global__ __launch_bounds__(kT) void k_graph_emit(DrlgxState S, GraphBufs G, co
   }
 }
 
+constexpr size_t kGraphLds = 160 * 1024;  // the opt-in limit drlgx_launch_graph sets
+// k_graph_build: flags | per-thread counts | frontier cell list | best cell per query
+size_t build_lds_bytes(int L_max, int V) {
+  return ((V + 15) & ~15) + (size_t)(kT + 4) * 4 + (size_t)((V + 3) & ~3) * 2 + (size_t)(L_max + 2) * 4;
+}
+// k_graph_emit: obs table [L][P] | row start offsets (N + 1 <= 2 L + P + 2)
+size_t emit_lds_bytes(int P_max, int L_max) {
+  return (((size_t)L_max * P_max * 2 + 15) & ~(size_t)15) + (size_t)(2 * L_max + P_max + 4) * 4;
+}
+
 }  // namespace
+
+// capacities and map sizes the export can launch with: both kernels' LDS within the limit (the frontier cell list holds 16-bit
+// cell indices: V <= 65535 follows from 3 V < 160 KB).  drlgx_create refuses the others, so no launch below can ask for more.
+bool drlgx_graph_capacity_ok(int P_max, int L_max, int V) {
+  return build_lds_bytes(L_max, V) <= kGraphLds && emit_lds_bytes(P_max, L_max) <= kGraphLds;
+}
 
 void drlgx_launch_graph(const DrlgxState &S, hipStream_t st, int *gi, int gi_stride, int32_t *node_off, int32_t *edge_off,
                         float *x, int64_t *edge_index, float *edge_attr, int32_t *n_frontier, double *frontier_xy,
                         int32_t *nearest_node, int max_frontier) {
   GraphBufs G{gi, gi_stride};
-  const size_t lds_a = ((S.V + 15) & ~15) + (size_t)(kT + 4) * 4 + (size_t)((S.V + 3) & ~3) * 2 + (size_t)(S.L_max + 2) * 4;
-  const size_t lds_c = (((size_t)S.L_max * S.P_max * 2 + 15) & ~(size_t)15) + (size_t)(2 * S.L_max + S.P_max + 4) * 4;
+  const size_t lds_a = build_lds_bytes(S.L_max, S.V), lds_c = emit_lds_bytes(S.P_max, S.L_max);
   static bool attr_set[32] = {false};
   const void *fns[] = {reinterpret_cast<const void *>(&k_graph_build), reinterpret_cast<const void *>(&k_graph_emit)};
-  drlgx_ensure_lds_attr(attr_set, fns, 2, 160 * 1024);
+  drlgx_ensure_lds_attr(attr_set, fns, 2, (int)kGraphLds);
   hipLaunchKernelGGL(k_graph_build, dim3(S.n_envs), dim3(kT), lds_a, st, S, G);
   hipLaunchKernelGGL(k_graph_scan, dim3(1), dim3(1024), 0, st, S, G, node_off, edge_off);
   hipLaunchKernelGGL(k_graph_emit, dim3(S.n_envs), dim3(kT), lds_c, st, S, G, node_off, edge_off, x, edge_index, edge_attr,

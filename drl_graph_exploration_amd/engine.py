@@ -32,7 +32,7 @@ class Engine(object):
         self.n_rollouts = n_rollouts
         self.device = torch.device("cuda", device)
         self.h = C.c_void_p()
-        _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)))
+        _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)), self.h)  # (NULL: the creation's error)
         r, c = C.c_int32(), C.c_int32()
         self.L.drlgx_vm_shape(self.h, C.byref(r), C.byref(c))
         self.rows, self.cols = r.value, c.value

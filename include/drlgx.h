@@ -50,7 +50,7 @@ typedef struct drlgx_config {
   /* map box = environment padded by ext = 20 m (pyss2d.py:48-55) */
   double map_min_x, map_max_x, map_min_y, map_max_y;
   /* [Virtual Map]  VirtualMap::Parameter (include/em_exploration/VirtualMap.h:17-38) */
-  double resolution, sigma0;
+  double resolution, sigma0; /* resolution >= 1: the reference divides by (int)resolution (VirtualMap.cpp:341) */
   int32_t num_samples; /* only 1 is supported (the shipped value); >1 re-averages identical maps */
   /* [Simulator] */
   double sigma_x0, sigma_y0, sigma_theta0;
@@ -80,6 +80,7 @@ int drlgx_destroy(drlgx_engine *e);
 int drlgx_set_stream(drlgx_engine *e, void *hip_stream);
 int drlgx_synchronize(drlgx_engine *e);
 const char *drlgx_strerror(int code);
+/* Text of the engine's last error; with e = NULL, why this thread's last drlgx_create failed (the engine is gone by then). */
 const char *drlgx_last_error(const drlgx_engine *e);
 /* Device-side status word of the last kernels: 0 or a DRLGX_E_* code (synchronises). */
 int drlgx_status_host(drlgx_engine *e);

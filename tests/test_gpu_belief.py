@@ -430,6 +430,27 @@ def test_capacities_beyond_the_kernels_are_refused():
     for kw in (dict(num_landmarks=4000, max_landmarks=4000), dict(max_poses=2000)):
         with pytest.raises(_lib.DrlgxError):
             Engine(default_config(MAP, **kw), 2, 0)
+    # a pair the SLAM kernels could serve whose observation table (2 x 500 x 200 bytes) is beyond the graph export's LDS: refused
+    # by the host's argument check, before anything is allocated or launched
+    with pytest.raises(_lib.DrlgxError, match="graph export"):
+        Engine(default_config(50, num_landmarks=500, max_landmarks=500, max_poses=200, max_factors=3600), 2, 0)
+
+
+def test_resolution_below_one_is_refused():
+    """The interior cell count divides by (int)resolution as VirtualMap.cpp:341 does: below 1 that is a division by zero, which
+    drlgx_create refuses in its argument check."""
+    from drl_graph_exploration_amd import _lib, default_config
+    from drl_graph_exploration_amd.engine import Engine
+    for res in (0.5, 0.999, 0.0, -2.0, float("nan")):
+        cfg = default_config(MAP)
+        cfg.resolution = res
+        with pytest.raises(_lib.DrlgxError, match="resolution"):
+            Engine(cfg, 2, 0)
+    cfg = default_config(20)
+    cfg.resolution, cfg.max_range = 1.0, 3.0  # (1 itself is served, with the reference's arithmetic: 60 x 60 cells, a 7 x 7 cell window)
+    eng = Engine(cfg, 1, 0)
+    assert (eng.rows, eng.cols) == (60, 60)
+    eng.close()
 
 
 def test_variant_follows_the_trajectory_length():

@@ -10,49 +10,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O  # noqa: E402  (checker only)
+from graph_checks import check_graphs  # noqa: E402
 
 MAP = 40
 
 
 def generic_starts(n):
     return np.array([O.start_pose(lo, MAP / 2 + 20) for lo in range(n)]) + np.array([0.3183, -0.2718, 0.1234])
-
-
-def check_graphs(eng, envs, g, skip=()):
-    n = len(envs)
-    node_off = g["node_off"].cpu().numpy()
-    edge_off = g["edge_off"].cpu().numpy()
-    x = g["x"].cpu().numpy()
-    ei = g["edge_index"].cpu().numpy()
-    ea = g["edge_attr"].cpu().numpy()
-    nfr = g["n_frontier"].cpu().numpy()
-    fxy = g["frontier_xy"].cpu().numpy()
-    near = g["nearest_frontier_node"].cpu().numpy()
-    batch = g["batch"].cpu().numpy()
-    out = []
-    for i, env in enumerate(envs):
-        if i in skip:
-            out.append((int(node_off[i + 1] - node_off[i]), int(nfr[i])))
-            continue
-        A, X, _, fro = env.graph_matrix()
-        oei, oea, ox = O.data_process(A, X)
-        N = A.shape[0]
-        assert node_off[i + 1] - node_off[i] == N
-        assert nfr[i] == fro
-        np.testing.assert_array_equal(fxy[i, :fro], np.array(env._frontier))
-        assert near[i] == env.nearest_frontier_point
-        xs = x[node_off[i]:node_off[i + 1]]
-        # features are float32 casts of float64 values computed the same way
-        np.testing.assert_allclose(xs, ox, rtol=2e-6, atol=1e-7)
-        assert np.all(xs[:, 4] == ox[:, 4])
-        E = oei.shape[1]
-        assert edge_off[i + 1] - edge_off[i] == E
-        es = ei[:, edge_off[i]:edge_off[i + 1]] - node_off[i]
-        np.testing.assert_array_equal(es, oei)  # topology and edge order exact
-        np.testing.assert_allclose(ea[edge_off[i]:edge_off[i + 1]], oea, rtol=1e-6)
-        assert np.all(batch[node_off[i]:node_off[i + 1]] == i)
-        out.append((N, fro))
-    return out
 
 
 @pytest.mark.parametrize("num_lm", [None, 60])

@@ -43,6 +43,18 @@ def test_error_strings_and_create_without_device():
     assert L.drlgx_create(C.byref(default_config(40, max_poses=4096)), 4, 0, 0, C.byref(h)) == -1 and not h.value
     assert L.drlgx_create(C.byref(default_config(40, num_landmarks=4000, max_landmarks=4000)), 4, 0, 0, C.byref(h)) == -1
     assert L.drlgx_create(C.byref(default_config(40, max_poses=1)), 4, 0, 0, C.byref(h)) == -1 and not h.value
+    # ... as are a (landmarks, poses) pair whose observation table is beyond the graph export's LDS although the SLAM kernels could
+    # serve it, and a resolution below 1 (the interior cell count divides by its integer part); drlgx_last_error(NULL) says why
+    big = default_config(50, num_landmarks=500, max_landmarks=500, max_poses=200, max_factors=3600)
+    assert L.drlgx_create(C.byref(big), 2, 0, 0, C.byref(h)) == -1 and not h.value
+    assert b"graph export" in L.drlgx_last_error(None)
+    for res in (0.5, 0.0, -2.0, float("nan")):
+        cfg = default_config(40)
+        cfg.resolution = res
+        assert L.drlgx_create(C.byref(cfg), 2, 0, 0, C.byref(h)) == -1 and not h.value
+        assert b"resolution" in L.drlgx_last_error(None)
+    assert L.drlgx_create(C.byref(default_config(40, max_poses=1)), 4, 0, 0, C.byref(h)) == -1
+    assert L.drlgx_last_error(None) == b"null engine"  # (no text for this one: the previous creation's is gone)
     if torch.cuda.is_available():
         pytest.skip("needs a box without a GPU")
     rc = L.drlgx_create(C.byref(default_config(40)), 4, 0, 0, C.byref(h))
