@@ -9,8 +9,8 @@
 #include <stdint.h>
 
 #include "../../include/drlgx.h"
+#include "map_carve.h"
 
-#define DRLGX_LO_TAB 64
 #define DRLGX_MT_N 624
 #define DRLGX_MT_STRIDE 626  // 624 state words + gen index + cons index
 #define DRLGX_CNT_STRIDE 8
@@ -40,14 +40,12 @@ struct DrlgxState {
   int n_sweep;                                         // bbox sweep table length
   const double *sweep_b;                               // [n_sweep] b values of OccupancyMap.cpp:86
   // occupancy ladder as a finite state machine (closure of l -> clamp(l + lo_occ / lo_free) from l = 0, built on the
-  // host): state 0 is LOGODDS_UNKNOWN; lo_tr[4 i] = {next on occupied, next on free, flags (1: at the minimum - frozen,
-  // 2: above the occupancy threshold), 0}; lo_pv[i] = cell probability of state i (host libm).  lo_ntab == 0: not closed
-  // within DRLGX_LO_TAB states, the kernels fall back to the arithmetic ladder.
+  // host: build_ladder; drlgx_create fails if it does not close within DRLGX_LO_TAB states): state 0 is LOGODDS_UNKNOWN;
+  // lo_pv[i] = cell probability of state i (host libm)
   int lo_ntab;
   const double *lo_pv;
-  const uint8_t *lo_tr;
-  unsigned long long lo_tocc, lo_tfree;  // lo_tr packed for <= 16 states: 4 bits per next state (occupied / free)
-  unsigned int lo_tflag;                 // 2 bits of flags per state
+  unsigned long long lo_tocc, lo_tfree;  // 4 bits per state: the next state on an occupied / a free update
+  unsigned int lo_tflag;                 // 2 bits per state: 1 at the minimum (frozen), 2 above the occupancy threshold
   double vm_i0;                          // 1 / sigma0^2 (host pow, like the reference's initialisation)
   double w_trans, w_rot, w_bear, w_range;  // 1 / noise^2 of the odometry (translation, rotation) and bearing-range factors
   const int *lm_order;                                 // [LG] libstdc++ unordered_map iteration order of GT keys
@@ -672,9 +670,9 @@ inline void drlgx_ensure_lds_attr(bool (&done)[32], const void *const *fns, int 
 __host__ __device__ inline size_t drlgx_sim_lds_bytes(int LG, int P_max) {
   size_t b = (size_t)2 * DRLGX_MT_STRIDE * 4 + (size_t)(2 * LG + 2) * 8 + (size_t)LG * 4 + 16;
   b = ((b + 7) & ~(size_t)7) + (size_t)2 * LG * 8;  // the new landmarks' initial estimates, for the SLAM stage (ksim::measure)
-  // ... and, when that costs little, wide enough for the map stage's pose tables (19 P_max doubles), so that the SLAM stage
+  // ... and, when that costs little, wide enough for the map stage's pose tables (kmap::MapCarve), so that the SLAM stage
   // can leave its outputs in them (see k_step)
-  if (P_max <= 64) b = b > (size_t)P_max * 19 * 8 + 32 ? b : (size_t)P_max * 19 * 8 + 32;
+  if (P_max <= 64) b = b > kmap::MapCarve::pose_tables_bytes(P_max) + 32 ? b : kmap::MapCarve::pose_tables_bytes(P_max) + 32;
   return (b + 31) & ~(size_t)31;
 }
 

@@ -204,6 +204,12 @@ static int check_config(const drlgx_config *cfg, int n_envs, int n_rollouts) {
     g_create_error = "max_landmarks x max_poses (or the cell count of the map) too large for the LDS tables of the graph export";
     return DRLGX_E_INVALID;
   }
+  // the map kernel keeps its per-pose tables, two masks and a landmark count per cell in LDS (kmap::MapCarve); with one pose per
+  // pass it takes the least it can
+  if (kmap::MapCarve(cfg->max_poses, 1, (int)cells, false).bytes > kmap::kLdsBudget) {
+    g_create_error = "map too large for the LDS tables of the map kernel";
+    return DRLGX_E_INVALID;
+  }
   return DRLGX_OK;
 }
 
@@ -268,9 +274,11 @@ static int set_map_constants(drlgx_engine *e) {
   return DRLGX_OK;
 }
 
-// occupancy ladder closure (see DrlgxState::lo_tr): the packed nibble tables into S, the value and transition tables for the upload
-static void build_ladder(DrlgxState &S, std::vector<double> &lo_pv, std::vector<uint8_t> &lo_tr) {
+// occupancy ladder closure (see DrlgxState::lo_tocc): the packed transition tables into S, the value table for the upload
+static int build_ladder(drlgx_engine *e, std::vector<double> &lo_pv) {
+  DrlgxState &S = e->S;
   const drlgx_config *cfg = &S.cfg;
+  std::vector<uint8_t> lo_tr;  // per state: next on occupied, next on free, flags (1: at the minimum - frozen, 2: above the threshold)
   S.lo_tocc = S.lo_tfree = 0ull;
   S.lo_tflag = 0u;
   std::vector<double> lo_val{0.0};
@@ -305,27 +313,28 @@ static void build_ladder(DrlgxState &S, std::vector<double> &lo_pv, std::vector<
       if ((size_t)f >= is_chain.size()) is_chain.push_back(0);
     }
     const uint8_t flags = (uint8_t)((frozen ? 1 : 0) | (above ? 2 : 0));
-    lo_tr.push_back((uint8_t)o); lo_tr.push_back((uint8_t)f); lo_tr.push_back(flags); lo_tr.push_back(0);
+    lo_tr.push_back((uint8_t)o); lo_tr.push_back((uint8_t)f); lo_tr.push_back(flags);
   }
-  if (closed && lo_val.size() <= DRLGX_LO_TAB) {
-    for (double l : lo_val) {  // OccupancyMap LOGODDS2PROB + VirtualMap::updateProbability (num_samples identical maps)
-      const double pv1 = l2p(l);
-      double acc = 0.0;
-      for (int s2 = 0; s2 < cfg->num_samples; ++s2) acc += pv1 / cfg->num_samples;
-      lo_pv.push_back(acc);
-    }
-    S.lo_ntab = (int)lo_val.size();
-    if (S.lo_ntab <= 16)
-      for (int i = 0; i < S.lo_ntab; ++i) {
-        S.lo_tocc |= (unsigned long long)(lo_tr[4 * i] & 15) << (4 * i);
-        S.lo_tfree |= (unsigned long long)(lo_tr[4 * i + 1] & 15) << (4 * i);
-        S.lo_tflag |= (unsigned int)(lo_tr[4 * i + 2] & 3) << (2 * i);
-      }
-  } else {
-    S.lo_ntab = 0;
-    lo_pv.assign(1, 0.5);
-    lo_tr.assign(4, 0);
+  // The kernels walk the packed tables and have no other form of the ladder.  The log-odds constants are not configuration
+  // (set_map_constants fixes them), and with them the closure always ends on the same six states - 0, 0.7211, -0.8473, -1.6946,
+  // -2.5419, -2.9444; num_samples only changes lo_pv - so this cannot happen unless those constants change.
+  if (!closed || lo_val.size() > DRLGX_LO_TAB) {
+    e->last_error = "occupancy ladder does not close within 16 states";
+    return DRLGX_E_INVALID;
   }
+  for (double l : lo_val) {  // OccupancyMap LOGODDS2PROB + VirtualMap::updateProbability (num_samples identical maps)
+    const double pv1 = l2p(l);
+    double acc = 0.0;
+    for (int s2 = 0; s2 < cfg->num_samples; ++s2) acc += pv1 / cfg->num_samples;
+    lo_pv.push_back(acc);
+  }
+  S.lo_ntab = (int)lo_val.size();
+  for (int i = 0; i < S.lo_ntab; ++i) {
+    S.lo_tocc |= (unsigned long long)(lo_tr[3 * i] & 15) << (4 * i);
+    S.lo_tfree |= (unsigned long long)(lo_tr[3 * i + 1] & 15) << (4 * i);
+    S.lo_tflag |= (unsigned int)(lo_tr[3 * i + 2] & 3) << (2 * i);
+  }
+  return DRLGX_OK;
 }
 
 // sector-sweep table (OccupancyMap.cpp:86) and what follows from the sensor's sector and range: bbox_noop, fov_*, r2_*
@@ -492,8 +501,7 @@ static int build_engine(drlgx_engine *e) {
   if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
   TRY(set_map_constants(e));
   std::vector<double> lo_pv;
-  std::vector<uint8_t> lo_tr;
-  build_ladder(S, lo_pv, lo_tr);
+  TRY(build_ladder(e, lo_pv));
   const std::vector<double> sweep = set_sensor_constants(S);
   // libstdc++ iteration order of unordered_map<unsigned, ...> filled with keys 0..n-1 (Simulator2D.cpp:331-344)
   {
@@ -505,7 +513,6 @@ static int build_engine(drlgx_engine *e) {
   TRY(upload_table(e, &S.sweep_b, sweep));
   TRY(upload_table(e, &S.lm_order, e->lm_order));
   TRY(upload_table(e, &S.lo_pv, lo_pv));
-  TRY(upload_table(e, &S.lo_tr, lo_tr));
   TRY(alloc_fields(e));
   // SLAM workspace (not copied between instances; k_slam_host.hip: drlgx_slam_ws_doubles)
   S.slam_ws_stride = drlgx_slam_ws_doubles(S.P_max, S.L_max, S.M_max);

@@ -18,7 +18,7 @@
 //            algebra in registers); the 2x2 information goes to an LDS stage and the pose's bit is set (LDS atomics) in
 //            the cell's "updates me" mask and, for the occupancy model, in its "sees me" mask.
 //   phase C (cell-centric, one pass): covariance-intersection fusion over the set bits in trajectory order; occupancy
-//            ladder over the "sees me" bits as a host-built state machine (DrlgxState::lo_tr); probability, trace,
+//            ladder over the "sees me" bits as a host-built state machine (DrlgxState::lo_tocc ...); probability, trace,
 //            and the five utility sums.  Every cell is written once per belief update and never read back.
 //   phase R: block reduction of the sums (wave shuffles + LDS).
 // fp64 instruction count is what every phase pays, so (1) only (cell, pose) pairs that interact are visited, (2) divisions and
@@ -35,10 +35,7 @@
 
 namespace kmap {
 
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
-
-__device__ __forceinline__ double logodds2prob(double l) { return exp(l) / (1.0 + exp(l)); }
+// (kThreads, kWaves, kPairsPerPose and the LDS layout: map_carve.h)
 
 // BearingRangeSensorModel::check / checkWithoutMinRange on the bearing only (Simulator2D.cpp:100-111)
 __device__ __forceinline__ bool in_fov(const DrlgxState &S, const Pose &ps, const P2 &pt) {
@@ -175,12 +172,11 @@ __device__ __forceinline__ double wave_sum63(double v) {
 // handed (k_step): est_pose / pose_info of this instance already are in the LDS where this stage keeps them (sp, si) and
 // lm_lds holds the landmark estimates (LDS of the SLAM stage that this stage does not overwrite before it has read them):
 // nothing is fetched back from HBM
-// lo: entry threadIdx.x of the ladder tables (k_step fetches them before the SLAM stage: one HBM round trip less here)
+// lo: entry threadIdx.x of the ladder's value table (k_step fetches it before the SLAM stage: one HBM round trip less here)
 // P >= 0: the instance's counts and rejected-move flag as k_step knows them from the simulator wave (else read from S.cnt)
 struct LadderEntry {
   bool have;
   double pv;
-  uint32_t tr;
   int P, L, flag;
 };
 // kCompact: the LDS-lean form that lets TWO workgroups share a CU (the stand-alone kernel when there are more instances than
@@ -189,8 +185,93 @@ struct LadderEntry {
 // in their stage entry) and keeps the stage compact: entry k of the in-range pair list instead of a slot per (pose, window
 // cell), found through a 16-bit index table.  Same arithmetic in the same order: bit-equal results.
 constexpr int kMapCWaves = 4;  // waves per SIMD k_map_c is compiled for (__launch_bounds__: <= 128 VGPRs)
-constexpr int kPairsPerPose = 40;  // in-range cells per pose the compact stage has room for (the disc of radius max_range
-                                   // holds ~28 cell centres of the 7 x 7 window, never more than 32)
+constexpr int kInterior = 20;  // cells this far inside the map's border count as explorable (VirtualMap.cpp:47-59)
+
+// What the phases of map_body share: the LDS arrays (MapCarve), the instance's planes, its counts and the launch's sizes.
+struct MapCtx {
+  double *sp, *si, *sl, *stage;
+  unsigned long long *mask, *omask;
+  double *lpv;
+  int *bbox, *worg, *pskip, *lmc;
+  int *pcount;
+  unsigned short *plist, *sidx;
+  double *prob, *ixx, *ixy, *iyy, *vtr;  // planes of the instance
+  uint8_t *upd;
+  int inst, P, L, pc, chunk;
+
+  // the per-pose tables hold pc poses: the launch's pose bound (LaunchSel::pcap), not the engine's capacity
+  template <bool kCompact>
+  __device__ __forceinline__ void carve(const DrlgxState &S, double *smem) {
+    const MapCarve mc(pc, chunk, S.V, kCompact);
+    unsigned char *b = reinterpret_cast<unsigned char *>(smem);
+    sp = reinterpret_cast<double *>(b + mc.sp);
+    si = reinterpret_cast<double *>(b + mc.si);
+    sl = reinterpret_cast<double *>(b + mc.sl);
+    stage = reinterpret_cast<double *>(b + mc.stage);
+    mask = reinterpret_cast<unsigned long long *>(b + mc.mask);
+    omask = reinterpret_cast<unsigned long long *>(b + mc.omask);
+    lpv = reinterpret_cast<double *>(b + mc.lpv);
+    bbox = reinterpret_cast<int *>(b + mc.bbox);
+    worg = reinterpret_cast<int *>(b + mc.worg);
+    pskip = reinterpret_cast<int *>(b + mc.pskip);
+    lmc = reinterpret_cast<int *>(b + mc.lmc);
+    pcount = reinterpret_cast<int *>(b + mc.pcount);
+    plist = reinterpret_cast<unsigned short *>(b + mc.plist);
+    sidx = reinterpret_cast<unsigned short *>(b + mc.sidx);
+    const size_t V = S.V;
+    prob = S.vm_prob + (size_t)inst * V;
+    ixx = S.vm_info + ((size_t)inst * 3 + 0) * V;
+    ixy = S.vm_info + ((size_t)inst * 3 + 1) * V;
+    iyy = S.vm_info + ((size_t)inst * 3 + 2) * V;
+    upd = S.vm_upd + (size_t)inst * S.Vu;
+    vtr = S.vm_tr + (size_t)inst * V;
+  }
+};
+
+__device__ __forceinline__ P2 cell_centre(const drlgx_config &cfg, int row, int col) {
+  return P2{(col + 0.5) * cfg.resolution + cfg.map_min_x, (row + 0.5) * cfg.resolution + cfg.map_min_y};
+}
+
+// the five utility sums of a thread (Planner2D.cpp:321-366, VirtualMap.cpp:47-59)
+struct UtilSums {
+  double utr = 0, known = 0, expl = 0, udet = 0, uwtr = 0;
+  // one cell: its probability, the trace of its covariance (= information^-1, 2 x 2) and the reciprocal of the information's
+  // determinant (= the covariance's determinant)
+  __device__ __forceinline__ void add_cell(const drlgx_config &cfg, int row, int col, double pv, double tr, double rdet) {
+    utr += 1.0 * tr;
+    if (pv < cfg.occupancy_threshold) known += 1.0;
+    const double wgt = pv > 0.49 ? 1.0 : 0.0;
+    udet += wgt * rdet;
+    uwtr += wgt * tr;
+    if (pv < 0.49 || pv > 0.6) {  // explored, and in the interior box
+      const P2 x = cell_centre(cfg, row, col);
+      if (cfg.map_min_x + kInterior <= x.x && x.x <= cfg.map_max_x - kInterior && cfg.map_min_y + kInterior <= x.y && x.y <= cfg.map_max_y - kInterior)
+        expl += 1.0;
+    }
+  }
+};
+
+// Candidate pair e = 64 pl + 8 wr + wc of the chunk that starts at pose c0: pose pl of the chunk and slot (wr, wc) of the
+// 8 x 8 slot grid over its window (whatever the window width W <= 8 - no integer divisions).
+struct Pair {
+  int pl, p, wr, wc, row, col;
+  Pose ps;
+  P2 pt;  // the cell's centre
+};
+__device__ __forceinline__ Pair decode_pair(const DrlgxState &S, const MapCtx &c, int c0, int e) {
+  Pair q;
+  q.pl = e >> 6;
+  const int widx = e & 63;
+  q.p = c0 + q.pl;
+  q.wr = widx >> 3;
+  q.wc = widx & 7;
+  q.row = c.worg[2 * q.p] + q.wr;
+  q.col = c.worg[2 * q.p + 1] + q.wc;
+  q.ps = Pose{c.sp[4 * q.p], c.sp[4 * q.p + 1], c.sp[4 * q.p + 2], c.sp[4 * q.p + 3]};
+  q.pt = cell_centre(S.cfg, q.row, q.col);
+  return q;
+}
+
 // the planes of instance s -> d, by the whole workgroup (LaunchSel::vm_from: an instance whose planes this launch does not rebuild)
 __device__ __forceinline__ void copy_planes(const DrlgxState &S, int s, int d) {
   const size_t V = S.V, Vu4 = (size_t)S.Vu / 4;
@@ -203,536 +284,470 @@ __device__ __forceinline__ void copy_planes(const DrlgxState &S, int s, int d) {
   uint32_t *ud = reinterpret_cast<uint32_t *>(S.vm_upd + (size_t)d * S.Vu);
   for (size_t v = drlgx_tid(); v < Vu4; v += kThreads) ud[v] = us[v];
 }
-template <bool kCompact = false>
-__device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &sel, int rebuild, int chunk, bool handed = false,
-                                         const double *lm_lds = nullptr, LadderEntry lo = LadderEntry{false, 0.0, 0u, -1, 0, 0}) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6;
-  const int bi = drlgx_bid();
-  const int inst = sel.base + bi;
-  // (a lazy restore left the planes in the snapshot: every exit below that does not rebuild them copies them over)
-  const int owed_from = sel.vm_from >= 0 ? sel.vm_from + bi : -1;
-  if (!sel.on(bi) || !sel.map_on(bi)) {
-    if (owed_from >= 0) copy_planes(S, owed_from, inst);
-    return;
-  }
-  const int *cnt = S.cnt + (size_t)inst * DRLGX_CNT_STRIDE;
-  // a rejected move leaves the belief as it was: nothing to rebuild, unless this is the one rebuild of a rollout
-  if ((lo.P >= 0 ? lo.flag : cnt[C_FLAG]) && !sel.map_last_only) {
-    if (owed_from >= 0) copy_planes(S, owed_from, inst);
-    return;
-  }
-  const drlgx_config &cfg = S.cfg;
-  const int P = lo.P >= 0 ? lo.P : cnt[C_P], L = lo.P >= 0 ? lo.L : cnt[C_L];
-  const int V = S.V, cols = S.cols, rows = S.rows, W = S.win;
-  // LDS carve; the per-pose tables hold pc poses: the launch's pose bound (LaunchSel::pcap), not the engine's capacity
-  const int pc = sel.cap(S.P_max);
-  if (rebuild && P > pc) {  // (the host's bound was wrong: flag it, touch nothing)
-    if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
-    if (owed_from >= 0) copy_planes(S, owed_from, inst);
-    return;
-  }
-  double *sp = smem;                   // [pc][4]
-  double *si = sp + (size_t)pc * 4;    // [pc][6]
-  double *sl = si + (size_t)pc * 6;    // [pc][9] LLT factor of the pose information + reciprocals
-  double *stage = sl + (size_t)pc * 9;  // [chunk][64][3]; kCompact: [chunk * kPairsPerPose][3]
-  unsigned long long *mask = reinterpret_cast<unsigned long long *>(stage + (size_t)chunk * (kCompact ? kPairsPerPose : 64) * 3);  // [V]
-  unsigned long long *omask = kCompact ? mask : mask + V;  // [V] poses that see the cell (occupancy ladder); kCompact: the same mask
-  double *scratch = reinterpret_cast<double *>(omask + V);  // [kWaves]
-  int *bbox = reinterpret_cast<int *>(scratch + kWaves + DRLGX_LO_TAB);  // [pc][4] min_row max_row min_col max_col
-  int *worg = bbox + (size_t)pc * 4;                  // [pc][2] window origin row, col
-  int *pskip = worg + (size_t)pc * 2;                 // [pc]
-  int *lmc = pskip + pc;                              // [V] estimated landmarks per cell
-  uint8_t *ltr = reinterpret_cast<uint8_t *>(lmc + V);  // [DRLGX_LO_TAB][4] ladder transitions
-  double *lpv = scratch + kWaves;                      // [DRLGX_LO_TAB] ladder state -> cell probability
-  int *pcount = reinterpret_cast<int *>(ltr + 4 * DRLGX_LO_TAB);  // number of (pose, cell) pairs in range (phase A)
-  unsigned short *plist = reinterpret_cast<unsigned short *>(pcount + 1);  // [chunk * 64] their pair indices
-  unsigned short *sidx = plist + (size_t)chunk * 64;  // kCompact: [chunk][64] stage entry of (pose, window slot)
-  double *prob = S.vm_prob + (size_t)inst * V;
-  double *ixx = S.vm_info + ((size_t)inst * 3 + 0) * V, *ixy = S.vm_info + ((size_t)inst * 3 + 1) * V,
-         *iyy = S.vm_info + ((size_t)inst * 3 + 2) * V;
-  uint8_t *upd = S.vm_upd + (size_t)inst * S.Vu;
-  double *vtr = S.vm_tr + (size_t)inst * V;
+// a lazy restore left the planes of this instance in the snapshot: every path that does not rebuild them copies them over
+__device__ __forceinline__ void owed_planes(const DrlgxState &S, const LaunchSel &sel, int bi) {
+  if (sel.vm_from >= 0) copy_planes(S, sel.vm_from + bi, sel.base + bi);
+}
 
-  double utr = 0, known = 0, expl = 0, udet = 0, uwtr = 0;
-  DRLGX_PROF(S, 16);
-  if (rebuild) {
-    const double *ep = S.est_pose + (size_t)inst * S.P_max * 4;
-    const double *pin = S.pose_info + (size_t)inst * S.P_max * 6;
-    if (!handed) {
-      for (int e = tid; e < P * 4; e += kThreads) sp[e] = ep[e];
-      for (int e = tid; e < P * 6; e += kThreads) si[e] = pin[e];
+// the cell masks and the pair counter of a chunk; first: the landmark counts too
+template <bool kCompact>
+__device__ __forceinline__ void clear_masks(const DrlgxState &S, const MapCtx &c, bool first) {
+  const int tid = drlgx_tid();
+  for (int v = tid; v < S.V; v += kThreads) {
+    if (first) c.lmc[v] = 0;
+    c.mask[v] = 0ull;
+    if (!kCompact) c.omask[v] = 0ull;
+  }
+  if (tid == 0) *c.pcount = 0;
+}
+
+// ---- pose set-up: the pose tables, cleared masks and the ladder tables into LDS; landmark counts per cell; per pose its
+// window, the start of its bbox and the LLT factor of its information ----
+template <bool kCompact>
+__device__ __forceinline__ void pose_setup(const DrlgxState &S, const MapCtx &c, bool handed, const double *lm_lds, const LadderEntry &lo) {
+  const drlgx_config &cfg = S.cfg;
+  const int tid = drlgx_tid();
+  const int cols = S.cols, rows = S.rows, P = c.P;
+  const double *ep = S.est_pose + (size_t)c.inst * S.P_max * 4;
+  const double *pin = S.pose_info + (size_t)c.inst * S.P_max * 6;
+  if (!handed) {
+    for (int e = tid; e < P * 4; e += kThreads) c.sp[e] = ep[e];
+    for (int e = tid; e < P * 6; e += kThreads) c.si[e] = pin[e];
+  }
+  const double *el = (handed && lm_lds) ? lm_lds : S.est_lm + (size_t)c.inst * S.L_max * 2;
+  clear_masks<kCompact>(S, c, true);  // (the first chunk's masks too, while the loads above are in flight)
+  if (tid < S.lo_ntab) c.lpv[tid] = lo.have ? lo.pv : S.lo_pv[tid];  // (lo_ntab <= DRLGX_LO_TAB < kThreads)
+  __syncthreads();
+  DRLGX_PROF(S, 40);
+  // landmarks on the last threads, poses on the first ones: both in the same barrier interval
+  for (int j = kThreads - 1 - tid; j < c.L; j += kThreads) {
+    // OccupancyMap::update(map): landmark cell (OccupancyMap.cpp:127-131); every landmark in a cell is one occupied update
+    int r = (int)floor((el[2 * j + 1] - cfg.map_min_y) / cfg.resolution);
+    int cc = (int)floor((el[2 * j] - cfg.map_min_x) / cfg.resolution);
+    if (!(r >= rows || r < 0 || cc >= cols || cc < 0)) atomicAdd(&c.lmc[r * cols + cc], 1);
+  }
+  for (int p = tid; p < P; p += kThreads) {
+    const double x = c.sp[4 * p], y = c.sp[4 * p + 1];
+    int orow = (int)floor((y - cfg.map_min_y) / cfg.resolution);
+    int ocol = (int)floor((x - cfg.map_min_x) / cfg.resolution);
+    orow = min(max(0, orow), rows - 1);
+    ocol = min(max(0, ocol), cols - 1);
+    c.bbox[4 * p + 0] = orow; c.bbox[4 * p + 1] = orow; c.bbox[4 * p + 2] = ocol; c.bbox[4 * p + 3] = ocol;
+    // window of candidate cells for the information update: one cell wider than the tightest
+    // (open) interval so that no cell the reference's radius query accepts can fall outside
+    c.worg[2 * p + 0] = (int)floor((y - cfg.max_range - cfg.map_min_y) / cfg.resolution - 0.5);
+    c.worg[2 * p + 1] = (int)floor((x - cfg.max_range - cfg.map_min_x) / cfg.resolution - 0.5);
+    const double *pi = c.si + 6 * p;
+    c.pskip[p] = det3s(pi[0], pi[1], pi[2], pi[3], pi[4], pi[5]) < 1e-10 ? 1 : 0;  // VirtualMap.cpp:293-294
+    // state.information.llt(): factored once per pose; the push-through needs the off-diagonal entries and the
+    // reciprocals of the diagonal only (tolerance-only algebra: reciprocal square roots, no sqrt / division)
+    double *o = c.sl + 9 * p;
+    const double r00 = rsqrt_n1(pi[0]);
+    const double l10 = pi[1] * r00, l20 = pi[2] * r00;
+    const double r11 = rsqrt_n1(pi[3] - l10 * l10);
+    const double l21 = (pi[4] - l20 * l10) * r11;
+    const double r22 = rsqrt_n1(pi[5] - l20 * l20 - l21 * l21);
+    o[1] = l10; o[3] = l20; o[4] = l21;
+    o[6] = r00; o[7] = r11; o[8] = r22;
+  }
+  __syncthreads();
+}
+
+// ---- bbox of the 3-degree sector sweep (OccupancyMap.cpp:79-96): (pose, sample) pairs in parallel ----
+__device__ __forceinline__ void bbox_sweep(const DrlgxState &S, const MapCtx &c) {
+  const drlgx_config &cfg = S.cfg;
+  for (int e = drlgx_tid(); e < c.P * S.n_sweep; e += kThreads) {
+    const int p = e / S.n_sweep, k = e - p * S.n_sweep;
+    const Pose ps{c.sp[4 * p], c.sp[4 * p + 1], c.sp[4 * p + 2], c.sp[4 * p + 3]};
+    const double th0 = theta_of(ps), b = S.sweep_b[k];
+    const double x = ps.x + cfg.max_range * cos(th0 + b);
+    const double y = ps.y + cfg.max_range * sin(th0 + b);
+    int row = (int)floor((y - cfg.map_min_y) / cfg.resolution);
+    int col = (int)floor((x - cfg.map_min_x) / cfg.resolution);
+    row = min(max(0, row), S.rows - 1);
+    col = min(max(0, col), S.cols - 1);
+    atomicMin(&c.bbox[4 * p + 0], row);
+    atomicMax(&c.bbox[4 * p + 1], row);
+    atomicMin(&c.bbox[4 * p + 2], col);
+    atomicMax(&c.bbox[4 * p + 3], col);
+  }
+  __syncthreads();
+}
+
+// ---- pair list: the (pose, window cell) pairs of poses [c0, c0 + nc): a cheap pass keeps the ones in range and in the field
+// of view (~45 % of the window) in a compact list, so that the EKF push-through runs on full waves (a wave tests one pose's
+// window per round) ----
+// Returns 1: accepted, 0: rejected, 2: in range but the field of view needs the exact bearing (thin wedge around the blind
+// ray, or a narrow sensor).
+__device__ __forceinline__ int pair_test(const DrlgxState &S, const MapCtx &c, int c0, int e) {
+  const Pair q = decode_pair(S, c, c0, e);
+  const double dx = q.ps.x - q.pt.x, dy = q.ps.y - q.pt.y;
+  // KDTreeR2::queryRadiusNeighbors / OccupancyMap range test: sqrt(d2) < max_range, exactly
+  const bool inr = !c.pskip[q.p] && q.wr < S.win && q.wc < S.win && q.row >= 0 && q.row < S.rows && q.col >= 0 && q.col < S.cols &&
+                   dx * dx + dy * dy < S.r2_max_lt;
+  const P2 d = transform_to(q.ps, q.pt);
+  const bool sure = S.fov_fast && (d.x >= 0.0 || fabs(d.y) > S.fov_tan * fabs(d.x));  // provably inside
+  return inr ? (sure ? 1 : 2) : 0;
+}
+__device__ __forceinline__ bool pair_exact(const DrlgxState &S, const MapCtx &c, int c0, int e) {  // BearingRangeSensorModel::check on the bearing itself
+  const Pair q = decode_pair(S, c, c0, e);
+  const double bearing = bearing_of<false>(q.ps, q.pt, nullptr, nullptr);
+  return bearing < S.cfg.max_bearing && bearing > S.cfg.min_bearing;
+}
+__device__ __forceinline__ void pair_list(const DrlgxState &S, const MapCtx &c, int c0, int nc) {
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6;
+  int e0 = 0;
+  // four rounds at a time as straight-line code (the LDS loads of the four candidates overlap), one LDS atomic per
+  // wave and group
+  for (; e0 + 4 * kThreads <= nc * 64; e0 += 4 * kThreads) {
+    int t[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = pair_test(S, c, c0, e0 + r * kThreads + tid);
+    if (__ballot((t[0] | t[1] | t[2] | t[3]) & 2)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (t[r] == 2) t[r] = pair_exact(S, c, c0, e0 + r * kThreads + tid) ? 1 : 0;
     }
-    const double *el = (handed && lm_lds) ? lm_lds : S.est_lm + (size_t)inst * S.L_max * 2;
-    for (int v = tid; v < V; v += kThreads) {  // (the first chunk's masks too, while the loads above are in flight)
-      lmc[v] = 0;
-      mask[v] = 0ull;
-      if (!kCompact) omask[v] = 0ull;
+    unsigned long long bal[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bal[r] = __ballot(t[r] == 1);
+    const int n0 = __popcll(bal[0]), n1 = __popcll(bal[1]), n2 = __popcll(bal[2]), n3 = __popcll(bal[3]);
+    int base = 0;
+    if (lane == 0 && (n0 + n1 + n2 + n3)) base = atomicAdd(c.pcount, n0 + n1 + n2 + n3);
+    base = __builtin_amdgcn_readfirstlane(base);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int off[4] = {0, n0, n0 + n1, n0 + n1 + n2};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (t[r] == 1) c.plist[base + off[r] + __popcll(bal[r] & below)] = (unsigned short)(e0 + r * kThreads + tid);
+  }
+  for (; e0 < nc * 64; e0 += kThreads) {  // remaining rounds (waves beyond the last pose's window skip)
+    const int e = e0 + tid;
+    if ((e0 >> 6) + wave >= nc) continue;
+    int t = pair_test(S, c, c0, e);
+    if (t == 2) t = pair_exact(S, c, c0, e) ? 1 : 0;
+    const unsigned long long bal = __ballot(t == 1);
+    int base = 0;
+    if (lane == 0 && bal) base = atomicAdd(c.pcount, __popcll(bal));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (t == 1) c.plist[base + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)e;
+  }
+  __syncthreads();
+}
+
+// ---- phase A: EKF push-through of the pose covariance to every listed cell (predict_cell); the 2x2 information goes to the
+// LDS stage and the pose's bit is set in the cell's 64-bit mask (LDS atomic) ----
+template <bool kCompact>
+__device__ __forceinline__ void push_through(const DrlgxState &S, const MapCtx &c, int c0, int npairs) {
+  const bool use_bbox = !S.bbox_noop;
+  const int cols = S.cols;
+  for (int k = drlgx_tid(); k < npairs; k += kThreads) {
+    const Pair q = decode_pair(S, c, c0, c.plist[k]);
+    const int p = q.p, row = q.row, col = q.col;
+    const bool in_bbox = !use_bbox || !(row < c.bbox[4 * p] || row > c.bbox[4 * p + 1] || col < c.bbox[4 * p + 2] || col > c.bbox[4 * p + 3]);
+    if (in_bbox) atomicOr(&c.omask[row * cols + col], 1ull << q.pl);  // OccupancyMap::update visits this cell
+    double a, b, d;
+    const bool upd_ok = predict_cell<false>(S, q.ps, c.sl + 9 * p, q.pt, a, b, d);
+    if constexpr (kCompact) {
+      // entry k of the pair list; the cell pass finds it through sidx[(pose, window slot)].  A pair that is seen but does not
+      // update (inside min_range) keeps its bit - the one mask is the sees-me mask - and carries a negative sentinel
+      double *o = c.stage + (size_t)k * 3;
+      o[0] = upd_ok ? a : -1.0; o[1] = b; o[2] = d;
+      c.sidx[q.pl * 64 + (row & 7) * 8 + (col & 7)] = (unsigned short)k;
+    } else if (upd_ok) {
+      // stage slot of (pose, cell): the window spans at most 8 consecutive rows / columns, so (row mod 8, col mod 8)
+      // is unique within it - the cell pass finds the entry without the window origin
+      double *o = c.stage + ((size_t)q.pl * 64 + (row & 7) * 8 + (col & 7)) * 3;
+      o[0] = a; o[1] = b; o[2] = d;
+      atomicOr(&c.mask[row * cols + col], 1ull << q.pl);
     }
-    if (tid == 0) *pcount = 0;
-    if (lo.have) {
-      if (tid < S.lo_ntab) {
-        lpv[tid] = lo.pv;
-        reinterpret_cast<uint32_t *>(ltr)[tid] = lo.tr;
+  }
+  __syncthreads();
+}
+
+// the occupancy ladder's transition table in registers (<= 16 states: 4 bits per next state, 2 per flag, packed on the
+// host - DrlgxState::lo_tocc): a cell's walk over its sees-me bits is pure ALU, no dependent LDS load per pose
+struct LadderFsm {
+  unsigned long long t_occ, t_free;
+  unsigned int t_flag;
+};
+
+// ---- phase C (cell-centric) visits exactly the poses that update a cell, in trajectory order (ascending bits), for the
+// covariance-intersection fusion - instead of testing every (cell, pose) pair.  The last chunk's C pass also runs the
+// occupancy ladder (branch-free over the poses), writes the cell and accumulates the reductions: every cell is read and
+// written once per belief update. ----
+template <bool kCompact>
+__device__ __forceinline__ void cell_pass(const DrlgxState &S, const MapCtx &c, int c0, bool last, const LadderFsm &fsm_t, UtilSums &sums) {
+  const drlgx_config &cfg = S.cfg;
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6;
+  const int cols = S.cols, rows = S.rows;
+  const double i0 = S.vm_i0;
+  const bool wprof = S.prof && blockIdx.x == S.prof_block && lane == 0 && c0 == 0;
+  long long ci_clk = 0;
+  // cell pass: one 8 x 8 tile of cells per wave and round (lane = 8 (row mod 8) + (col mod 8)).  Cells of a tile
+  // are seen by nearly the same poses, so the lanes' covariance-intersection chains have similar lengths and tiles
+  // away from the trajectory skip the loop altogether (row-major strips of 64 cells cross the whole map instead).
+  // (Tiles on the trajectory cost several times the others and the round-robin deal leaves some waves idle from 2.2 us
+  // while others work until 6.5 us; a tile queue - with the utility terms summed per tile, or parked per cell and summed
+  // afterwards, to keep the sums reproducible - and a deal by ranked cost both evened the waves out and both made the
+  // kernel slower: ranking costs more than it saves, and with the queue the barrier after the pass completed 1.9 us
+  // after the last wave instead of 0.2 us.  Round 6 measured two more forms, both slower: two tiles per wave with their chains
+  // interleaved in one loop (11.9 against 6.9 us: the waves are bound by fp64 issue on their SIMD, not by the chain's latency),
+  // and the cells sorted by chain length - ballots and a prefix, deterministic - with 64 consecutive ones per wave (9.2 us: the
+  // two classification passes and the prefix cost 4.9 us, and the longest chain alone, ~30 fusions of ~140 ns, lasts 4.2 us -
+  // that chain is the floor of this pass; 97 against 89 us at 2 048 instances).)
+  const int tiles_c = (cols + 7) >> 3, ntiles = ((rows + 7) >> 3) * tiles_c;
+  // the untouched cell (prior information I / sigma0^2, ladder state 0), as the general path computes it
+  const double pv_prior = c.lpv[0];
+  const double rdet_prior = rcp_n1(i0 * i0 - 0.0 * 0.0), tr_prior = (i0 + i0) * rdet_prior;
+  // the three per-cell LDS words of a tile (update mask, sees-me mask, landmark count) are fetched one tile ahead: each
+  // is the head of a dependent chain and a wave has nothing else to cover the LDS latency with
+  auto cell_of = [&](int t, int &row, int &col) -> int {
+    const int trow = t / tiles_c, tcol = t - trow * tiles_c;
+    row = 8 * trow + (lane >> 3);
+    col = 8 * tcol + (lane & 7);
+    return (row < rows && col < cols) ? row * cols + col : -1;
+  };
+  int nrow = 0, ncol = 0;
+  int nv = wave < ntiles ? cell_of(wave, nrow, ncol) : -1;
+  unsigned long long nm = nv >= 0 ? c.mask[nv] : 0ull, nom = (!kCompact && nv >= 0) ? c.omask[nv] : 0ull;
+  int nlmc = nv >= 0 ? c.lmc[nv] : 0;
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int row = nrow, col = ncol;
+    const bool ok = nv >= 0;
+    const int v = ok ? nv : 0;
+    unsigned long long m = nm;
+    const unsigned long long om_cell = kCompact ? nm : nom;
+    const int lmc_cell = nlmc;
+    if (t + kWaves < ntiles) {
+      nv = cell_of(t + kWaves, nrow, ncol);
+      nm = nv >= 0 ? c.mask[nv] : 0ull;
+      if (!kCompact) nom = nv >= 0 ? c.omask[nv] : 0ull;
+      nlmc = nv >= 0 ? c.lmc[nv] : 0;
+    }
+    // a middle chunk of poses (trajectories beyond 128 poses) that neither updates nor sees any cell of the tile leaves
+    // it as it is: no read-modify-write of its planes
+    if (c0 > 0 && !last && __ballot((m | om_cell) != 0ull) == 0ull) continue;
+    // a tile that no pose sees and no landmark lies in (most of the map: ~15 of 25 tiles at the bench state), whole
+    // trajectory in one chunk: every cell is the untouched prior - the same values the general path below computes for
+    // such a cell (same expressions, same order of the utility sums), without its ladder walk and per-cell algebra
+    if (c0 == 0 && last && __ballot((m | om_cell) != 0ull || lmc_cell != 0) == 0ull) {
+      if (ok) {
+        c.ixx[v] = i0; c.ixy[v] = 0.0; c.iyy[v] = i0;
+        c.upd[v] = (uint8_t)0;
+        c.prob[v] = pv_prior;
+        c.vtr[v] = tr_prior;
+        sums.add_cell(cfg, row, col, pv_prior, tr_prior, rdet_prior);
+      }
+      continue;
+    }
+    double axx = i0, axy = 0.0, ayy = i0;
+    int u = 0;
+    if (c0 > 0) {
+      axx = c.ixx[v]; axy = c.ixy[v]; ayy = c.iyy[v];
+      u = c.upd[v];
+    }
+    const double *nx = c.stage + lane * 3;  // + 192 * (pose within the chunk): the slot is the lane
+    const long long tc0 = wprof ? wall_clock64() : 0;
+    if constexpr (kCompact) {
+      // the same walk over the set bits in trajectory order; an entry is found through the index table and fetched one
+      // step ahead of its use, an entry with the sentinel is a pose that sees the cell without updating it
+      auto fetch = [&](unsigned long long &mm, double &xx, double &xy, double &yy) {
+        const int pl = __ffsll((long long)mm) - 1;
+        mm &= mm - 1;
+        const double *o = c.stage + (size_t)c.sidx[pl * 64 + lane] * 3;
+        xx = o[0]; xy = o[1]; yy = o[2];
+      };
+      if (m) {
+        double nxx, nxy, nyy;
+        fetch(m, nxx, nxy, nyy);
+        while (true) {
+          const double bxx = nxx, bxy = nxy, byy = nyy;
+          const bool more = m != 0ull;
+          if (more) fetch(m, nxx, nxy, nyy);
+          if (bxx >= 0.0) {
+            if (!u) {  // the first update of an untouched cell replaces the prior (VirtualMap.cpp:300-304)
+              axx = bxx; axy = bxy; ayy = byy;
+              u = 1;
+            } else {
+              ci_fuse(axx, axy, ayy, bxx, bxy, byy);
+            }
+          }
+          if (!more) break;
+        }
       }
     } else {
-      for (int t = tid; t < S.lo_ntab; t += kThreads) {
-        lpv[t] = S.lo_pv[t];
-        reinterpret_cast<uint32_t *>(ltr)[t] = reinterpret_cast<const uint32_t *>(S.lo_tr)[t];
-      }
+    if (m && !u) {  // the first update of an untouched cell replaces the prior (VirtualMap.cpp:300-304)
+      const double *o = nx + (__ffsll((long long)m) - 1) * 192;
+      axx = o[0]; axy = o[1]; ayy = o[2];
+      u = 1;
+      m &= m - 1;
     }
-    __syncthreads();
-    DRLGX_PROF(S, 40);
-    // landmarks on the last threads, poses on the first ones: both in the same barrier interval
-    for (int j = kThreads - 1 - tid; j < L; j += kThreads) {
-      // OccupancyMap::update(map): landmark cell (OccupancyMap.cpp:127-131); every landmark in a cell is one occupied update
-      int r = (int)floor((el[2 * j + 1] - cfg.map_min_y) / cfg.resolution);
-      int c = (int)floor((el[2 * j] - cfg.map_min_x) / cfg.resolution);
-      if (!(r >= rows || r < 0 || c >= cols || c < 0)) atomicAdd(&lmc[r * cols + c], 1);
-    }
-    for (int p = tid; p < P; p += kThreads) {
-      const double x = sp[4 * p], y = sp[4 * p + 1];
-      int orow = (int)floor((y - cfg.map_min_y) / cfg.resolution);
-      int ocol = (int)floor((x - cfg.map_min_x) / cfg.resolution);
-      orow = min(max(0, orow), rows - 1);
-      ocol = min(max(0, ocol), cols - 1);
-      bbox[4 * p + 0] = orow; bbox[4 * p + 1] = orow; bbox[4 * p + 2] = ocol; bbox[4 * p + 3] = ocol;
-      // window of candidate cells for the information update: one cell wider than the tightest
-      // (open) interval so that no cell the reference's radius query accepts can fall outside
-      worg[2 * p + 0] = (int)floor((y - cfg.max_range - cfg.map_min_y) / cfg.resolution - 0.5);
-      worg[2 * p + 1] = (int)floor((x - cfg.max_range - cfg.map_min_x) / cfg.resolution - 0.5);
-      const double *pi = si + 6 * p;
-      pskip[p] = det3s(pi[0], pi[1], pi[2], pi[3], pi[4], pi[5]) < 1e-10 ? 1 : 0;  // VirtualMap.cpp:293-294
-      // state.information.llt(): factored once per pose; the push-through needs the off-diagonal entries and the
-      // reciprocals of the diagonal only (tolerance-only algebra: reciprocal square roots, no sqrt / division)
-      double *o = sl + 9 * p;
-      const double r00 = rsqrt_n1(pi[0]);
-      const double l10 = pi[1] * r00, l20 = pi[2] * r00;
-      const double r11 = rsqrt_n1(pi[3] - l10 * l10);
-      const double l21 = (pi[4] - l20 * l10) * r11;
-      const double r22 = rsqrt_n1(pi[5] - l20 * l20 - l21 * l21);
-      o[1] = l10; o[3] = l20; o[4] = l21;
-      o[6] = r00; o[7] = r11; o[8] = r22;
-    }
-    __syncthreads();
-    DRLGX_PROF(S, 41);
-    const bool use_bbox = !S.bbox_noop;
-    if (use_bbox) {
-      // bbox of the 3-degree sector sweep (OccupancyMap.cpp:79-96): (pose, sample) pairs in parallel
-      for (int e = tid; e < P * S.n_sweep; e += kThreads) {
-        const int p = e / S.n_sweep, k = e - p * S.n_sweep;
-        const Pose ps{sp[4 * p], sp[4 * p + 1], sp[4 * p + 2], sp[4 * p + 3]};
-        const double th0 = theta_of(ps), b = S.sweep_b[k];
-        const double x = ps.x + cfg.max_range * cos(th0 + b);
-        const double y = ps.y + cfg.max_range * sin(th0 + b);
-        int row = (int)floor((y - cfg.map_min_y) / cfg.resolution);
-        int col = (int)floor((x - cfg.map_min_x) / cfg.resolution);
-        row = min(max(0, row), rows - 1);
-        col = min(max(0, col), cols - 1);
-        atomicMin(&bbox[4 * p + 0], row);
-        atomicMax(&bbox[4 * p + 1], row);
-        atomicMin(&bbox[4 * p + 2], col);
-        atomicMax(&bbox[4 * p + 3], col);
-      }
-      __syncthreads();
-    }
-    DRLGX_PROF(S, 17);
-    // ---- phases A / C, `chunk` poses at a time (one chunk unless P > 64 or the stage does not fit the LDS) ----
-    // A (pose-centric): one wave per pose, one lane per cell of the W x W window around the pose: EKF push-through of the
-    //    pose covariance to the cell (predict_cell); the 2x2 information goes to the LDS stage and the pose's bit is set in
-    //    the cell's 64-bit mask (LDS atomic), so that
-    // C (cell-centric) visits exactly the poses that update a cell, in trajectory order (ascending bits), for the
-    //    covariance-intersection fusion - instead of testing every (cell, pose) pair.  The last chunk's C pass also runs
-    //    the occupancy ladder (branch-free over the poses), writes the cell and accumulates the reductions: every cell is
-    //    read and written once per belief update.
-    const double i0 = S.vm_i0;
-    const int extg = 20;
-    // the ladder's transition table packed into registers when it has <= 16 states (4 bits per next state, 2 per flag,
-    // packed on the host): a cell's walk over its sees-me bits is then pure ALU instead of one dependent LDS byte load
-    // per pose
-    const bool fsm_reg = S.lo_ntab > 0 && S.lo_ntab <= 16;
-    const unsigned long long t_occ = S.lo_tocc, t_free = S.lo_tfree;
-    const unsigned int t_flag = S.lo_tflag;
-    for (int c0 = 0; c0 < P; c0 += chunk) {
-      const int nc = min(chunk, P - c0);
-      const bool last = c0 + nc >= P;
-      if (c0 > 0) {  // (the first chunk's masks were cleared while the pose tables were loading)
-        for (int v = tid; v < V; v += kThreads) {
-          mask[v] = 0ull;
-          if (!kCompact) omask[v] = 0ull;
+    if (m) {
+      // every further update is fused; the next entry is loaded before the current one is fused, so that the LDS
+      // latency stays off the dependent chain
+      const double *o = nx + (__ffsll((long long)m) - 1) * 192;
+      double nxx = o[0], nxy = o[1], nyy = o[2];
+      m &= m - 1;
+      while (true) {
+        const double bxx = nxx, bxy = nxy, byy = nyy;
+        const bool more = m != 0ull;
+        if (more) {
+          const double *o2 = nx + (__ffsll((long long)m) - 1) * 192;
+          nxx = o2[0]; nxy = o2[1]; nyy = o2[2];
+          m &= m - 1;
         }
-        if (tid == 0) *pcount = 0;
-        __syncthreads();
+        ci_fuse(axx, axy, ayy, bxx, bxy, byy);
+        if (!more) break;
       }
-      if (c0 == 0) DRLGX_PROF(S, 42);
-      // (pose, window cell) pairs: a cheap pass keeps the ones in range and in the field of view (~45 % of the window)
-      // in a compact list, so that the EKF push-through below runs on full waves
-      // (candidate e = 64 pl + 8 wr + wc: an 8 x 8 slot grid per pose whatever the window width W <= 8 - no integer
-      // divisions; a wave tests one pose's window per round).  Returns 1: accepted, 0: rejected, 2: in range but the
-      // field of view needs the exact bearing (thin wedge around the blind ray, or a narrow sensor).
-      auto pair_test = [&](int e) -> int {
-        const int pl = e >> 6, widx = e & 63;
-        const int p = c0 + pl;
-        const int wr = widx >> 3, wc = widx & 7;
-        const int row = worg[2 * p] + wr, col = worg[2 * p + 1] + wc;
-        const Pose ps{sp[4 * p], sp[4 * p + 1], sp[4 * p + 2], sp[4 * p + 3]};
-        const P2 pt{(col + 0.5) * cfg.resolution + cfg.map_min_x, (row + 0.5) * cfg.resolution + cfg.map_min_y};
-        const double dx = ps.x - pt.x, dy = ps.y - pt.y;
-        // KDTreeR2::queryRadiusNeighbors / OccupancyMap range test: sqrt(d2) < max_range, exactly
-        const bool inr = !pskip[p] && wr < W && wc < W && row >= 0 && row < rows && col >= 0 && col < cols &&
-                         dx * dx + dy * dy < S.r2_max_lt;
-        const P2 d = transform_to(ps, pt);
-        const bool sure = S.fov_fast && (d.x >= 0.0 || fabs(d.y) > S.fov_tan * fabs(d.x));  // provably inside
-        return inr ? (sure ? 1 : 2) : 0;
-      };
-      auto pair_exact = [&](int e) -> bool {  // BearingRangeSensorModel::check on the bearing itself
-        const int pl = e >> 6, widx = e & 63;
-        const int p = c0 + pl;
-        const int row = worg[2 * p] + (widx >> 3), col = worg[2 * p + 1] + (widx & 7);
-        const Pose ps{sp[4 * p], sp[4 * p + 1], sp[4 * p + 2], sp[4 * p + 3]};
-        const P2 pt{(col + 0.5) * cfg.resolution + cfg.map_min_x, (row + 0.5) * cfg.resolution + cfg.map_min_y};
-        const double bearing = bearing_of<false>(ps, pt, nullptr, nullptr);
-        return bearing < cfg.max_bearing && bearing > cfg.min_bearing;
-      };
-      int e0 = 0;
-      // four rounds at a time as straight-line code (the LDS loads of the four candidates overlap), one LDS atomic per
-      // wave and group
-      for (; e0 + 4 * kThreads <= nc * 64; e0 += 4 * kThreads) {
-        int t[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t[r] = pair_test(e0 + r * kThreads + tid);
-        if (__ballot((t[0] | t[1] | t[2] | t[3]) & 2)) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (t[r] == 2) t[r] = pair_exact(e0 + r * kThreads + tid) ? 1 : 0;
-        }
-        unsigned long long bal[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bal[r] = __ballot(t[r] == 1);
-        const int n0 = __popcll(bal[0]), n1 = __popcll(bal[1]), n2 = __popcll(bal[2]), n3 = __popcll(bal[3]);
-        int base = 0;
-        if (lane == 0 && (n0 + n1 + n2 + n3)) base = atomicAdd(pcount, n0 + n1 + n2 + n3);
-        base = __builtin_amdgcn_readfirstlane(base);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const int off[4] = {0, n0, n0 + n1, n0 + n1 + n2};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (t[r] == 1) plist[base + off[r] + __popcll(bal[r] & below)] = (unsigned short)(e0 + r * kThreads + tid);
-      }
-      for (; e0 < nc * 64; e0 += kThreads) {  // remaining rounds (waves beyond the last pose's window skip)
-        const int e = e0 + tid;
-        if ((e0 >> 6) + wave >= nc) continue;
-        int t = pair_test(e);
-        if (t == 2) t = pair_exact(e) ? 1 : 0;
-        const unsigned long long bal = __ballot(t == 1);
-        int base = 0;
-        if (lane == 0 && bal) base = atomicAdd(pcount, __popcll(bal));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (t == 1) plist[base + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)e;
-      }
-      __syncthreads();
-      if (c0 == 0) DRLGX_PROF(S, 43);
-      const int npairs = *pcount;
-      if (kCompact && npairs > nc * kPairsPerPose) {  // (cannot happen for a disc-shaped footprint: flag it, leave the map alone)
-        if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
-        return;
-      }
-      for (int k = tid; k < npairs; k += kThreads) {
-        const int e = plist[k];
-        const int pl = e >> 6, widx = e & 63;
-        const int p = c0 + pl;
-        const int wr = widx >> 3, wc = widx & 7;
-        const int row = worg[2 * p] + wr, col = worg[2 * p + 1] + wc;
-        const Pose ps{sp[4 * p], sp[4 * p + 1], sp[4 * p + 2], sp[4 * p + 3]};
-        const P2 pt{(col + 0.5) * cfg.resolution + cfg.map_min_x, (row + 0.5) * cfg.resolution + cfg.map_min_y};
-        const bool in_bbox = !use_bbox || !(row < bbox[4 * p] || row > bbox[4 * p + 1] || col < bbox[4 * p + 2] || col > bbox[4 * p + 3]);
-        if (in_bbox) atomicOr(&omask[row * cols + col], 1ull << pl);  // OccupancyMap::update visits this cell
-        double a, b, d;
-        const bool upd_ok = predict_cell<false>(S, ps, sl + 9 * p, pt, a, b, d);
-        if constexpr (kCompact) {
-          // entry k of the pair list; the cell pass finds it through sidx[(pose, window slot)].  A pair that is seen but does not
-          // update (inside min_range) keeps its bit - the one mask is the sees-me mask - and carries a negative sentinel
-          double *o = stage + (size_t)k * 3;
-          o[0] = upd_ok ? a : -1.0; o[1] = b; o[2] = d;
-          sidx[pl * 64 + (row & 7) * 8 + (col & 7)] = (unsigned short)k;
-        } else if (upd_ok) {
-          // stage slot of (pose, cell): the window spans at most 8 consecutive rows / columns, so (row mod 8, col mod 8)
-          // is unique within it - the cell pass finds the entry without the window origin
-          double *o = stage + ((size_t)pl * 64 + (row & 7) * 8 + (col & 7)) * 3;
-          o[0] = a; o[1] = b; o[2] = d;
-          atomicOr(&mask[row * cols + col], 1ull << pl);
-        }
-      }
-      __syncthreads();
-      if (c0 == 0) DRLGX_PROF(S, 21);
-      const bool wprof = S.prof && blockIdx.x == S.prof_block && lane == 0 && c0 == 0;
-      long long ci_clk = 0;
-      // cell pass: one 8 x 8 tile of cells per wave and round (lane = 8 (row mod 8) + (col mod 8)).  Cells of a tile
-      // are seen by nearly the same poses, so the lanes' covariance-intersection chains have similar lengths and tiles
-      // away from the trajectory skip the loop altogether (row-major strips of 64 cells cross the whole map instead).
-      // (Tiles on the trajectory cost several times the others and the round-robin deal leaves some waves idle from 2.2 us
-      // while others work until 6.5 us; a tile queue - with the utility terms summed per tile, or parked per cell and summed
-      // afterwards, to keep the sums reproducible - and a deal by ranked cost both evened the waves out and both made the
-      // kernel slower: ranking costs more than it saves, and with the queue the barrier after the pass completed 1.9 us
-      // after the last wave instead of 0.2 us.  Round 6 measured two more forms, both slower: two tiles per wave with their chains
-      // interleaved in one loop (11.9 against 6.9 us: the waves are bound by fp64 issue on their SIMD, not by the chain's latency),
-      // and the cells sorted by chain length - ballots and a prefix, deterministic - with 64 consecutive ones per wave (9.2 us: the
-      // two classification passes and the prefix cost 4.9 us, and the longest chain alone, ~30 fusions of ~140 ns, lasts 4.2 us -
-      // that chain is the floor of this pass; 97 against 89 us at 2 048 instances).)
-      const int tiles_c = (cols + 7) >> 3, ntiles = ((rows + 7) >> 3) * tiles_c;
-      // the untouched cell (prior information I / sigma0^2, ladder state 0), as the general path computes it
-      double pv_prior = 0.0;
-      if (S.lo_ntab > 0) {
-        pv_prior = lpv[0];
+    }
+    }
+    if (wprof) ci_clk += wall_clock64() - tc0;
+    if (ok) {
+      c.ixx[v] = axx; c.ixy[v] = axy; c.iyy[v] = ayy;
+      c.upd[v] = (uint8_t)u;
+      // occupancy ladder (OccupancyMap.cpp:64-138) as its state machine: the landmarks of the cell (each one occupied
+      // update), then the poses that see it in trajectory order (ascending mask bits); between chunks the state is parked
+      // in prob[]
+      int st = 0;  // LOGODDS_UNKNOWN
+      if (c0 == 0) {
+        for (int n = lmc_cell; n > 0; --n) st = (int)((fsm_t.t_occ >> (4 * st)) & 15);
       } else {
-        const double pv1 = logodds2prob(0.0);
-        for (int s2 = 0; s2 < cfg.num_samples; ++s2) pv_prior += pv1 / cfg.num_samples;
+        st = (int)c.prob[v];
       }
-      const double rdet_prior = rcp_n1(i0 * i0 - 0.0 * 0.0), tr_prior = (i0 + i0) * rdet_prior;
-      const double wgt_prior = pv_prior > 0.49 ? 1.0 : 0.0;
-      const bool expl_prior = pv_prior < 0.49 || pv_prior > 0.6;
-      // the three per-cell LDS words of a tile (update mask, sees-me mask, landmark count) are fetched one tile ahead: each
-      // is the head of a dependent chain and a wave has nothing else to cover the LDS latency with
-      auto cell_of = [&](int t, int &row, int &col) -> int {
-        const int trow = t / tiles_c, tcol = t - trow * tiles_c;
-        row = 8 * trow + (lane >> 3);
-        col = 8 * tcol + (lane & 7);
-        return (row < rows && col < cols) ? row * cols + col : -1;
-      };
-      int nrow = 0, ncol = 0;
-      int nv = wave < ntiles ? cell_of(wave, nrow, ncol) : -1;
-      unsigned long long nm = nv >= 0 ? mask[nv] : 0ull, nom = (!kCompact && nv >= 0) ? omask[nv] : 0ull;
-      int nlmc = nv >= 0 ? lmc[nv] : 0;
-      for (int t = wave; t < ntiles; t += kWaves) {
-        const int row = nrow, col = ncol;
-        const bool ok = nv >= 0;
-        const int v = ok ? nv : 0;
-        unsigned long long m = nm;
-        const unsigned long long om_cell = kCompact ? nm : nom;
-        const int lmc_cell = nlmc;
-        if (t + kWaves < ntiles) {
-          nv = cell_of(t + kWaves, nrow, ncol);
-          nm = nv >= 0 ? mask[nv] : 0ull;
-          if (!kCompact) nom = nv >= 0 ? omask[nv] : 0ull;
-          nlmc = nv >= 0 ? lmc[nv] : 0;
-        }
-        // a middle chunk of poses (trajectories beyond 128 poses) that neither updates nor sees any cell of the tile leaves
-        // it as it is: no read-modify-write of its planes
-        if (c0 > 0 && !last && __ballot((m | om_cell) != 0ull) == 0ull) continue;
-        // a tile that no pose sees and no landmark lies in (most of the map: ~15 of 25 tiles at the bench state), whole
-        // trajectory in one chunk: every cell is the untouched prior - the same values the general path below computes for
-        // such a cell (same expressions, same order of the utility sums), without its ladder walk and per-cell algebra
-        if (c0 == 0 && last && __ballot((m | om_cell) != 0ull || lmc_cell != 0) == 0ull) {
-          if (ok) {
-            ixx[v] = i0; ixy[v] = 0.0; iyy[v] = i0;
-            upd[v] = (uint8_t)0;
-            prob[v] = pv_prior;
-            vtr[v] = tr_prior;
-            utr += 1.0 * tr_prior;
-            if (pv_prior < cfg.occupancy_threshold) known += 1.0;
-            udet += wgt_prior * rdet_prior;
-            uwtr += wgt_prior * tr_prior;
-            if (expl_prior) {
-              const double x = (col + 0.5) * cfg.resolution + cfg.map_min_x, y = (row + 0.5) * cfg.resolution + cfg.map_min_y;
-              if (cfg.map_min_x + extg <= x && x <= cfg.map_max_x - extg && cfg.map_min_y + extg <= y && y <= cfg.map_max_y - extg) expl += 1.0;
-            }
-          }
-          continue;
-        }
-        double axx = i0, axy = 0.0, ayy = i0;
-        int u = 0;
-        if (c0 > 0) {
-          axx = ixx[v]; axy = ixy[v]; ayy = iyy[v];
-          u = upd[v];
-        }
-        const double *nx = stage + lane * 3;  // + 192 * (pose within the chunk): the slot is the lane
-        const long long tc0 = wprof ? wall_clock64() : 0;
-        if constexpr (kCompact) {
-          // the same walk over the set bits in trajectory order; an entry is found through the index table and fetched one
-          // step ahead of its use, an entry with the sentinel is a pose that sees the cell without updating it
-          auto fetch = [&](unsigned long long &mm, double &xx, double &xy, double &yy) {
-            const int pl = __ffsll((long long)mm) - 1;
-            mm &= mm - 1;
-            const double *o = stage + (size_t)sidx[pl * 64 + lane] * 3;
-            xx = o[0]; xy = o[1]; yy = o[2];
-          };
-          if (m) {
-            double nxx, nxy, nyy;
-            fetch(m, nxx, nxy, nyy);
-            while (true) {
-              const double bxx = nxx, bxy = nxy, byy = nyy;
-              const bool more = m != 0ull;
-              if (more) fetch(m, nxx, nxy, nyy);
-              if (bxx >= 0.0) {
-                if (!u) {  // the first update of an untouched cell replaces the prior (VirtualMap.cpp:300-304)
-                  axx = bxx; axy = bxy; ayy = byy;
-                  u = 1;
-                } else {
-                  ci_fuse(axx, axy, ayy, bxx, bxy, byy);
-                }
-              }
-              if (!more) break;
-            }
-          }
-        } else {
-        if (m && !u) {  // the first update of an untouched cell replaces the prior (VirtualMap.cpp:300-304)
-          const double *o = nx + (__ffsll((long long)m) - 1) * 192;
-          axx = o[0]; axy = o[1]; ayy = o[2];
-          u = 1;
-          m &= m - 1;
-        }
-        if (m) {
-          // every further update is fused; the next entry is loaded before the current one is fused, so that the LDS
-          // latency stays off the dependent chain
-          const double *o = nx + (__ffsll((long long)m) - 1) * 192;
-          double nxx = o[0], nxy = o[1], nyy = o[2];
-          m &= m - 1;
-          while (true) {
-            const double bxx = nxx, bxy = nxy, byy = nyy;
-            const bool more = m != 0ull;
-            if (more) {
-              const double *o2 = nx + (__ffsll((long long)m) - 1) * 192;
-              nxx = o2[0]; nxy = o2[1]; nyy = o2[2];
-              m &= m - 1;
-            }
-            ci_fuse(axx, axy, ayy, bxx, bxy, byy);
-            if (!more) break;
-          }
-        }
-        }
-        if (wprof) ci_clk += wall_clock64() - tc0;
-        if (ok) {
-          ixx[v] = axx; ixy[v] = axy; iyy[v] = ayy;
-          upd[v] = (uint8_t)u;
-          // occupancy ladder (OccupancyMap.cpp:64-138): the landmarks of the cell, then the poses that see it in
-          // trajectory order (ascending mask bits); between chunks the log-odds value is parked in prob[]
-          double l = 0.0;  // LOGODDS_UNKNOWN
-          int st = 0;      // ... as a state of the precomputed ladder (DrlgxState::lo_tr) when it is closed
-          const bool fsm = S.lo_ntab > 0;
-          if (c0 == 0) {
-            for (int n = lmc_cell; n > 0; --n) {
-              l = fmin(S.lo_max, fmax(S.lo_min, l + S.lo_occ));
-              st = ltr[4 * st];
-            }
-          } else {
-            l = prob[v];
-            st = (int)l;
-          }
-          m = om_cell;
-          if (fsm_reg) {
-            // a state that maps to itself is absorbing (the transition depends on the state only): the remaining bits
-            // cannot change it (cells at the clamped minimum / maximum, i.e. every cell seen more than a few times)
-            while (m) {
-              m &= m - 1;
-              const int f = (t_flag >> (2 * st)) & 3;
-              const int nst = (f & 1) ? st : (int)((((f & 2) ? t_occ : t_free) >> (4 * st)) & 15);
-              if (nst == st) break;
-              st = nst;
-            }
-            l = (double)st;
-          } else if (fsm) {
-            while (m) {
-              m &= m - 1;
-              const int f = ltr[4 * st + 2];
-              st = (f & 1) ? st : ((f & 2) ? ltr[4 * st] : ltr[4 * st + 1]);
-            }
-            l = (double)st;
-          } else {
-            while (m) {
-              m &= m - 1;
-              if (fabs(l - S.lo_min) < 1e-5) continue;
-              const double add = (l > S.occ_thresh + 1e-8) ? S.lo_occ : S.lo_free;
-              l = fmin(S.lo_max, fmax(S.lo_min, l + add));
-            }
-          }
-          if (!last) {
-            prob[v] = l;
-            continue;
-          }
-          // VirtualMap::updateProbability: prob = sum over num_samples identical maps of p / n
-          double pv = 0.0;
-          if (fsm) {
-            pv = lpv[st];
-          } else {
-            const double pv1 = logodds2prob(l);
-            for (int s2 = 0; s2 < cfg.num_samples; ++s2) pv += pv1 / cfg.num_samples;
-          }
-          prob[v] = pv;
-          // reductions (Planner2D.cpp:321-366, VirtualMap.cpp:47-59)
-          // trace and determinant of the covariance (= information^-1, 2 x 2): (a + d) / det, 1 / det
-          const double rdet = rcp_n1(axx * ayy - axy * axy);
-          const double tr = (axx + ayy) * rdet;
-          vtr[v] = tr;
-          utr += 1.0 * tr;
-          if (pv < cfg.occupancy_threshold) known += 1.0;
-          const double wgt = pv > 0.49 ? 1.0 : 0.0;
-          udet += wgt * rdet;
-          uwtr += wgt * tr;
-          const double x = (col + 0.5) * cfg.resolution + cfg.map_min_x, y = (row + 0.5) * cfg.resolution + cfg.map_min_y;
-          if ((pv < 0.49 || pv > 0.6) && cfg.map_min_x + extg <= x && x <= cfg.map_max_x - extg && cfg.map_min_y + extg <= y &&
-              y <= cfg.map_max_y - extg)
-            expl += 1.0;
-        }
+      m = om_cell;
+      // a state that maps to itself is absorbing (the transition depends on the state only): the remaining bits
+      // cannot change it (cells at the clamped minimum / maximum, i.e. every cell seen more than a few times)
+      while (m) {
+        m &= m - 1;
+        const int f = (fsm_t.t_flag >> (2 * st)) & 3;
+        const int nst = (f & 1) ? st : (int)((((f & 2) ? fsm_t.t_occ : fsm_t.t_free) >> (4 * st)) & 15);
+        if (nst == st) break;
+        st = nst;
       }
-      if (wprof) {
-        S.prof[48 + wave] = wall_clock64();
-        S.prof[56 + wave] = ci_clk;
+      if (!last) {
+        c.prob[v] = (double)st;
+        continue;
       }
-      __syncthreads();
-    }
-  } else {
-    // reductions only (after reset): the cells are read back
-    if (owed_from >= 0) {
-      copy_planes(S, owed_from, inst);
-      __syncthreads();
-    }
-    const int extg = 20;
-    for (int v = tid; v < V; v += kThreads) {
-      const int row = v / cols, col = v - row * cols;
-      const double a = ixx[v], b = ixy[v], d = iyy[v], pv = prob[v];
-      double ca, cb, cd;
-      inv2_llt_s(a, b, d, ca, cb, cd);
-      const double tr = ca + cd;
-      vtr[v] = tr;
-      utr += 1.0 * tr;
-      if (pv < cfg.occupancy_threshold) known += 1.0;
-      const double wgt = pv > 0.49 ? 1.0 : 0.0;
-      udet += wgt / (a * d - b * b);
-      uwtr += wgt * tr;
-      const double x = (col + 0.5) * cfg.resolution + cfg.map_min_x, y = (row + 0.5) * cfg.resolution + cfg.map_min_y;
-      if ((pv < 0.49 || pv > 0.6) && cfg.map_min_x + extg <= x && x <= cfg.map_max_x - extg && cfg.map_min_y + extg <= y &&
-          y <= cfg.map_max_y - extg)
-        expl += 1.0;
+      // VirtualMap::updateProbability: prob = sum over num_samples identical maps of p / n (the host's table)
+      const double pv = c.lpv[st];
+      c.prob[v] = pv;
+      // reductions (Planner2D.cpp:321-366, VirtualMap.cpp:47-59)
+      // trace and determinant of the covariance (= information^-1, 2 x 2): (a + d) / det, 1 / det
+      const double rdet = rcp_n1(axx * ayy - axy * axy);
+      const double tr = (axx + ayy) * rdet;
+      c.vtr[v] = tr;
+      sums.add_cell(cfg, row, col, pv, tr, rdet);
     }
   }
-  // ---- phase R: block reduction of the five utility sums ----
+  if (wprof) {
+    S.prof[48 + wave] = wall_clock64();
+    S.prof[56 + wave] = ci_clk;
+  }
+  __syncthreads();
+}
+
+// ---- reductions only (after reset): the cells are read back ----
+__device__ __forceinline__ void reductions_only(const DrlgxState &S, const MapCtx &c, UtilSums &sums) {
+  const drlgx_config &cfg = S.cfg;
+  const int cols = S.cols;
+  for (int v = drlgx_tid(); v < S.V; v += kThreads) {
+    const int row = v / cols, col = v - row * cols;
+    const double a = c.ixx[v], b = c.ixy[v], d = c.iyy[v], pv = c.prob[v];
+    double ca, cb, cd;
+    inv2_llt_s(a, b, d, ca, cb, cd);
+    const double tr = ca + cd;
+    c.vtr[v] = tr;
+    sums.add_cell(cfg, row, col, pv, tr, 1.0 / (a * d - b * b));  // (a true division: this path's own arithmetic)
+  }
+}
+
+// ---- phase R: block reduction of the five utility sums (wave shuffles + LDS), the result to red[] ----
+__device__ __forceinline__ void block_reduce(const DrlgxState &S, const MapCtx &c, const UtilSums &sums) {
+  const int tid = drlgx_tid();
   DRLGX_PROF(S, 19);
-  {
-    double r5[5] = {utr, known, expl, udet, uwtr};
+  double r5[5] = {sums.utr, sums.known, sums.expl, sums.udet, sums.uwtr};
 #pragma unroll
-    for (int k = 0; k < 5; ++k) r5[k] = wave_sum63(r5[k]);
-    __syncthreads();  // stage[] is free again
-    if ((tid & 63) == 63)
-      for (int k = 0; k < 5; ++k) stage[k * kWaves + (tid >> 6)] = r5[k];
-    __syncthreads();
-    if (tid == 0) {  // wave-major order: the same summation order as before
-      double acc[5];
-      for (int k = 0; k < 5; ++k) {
-        acc[k] = 0;
-        for (int w = 0; w < kWaves; ++w) acc[k] += stage[k * kWaves + w];
-      }
-      utr = acc[0]; known = acc[1]; expl = acc[2]; udet = acc[3]; uwtr = acc[4];
+  for (int k = 0; k < 5; ++k) r5[k] = wave_sum63(r5[k]);
+  __syncthreads();  // stage[] is free again
+  if ((tid & 63) == 63)
+    for (int k = 0; k < 5; ++k) c.stage[k * kWaves + (tid >> 6)] = r5[k];
+  __syncthreads();
+  if (tid == 0) {  // wave-major order: the same summation order as before
+    for (int k = 0; k < 5; ++k) {
+      r5[k] = 0;
+      for (int w = 0; w < kWaves; ++w) r5[k] += c.stage[k * kWaves + w];
     }
   }
   DRLGX_PROF(S, 20);
   if (tid == 0) {
-    double *red = S.red + (size_t)inst * DRLGX_RED_STRIDE;
-    red[R_UTR] = utr;
-    red[R_KNOWN] = known;
-    red[R_EXPL] = expl;
-    red[R_UDET] = udet;
-    red[R_UWTR] = uwtr;
+    double *red = S.red + (size_t)c.inst * DRLGX_RED_STRIDE;
+    red[R_UTR] = r5[0];
+    red[R_KNOWN] = r5[1];
+    red[R_EXPL] = r5[2];
+    red[R_UDET] = r5[3];
+    red[R_UWTR] = r5[4];
   }
+}
+
+// One belief update of the virtual map of instance sel.base + blockIdx.x, by one workgroup.  rebuild 0: the reductions only.
+// The phases run `chunk` poses at a time (one chunk unless P > 64 or the stage does not fit the LDS): pair list, A, C.
+template <bool kCompact = false>
+__device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &sel, int rebuild, int chunk, bool handed = false,
+                                         const double *lm_lds = nullptr, LadderEntry lo = LadderEntry{false, 0.0, -1, 0, 0}) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int tid = drlgx_tid();
+  const int bi = drlgx_bid();
+  if (!sel.on(bi) || !sel.map_on(bi)) return owed_planes(S, sel, bi);
+  MapCtx c;
+  c.inst = sel.base + bi;
+  const int *cnt = S.cnt + (size_t)c.inst * DRLGX_CNT_STRIDE;
+  // a rejected move leaves the belief as it was: nothing to rebuild, unless this is the one rebuild of a rollout
+  if ((lo.P >= 0 ? lo.flag : cnt[C_FLAG]) && !sel.map_last_only) return owed_planes(S, sel, bi);
+  c.P = lo.P >= 0 ? lo.P : cnt[C_P];
+  c.L = lo.P >= 0 ? lo.L : cnt[C_L];
+  c.pc = sel.cap(S.P_max);
+  c.chunk = chunk;
+  if (rebuild && c.P > c.pc) {  // (the host's bound was wrong: flag it, touch nothing)
+    if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+    return owed_planes(S, sel, bi);
+  }
+  c.carve<kCompact>(S, smem);
+  UtilSums sums;
+  DRLGX_PROF(S, 16);
+  if (rebuild) {
+    pose_setup<kCompact>(S, c, handed, lm_lds, lo);
+    DRLGX_PROF(S, 41);
+    if (!S.bbox_noop) bbox_sweep(S, c);
+    DRLGX_PROF(S, 17);
+    const LadderFsm fsm_t{S.lo_tocc, S.lo_tfree, S.lo_tflag};
+    for (int c0 = 0; c0 < c.P; c0 += chunk) {
+      const int nc = min(chunk, c.P - c0);
+      const bool last = c0 + nc >= c.P;
+      if (c0 > 0) {  // (the first chunk's masks were cleared while the pose tables were loading)
+        clear_masks<kCompact>(S, c, false);
+        __syncthreads();
+      }
+      if (c0 == 0) DRLGX_PROF(S, 42);
+      pair_list(S, c, c0, nc);
+      if (c0 == 0) DRLGX_PROF(S, 43);
+      const int npairs = *c.pcount;
+      if (kCompact && npairs > nc * kPairsPerPose) {  // (cannot happen for a disc-shaped footprint: flag it, leave the map alone)
+        if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+        return;
+      }
+      push_through<kCompact>(S, c, c0, npairs);
+      if (c0 == 0) DRLGX_PROF(S, 21);
+      cell_pass<kCompact>(S, c, c0, last, fsm_t, sums);
+    }
+  } else {
+    if (sel.vm_from >= 0) {
+      owed_planes(S, sel, bi);
+      __syncthreads();
+    }
+    reductions_only(S, c, sums);
+  }
+  block_reduce(S, c, sums);
 }
 
 __global__ __launch_bounds__(kThreads) void k_map(DRLGX_KS_PARAM, LaunchSel sel, int rebuild, int chunk) {
@@ -748,24 +763,14 @@ __global__ __launch_bounds__(kThreads, kMapCWaves) void k_map_c(DRLGX_KS_PARAM, 
 
 }  // namespace kmap
 
-static size_t map_lds_bytes(const DrlgxState &S, int chunk, int pc, bool compact = false) {
-  // pose tables, stage, the u64 mask(s) per cell, reduction scratch + ladder values
-  size_t d = (size_t)pc * 19 + (size_t)chunk * (compact ? kmap::kPairsPerPose : 64) * 3 + (compact ? 1 : 2) * (size_t)S.V + kmap::kWaves + DRLGX_LO_TAB;
-  // per-pose ints, landmark counts, ladder transitions, pair counter, pair list (+ the compact stage's index table)
-  size_t i = (size_t)pc * 7 + (size_t)S.V + DRLGX_LO_TAB + 1 + (size_t)chunk * 32 * (compact ? 2 : 1);
-  return d * sizeof(double) + i * sizeof(int) + 16;
-}
-namespace kmap {
-// byte offset of the cell masks inside map_body's LDS carve (k_step checks that what the SLAM stage hands over lies below)
-__host__ __device__ inline size_t masks_offset(int pc, int chunk) { return ((size_t)pc * 19 + (size_t)chunk * 64 * 3) * sizeof(double); }
-}  // namespace kmap
+static size_t map_lds_bytes(const DrlgxState &S, int chunk, int pc, bool compact = false) { return kmap::MapCarve(pc, chunk, S.V, compact).bytes; }
 
 // LDS bytes of k_map and the poses per A/C pass: all of them when the stage fits the LDS (<= 64: one mask bit per pose)
 // (pcap: the launch's pose bound - the tables and the chunk follow it, not the engine's capacity)
 size_t drlgx_map_lds_bytes(const DrlgxState &S, int *chunk_out, int pcap) {
   const int pc = pcap > 0 && pcap < S.P_max ? pcap : S.P_max;
   int chunk = pc < 64 ? pc : 64;
-  while (chunk > 1 && map_lds_bytes(S, chunk, pc) > 160 * 1024) chunk /= 2;
+  while (chunk > 1 && map_lds_bytes(S, chunk, pc) > kmap::kLdsBudget) chunk /= 2;
   if (chunk_out) *chunk_out = chunk;
   return map_lds_bytes(S, chunk, pc);
 }
@@ -776,7 +781,7 @@ static size_t map_lds_bytes_compact(const DrlgxState &S, int pcap, int *chunk_ou
   const int pc = pcap > 0 && pcap < S.P_max ? pcap : S.P_max;
   const int chunk = pc < 64 ? pc : 64;
   const size_t b = map_lds_bytes(S, chunk, pc, true);
-  if (b > 80 * 1024) return 0;
+  if (b > kmap::kLdsBudget / 2) return 0;
   *chunk_out = chunk;
   return b;
 }
@@ -809,7 +814,7 @@ void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel, int re
   const size_t lds = drlgx_map_lds_bytes(S, &chunk, sel.pcap);
   static bool attr_set[32] = {false};
   const void *fns[] = {reinterpret_cast<const void *>(&kmap::k_map), reinterpret_cast<const void *>(&kmap::k_map_c)};
-  drlgx_ensure_lds_attr(attr_set, fns, 2, 160 * 1024);
+  drlgx_ensure_lds_attr(attr_set, fns, 2, (int)kmap::kLdsBudget);
   // the form of which two workgroups fit a CU, for launches with more instances than CUs (DRLGX_MAP_COMPACT=1)
   static int n_cu = 0;
   const int force = map_form();

@@ -48,12 +48,9 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
   double *sim_dyn = reinterpret_cast<double *>(step_smem + 2 * DRLGX_MT_STRIDE * sizeof(uint32_t));
   double *lmbox = reinterpret_cast<double *>(step_smem + sim_bytes - 16 - (size_t)2 * S.LG * 8);
   const kslam::SimBox box{(n_measure == 2 && !sel.simlog) ? sim_dyn : nullptr, reinterpret_cast<const int *>(sim_dyn + 2 * S.LG + 2), lmbox};
-  // (the map stage's ladder tables: fetched now, stored to its LDS after the SLAM stage)
-  kmap::LadderEntry lo{S.lo_ntab <= kslam::kThreads, 0.0, 0u, -1, 0, 0};
-  if (lo.have && tid < S.lo_ntab) {
-    lo.pv = S.lo_pv[tid];
-    lo.tr = reinterpret_cast<const uint32_t *>(S.lo_tr)[tid];
-  }
+  // (the map stage's ladder values: fetched now, stored to its LDS after the SLAM stage)
+  kmap::LadderEntry lo{true, 0.0, -1, 0, 0};
+  if (tid < S.lo_ntab) lo.pv = S.lo_pv[tid];
   kslam::SlamCtx ctx;
   bool pre = false, accepted = false, inc_try = false;
   double od3[3] = {0, 0, 0};
@@ -124,12 +121,13 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     const uint32_t *img = reinterpret_cast<const uint32_t *>(step_smem);
     for (int i = tid - 64; i < 2 * DRLGX_MT_STRIDE; i += kslam::kThreads - 64) g[i] = img[i];
   }
-  // The pose estimates / information blocks go straight to where the map stage keeps them (its first 10 P_max doubles; its
-  // pose tables - 19 P_max doubles - must end inside the simulator's region, free by now, because the map stage fills the
-  // last of them while it reads the landmarks).  The landmark estimates stay in the SLAM stage's LDS: the map stage reads
+  // The pose estimates / information blocks go straight to where the map stage keeps them (sp and si, the first two of its
+  // pose tables; all three - kmap::MapCarve - must end inside the simulator's region, free by now, because the map stage fills
+  // the last of them while it reads the landmarks).  The landmark estimates stay in the SLAM stage's LDS: the map stage reads
   // them before the first array it writes beyond its pose tables (the information stage, in its phase A) is touched - as
   // long as they lie below its cell masks, which it clears first.
-  const bool hand = (size_t)pc * 19 * sizeof(double) + 16 <= sim_bytes - 16;
+  const kmap::MapCarve map_carve(pc, map_chunk, S.V, false);
+  const bool hand = map_carve.stage + 16 <= sim_bytes - 16;  // (stage: the first array behind the pose tables)
   const double *lm_lds = nullptr;
   bool inc_done = false;
   if (inc_try) {
@@ -155,7 +153,7 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     lo.L = appended ? sub_cnt[2] : L0;
     lo.flag = appended ? 0 : 1;
   }
-  const unsigned char *map_masks = step_smem + kmap::masks_offset(pc, map_chunk);
+  const unsigned char *map_masks = step_smem + map_carve.mask;
   if (!handed || reinterpret_cast<const unsigned char *>(lm_lds + 2 * (size_t)S.L_max) > map_masks) lm_lds = nullptr;
   if (!sel.skip_map) kmap::map_body<false>(S, sel, 1, map_chunk, handed, lm_lds, lo);
   if (S.prof && tid == 0 && bi < 448) S.prof[129 + 2 * bi] = wall_clock64();

@@ -11,7 +11,7 @@ i = txt.find("_ZN4kmap5k_mapE")
 i = txt.find("\n", txt.find(":", i))
 j = txt.find(".end_amdhsa_kernel", i)
 body = txt[i:j].split("\n")
-# phases of k_map.hip by line range (map_body), helpers by function
+# phases of k_map.hip: the functions map_body calls, by the line each starts at (in file order)
 import os
 mapsrc = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "drl_graph_exploration_amd", "csrc", "k_map.hip")).read().split("\n")
 def line_of(pat, start=0):
@@ -19,25 +19,28 @@ def line_of(pat, start=0):
         if pat in mapsrc[k]:
             return k + 1
     raise KeyError(pat)
-L = {k: line_of("DRLGX_PROF(S, %d)" % k) for k in (16, 40, 41, 17, 42, 43, 21, 19, 20)}
-f_predict = (line_of("void predict_info("), line_of("// VirtualMap::covarianceIntersection2D"))
-f_fuse = (line_of("void ci_fuse("), line_of("// Sum over the 64 lanes of a wave"))
-ladder0 = line_of("// occupancy ladder (OccupancyMap.cpp:64-138)")
-ladder1 = line_of("// VirtualMap::updateProbability: prob = sum over num_samples")
+FUNCS = [("void predict_info(", "A  EKF push-through (predict_info / predict_cell)"),
+         ("void ci_fuse(", "C  covariance-intersection fusion (ci_fuse)"),
+         ("double dpp_add(", "R  block reduction, outputs"),
+         ("struct LadderEntry", "prologue (carve, counts)"),
+         ("void copy_planes(", "exits that owe a plane copy"),
+         ("void clear_masks(", "tables: loads, clears"),
+         ("void pose_setup(", "tables, landmark cells, pose windows, LLT of the pose information"),
+         ("void bbox_sweep(", "bbox sweep (narrow sensors only)"),
+         ("int pair_test(", "A  range / FOV tests + compaction"),
+         ("void push_through(", "A  pair loop around the push-through (stage stores, masks)"),
+         ("void cell_pass(", "C  cell pass: tile walk, chain walk, ladder, outputs, utility terms"),
+         ("void reductions_only(", "reductions only (after reset)"),
+         ("void block_reduce(", "R  block reduction, outputs"),
+         ("void map_body(", "prologue (carve, counts)")]
+STARTS = sorted((line_of(pat), name) for pat, name in FUNCS)
 def phase(fn, ln):
     if fn != "k_map.hip":
         return None  # an inlined helper of another file (Pose2 algebra, libm, reciprocals): goes to the phase of the code around it
-    if f_predict[0] <= ln < f_predict[1]: return "A  EKF push-through (predict_info / predict_cell)"
-    if f_fuse[0] <= ln < f_fuse[1]: return "C  covariance-intersection fusion (ci_fuse)"
-    if ln < L[16]: return "prologue (carve, counts)"
-    if ln < L[40]: return "tables: loads, clears"
-    if ln < L[41]: return "landmark cells, pose windows, LLT of the pose information"
-    if ln < L[17]: return "bbox sweep (narrow sensors only)"
-    if ln < L[43]: return "A  range / FOV tests + compaction"
-    if ln < L[21]: return "A  pair loop around the push-through (stage stores, masks)"
-    if ladder0 <= ln < ladder1: return "C  occupancy ladder"
-    if ln < L[19]: return "C  cell pass: tile walk, chain walk, outputs, utility terms"
-    return "R  block reduction, outputs"
+    name = "prologue (carve, counts)"
+    for start, n in STARTS:
+        if ln >= start: name = n
+    return name
 cnt = collections.OrderedDict()
 cur = ("?", 0)
 last_phase = "prologue (carve, counts)"

@@ -64,6 +64,29 @@ def test_error_strings_and_create_without_device():
         Engine(default_config(40), 4)
 
 
+def test_create_refuses_a_map_beyond_the_map_kernels_lds():
+    """The map kernel keeps two 64-bit masks and a landmark count per cell, and its per-pose tables, in LDS: with one pose per pass
+    180 max_poses + 20 cells + 1876 bytes of the 160 KB.  A configuration beyond that is refused at creation, before the device."""
+    from drl_graph_exploration_amd import _lib, default_config
+    L = _lib.lib()
+    h = C.c_void_p()
+
+    def cfg_of(map_size, max_poses):
+        cfg = default_config(map_size, max_poses=max_poses)
+        cfg.resolution = 1.0
+        return cfg
+
+    no_such_device = 1 << 20  # the configuration check comes first; a creation that passes it ends here, on any box
+    # 88 x 88 cells: 39 poses take 163 776 bytes (64 below the limit), 40 take 163 956
+    assert L.drlgx_create(C.byref(cfg_of(48, 39)), 2, 0, no_such_device, C.byref(h)) == -2 and not h.value
+    assert b"map too large" not in L.drlgx_last_error(None)
+    assert L.drlgx_create(C.byref(cfg_of(48, 40)), 2, 0, no_such_device, C.byref(h)) == -1 and not h.value
+    assert L.drlgx_last_error(None) == b"map too large for the LDS tables of the map kernel"
+    # the 100 m map at resolution 1: 19 600 cells
+    assert L.drlgx_create(C.byref(cfg_of(100, 41)), 2, 0, 0, C.byref(h)) == -1 and not h.value
+    assert L.drlgx_last_error(None) == b"map too large for the LDS tables of the map kernel"
+
+
 def test_config_matches_oracle_config():
     from drl_graph_exploration_amd import default_config
     for ms, nl, alg in [(40, None, 0), (60, None, 0), (100, 100, 1), (40, 60, 0)]:
