@@ -41,6 +41,7 @@ SYMBOLS = [
     "drlgx_timing_read_host", "drlgx_debug_phase_clocks_host", "drlgx_debug_gemm_tile_rows", "drlgx_debug_map_form", "drlgx_inc_stats_host", "drlgx_gcn_workspace_bytes", "drlgx_gcn_forward", "drlgx_gcn_forward_batched", "drlgx_gcn_backward",
     "drlgx_replay_collate", "drlgx_replay_collate_pair", "drlgx_dqn_targets", "drlgx_dqn_loss_grad", "drlgx_dqn_arena_bytes", "drlgx_dqn_arena_views", "drlgx_dqn_prepare", "drlgx_dqn_forward_backward", "drlgx_replay_cache_csr", "drlgx_gcn_collate_csr", "drlgx_gcn_forward_prebuilt", "drlgx_adam_step", "drlgx_adam_step_scaled", "drlgx_normalise_rewards",
     "drlgx_segment_softmax", "drlgx_segment_softmax_backward", "drlgx_mean_pool", "drlgx_mean_pool_backward",
+    "drlgx_ggnn_workspace_bytes", "drlgx_ggnn_forward", "drlgx_ggnn_backward",
 ]
 
 
@@ -116,6 +117,10 @@ def lib():
     L.drlgx_gcn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.drlgx_gcn_forward.argtypes = [vp] + [C.c_int] * 5 + [vp] * 12
     L.drlgx_gcn_backward.argtypes = [vp] + [C.c_int] * 5 + [vp] * 15
+    L.drlgx_ggnn_workspace_bytes.restype = C.c_size_t
+    L.drlgx_ggnn_workspace_bytes.argtypes = [C.c_int] * 5
+    L.drlgx_ggnn_forward.argtypes = [vp] + [C.c_int] * 6 + [vp] * 13 + [C.c_int, vp, vp, C.c_int]
+    L.drlgx_ggnn_backward.argtypes = [vp] + [C.c_int] * 6 + [vp] * 17
     L.drlgx_replay_collate.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.drlgx_replay_collate_pair.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
     L.drlgx_gcn_forward_batched.argtypes = [vp] + [C.c_int] * 5 + [vp] * 12 + [C.c_int, vp, vp, C.c_int]

@@ -284,6 +284,150 @@ class ValueGCN(torch.nn.Module):
         return (s / cnt.clamp(min=1).unsqueeze(1)).mean(dim=1)  # global_mean_pool(x, batch).mean(dim=1)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# GG-NN (scripts/Networks.py:73-122 over PyG 1.x GatedGraphConv(1000, 3)): drlgx_ggnn_forward / drlgx_ggnn_backward
+# (csrc/k_ggnn.hip).  The seven trunk tensors, in the order of the C ABI: weight [L, C, C] (applied as h @ weight[l]), the GRU
+# cell's weight_ih / weight_hh [3C, C] and bias_ih / bias_hh [3C] (gate order r, z, n), then the read-out layer's Wf, bf.
+# ---------------------------------------------------------------------------------------------------------------------
+def _ggnn_call_forward(L, x, edge_index, edge_attr, params, mask, segs):
+    weight, w_ih, w_hh, b_ih, b_hh, Wf, bf = params
+    N, in_dim = x.shape
+    E = edge_index.shape[1]
+    n_layers, hidden, out_dim = weight.shape[0], weight.shape[1], Wf.shape[0]
+    dims = (N, E, in_dim, hidden, n_layers, out_dim)
+    nbytes = L.drlgx_ggnn_workspace_bytes(N, E, hidden, n_layers, out_dim)
+    if nbytes == 0:
+        raise _lib.DrlgxError("drlgx_ggnn_workspace_bytes: invalid sizes %r" % (dims,))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(N, out_dim, dtype=torch.float32, device=x.device)
+    n_graphs, node_off, edge_off, max_edges = (int(segs[0]), segs[1], segs[2], int(segs[3])) if segs is not None else (0, None, None, 0)
+    _lib.check(L.drlgx_ggnn_forward(C.c_void_p(_lib.stream_ptr(x.device)), *dims, _p(x), _p(edge_index), _p(edge_attr), *(_p(t) for t in params),
+                                    _p(mask), _p(out), _p(ws), n_graphs, _p(node_off), _p(edge_off), max_edges))
+    return out, ws, dims
+
+
+def _ggnn_call_backward(L, saved, d_out, grads):
+    x, edge_index, edge_attr, weight, w_ih, w_hh, Wf, mask, ws, dims = saved
+    _lib.check(L.drlgx_ggnn_backward(C.c_void_p(_lib.stream_ptr(x.device)), *dims, _p(x), _p(edge_index), _p(edge_attr), _p(weight), _p(w_ih),
+                                     _p(w_hh), _p(Wf), _p(mask), _p(d_out), *(_p(g) for g in grads), _p(ws)))
+
+
+class _GGNNTrunk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, edge_index, edge_attr, weight, w_ih, w_hh, b_ih, b_hh, Wf, bf, mask, segs=None):
+        if not x.is_cuda:
+            raise _lib.DrlgxError("drlgx GG-NN kernels need HIP tensors (no CPU fallback)")
+        L = _lib.lib()
+        x = x.contiguous().float()
+        edge_index = edge_index.contiguous().long()
+        edge_attr = edge_attr.contiguous().float()
+        params = tuple(t.detach().contiguous().float() for t in (weight, w_ih, w_hh, b_ih, b_hh, Wf, bf))
+        if mask is not None:
+            mask = mask.contiguous().float()
+        out, ws, dims = _ggnn_call_forward(L, x, edge_index, edge_attr, params, mask, segs)
+        ctx.saved = (x, edge_index, edge_attr, params[0], params[1], params[2], params[5], mask, ws, dims)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x = ctx.saved[0]
+        N, E, in_dim, hidden, n_layers, out_dim = ctx.saved[-1]
+        grads = tuple(torch.empty(s, dtype=torch.float32, device=x.device) for s in
+                      ((n_layers, hidden, hidden), (3 * hidden, hidden), (3 * hidden, hidden), (3 * hidden,), (3 * hidden,), (out_dim, hidden),
+                       (out_dim,)))
+        _ggnn_call_backward(_lib.lib(), ctx.saved, d_out.contiguous().float(), grads)
+        return (None, None, None) + grads + (None, None)
+
+
+def ggnn_forward_raw(x, edge_index, edge_attr, params, mask=None, segs=None):
+    """The trunk without an autograd graph: `params` = (weight, w_ih, w_hh, b_ih, b_hh, Wf, bf) fp32 HIP tensors.  Returns
+    (out, saved); `saved` is what `ggnn_backward_raw` needs (the workspace holds both CSRs and every layer's panels)."""
+    if not x.is_cuda:
+        raise _lib.DrlgxError("drlgx GG-NN kernels need HIP tensors (no CPU fallback)")
+    params = tuple(t.detach() for t in params)
+    out, ws, dims = _ggnn_call_forward(_lib.lib(), x, edge_index, edge_attr, params, mask, segs)
+    return out, (x, edge_index, edge_attr, params[0], params[1], params[2], params[5], mask, ws, dims)
+
+
+def ggnn_backward_raw(saved, d_out, grads):
+    """Gradients of the seven parameter tensors written (not accumulated) into `grads` = (d_weight, d_w_ih, d_w_hh, d_b_ih,
+    d_b_hh, dWf, dbf)."""
+    _ggnn_call_backward(_lib.lib(), saved, d_out, grads)
+
+
+def ggnn_trunk(x, edge_index, edge_attr, weight, w_ih, w_hh, b_ih, b_hh, Wf, bf, mask=None, segs=None):
+    return _GGNNTrunk.apply(x, edge_index, edge_attr, weight, w_ih, w_hh, b_ih, b_hh, Wf, bf, mask, segs)
+
+
+class GatedGraphConvParams(torch.nn.Module):
+    """Parameter holder with PyG-1.x GatedGraphConv's layout and init: weight [num_layers, C, C] uniform(-1/sqrt(C), 1/sqrt(C)),
+    `rnn` a torch.nn.GRUCell(C, C) with torch's own reset_parameters."""
+
+    def __init__(self, out_channels, num_layers):
+        super().__init__()
+        self.out_channels, self.num_layers = out_channels, num_layers
+        self.weight = torch.nn.Parameter(torch.empty(num_layers, out_channels, out_channels))
+        self.rnn = torch.nn.GRUCell(out_channels, out_channels)
+        bound = 1.0 / math.sqrt(out_channels)
+        with torch.no_grad():
+            self.weight.uniform_(-bound, bound)
+
+
+class _GGNNBase(torch.nn.Module):
+    OUT = 1
+
+    def __init__(self):
+        super().__init__()
+        self.gconv1 = GatedGraphConvParams(1000, 3)
+        self.fully_con1 = torch.nn.Linear(1000, self.OUT)
+
+    def trunk_parameters(self):
+        """(weight, w_ih, w_hh, b_ih, b_hh, Wf, bf) in the order of drlgx_ggnn_forward / _backward."""
+        r = self.gconv1.rnn
+        return (self.gconv1.weight, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh, self.fully_con1.weight, self.fully_con1.bias)
+
+    def _trunk(self, data, p):
+        x = data.x
+        mask = _dropout_mask(x.shape[0], 1000, float(p), x.device)
+        return ggnn_trunk(x, data.edge_index, data.edge_attr, *self.trunk_parameters(), mask, graph_segments(data))
+
+
+class GGNN(_GGNNBase):
+    """scripts/Networks.py:73-89 (DQN head: one Q value per node)."""
+
+    def forward(self, data, prob, batch=None):
+        return self._trunk(data, prob)
+
+
+class PolicyGGNN(_GGNNBase):
+    """scripts/Networks.py:92-104 (A2C actor: softmax over the masked (frontier) nodes of every graph)."""
+
+    def forward(self, data, mask, batch=None):
+        q = self._trunk(data, 0.5)  # F.dropout(x): p = 0.5 even at inference
+        segs = graph_segments(data)
+        if segs is not None and mask.dtype == torch.bool:
+            n_masked = getattr(data, "n_masked", None)
+            return _SegmentSoftmax.apply(q.view(-1), mask, segs[1], int(mask.sum()) if n_masked is None else int(n_masked))
+        q = torch.masked_select(q.view(-1), mask)
+        b = torch.masked_select(batch, mask)
+        return segment_softmax(q, b, int(batch.max().item()) + 1 if batch.numel() else 0)
+
+
+class ValueGGNN(_GGNNBase):
+    """scripts/Networks.py:107-122 (A2C critic: Linear 1000->100, global mean pool, mean over the 100)."""
+    OUT = 100
+
+    def forward(self, data, mask, batch=None):
+        h = self._trunk(data, 0.5)
+        segs = graph_segments(data)
+        if segs is not None:
+            return _MeanPool.apply(h, segs[1])
+        g = int(batch.max().item()) + 1
+        s = torch.zeros(g, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, batch, h)
+        cnt = torch.zeros(g, dtype=h.dtype, device=h.device).index_add_(0, batch, torch.ones_like(batch, dtype=h.dtype))
+        return (s / cnt.clamp(min=1).unsqueeze(1)).mean(dim=1)  # global_mean_pool(x, batch).mean(dim=1)
+
+
 class GraphData(object):
     """Minimal stand-in for torch_geometric.data.Data / Batch (x, edge_index, edge_attr, batch, .to())."""
 

@@ -1,6 +1,6 @@
 """`run_training.py` of the reference (scripts/run_training.py): ONE training epoch - load the pickled trainer
 (`saved_training.pkl`, replay buffer included) and the two model checkpoints, run `trainer.running(...)`, pickle the
-trainer back.  `python -m drl_graph_exploration_amd.run_training <DQN|A2C> <GCN> [--data-root ../data] [--n-envs 64]`."""
+trainer back.  `python -m drl_graph_exploration_amd.run_training <DQN|A2C> <GCN|GG-NN> [--data-root ../data] [--n-envs 64]`."""
 import argparse
 import os
 import pickle
@@ -27,7 +27,7 @@ def run_epoch(training_method, model_name, data_root="../data", n_envs=64):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("training_method", choices=["DQN", "A2C"])
-    ap.add_argument("model_name")
+    ap.add_argument("model_name", help="GCN or GG-NN")
     ap.add_argument("--data-root", default="../data")
     ap.add_argument("--n-envs", type=int, default=64)
     args = ap.parse_args(argv)

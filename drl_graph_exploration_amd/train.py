@@ -5,7 +5,7 @@ reference spawns `python3 run_training.py <method> <model>` per epoch; `--subpro
 epoch appends `temp_reward.csv` / `temp_loss.csv` to the TensorBoard log `<data_root>/torch_logs/<case>/` under the tags
 'Train/avg_reward' and 'Train/loss' (scripts/train.py:85-94).
 
-    python -m drl_graph_exploration_amd.train [DQN|A2C] [GCN] [--data-root ../data] [--epochs N] [--n-envs 64] [--subprocess]
+    python -m drl_graph_exploration_amd.train [DQN|A2C] [GCN|GG-NN] [--data-root ../data] [--epochs N] [--n-envs 64] [--subprocess]
 """
 import argparse
 import os
@@ -27,12 +27,16 @@ def paths(data_root, training_method, model_name):
 
 
 def make_models(training_method, model_name, device):
-    if model_name != "GCN":
-        raise NotImplementedError("only the GCN models are on the accelerated path (GG-NN / g-U-Net: SURVEY.md, out of scope)")
+    """The reference's model families by its own names (scripts/train.py:12): "GCN" and "GG-NN" (case paths `DQN_GG-NN/`,
+    `A2C_GG-NN/`) are on the accelerated path."""
+    families = {"GCN": (networks.GCN, networks.PolicyGCN, networks.ValueGCN), "GG-NN": (networks.GGNN, networks.PolicyGGNN, networks.ValueGGNN)}
+    if model_name not in families:
+        raise NotImplementedError("g-U-Net is not on the accelerated path (SURVEY.md, out of scope); model_name is GCN or GG-NN")
+    q, actor, critic = families[model_name]
     if training_method == "DQN":
-        return networks.GCN().to(device), networks.GCN().to(device)
+        return q().to(device), q().to(device)
     if training_method == "A2C":
-        return networks.PolicyGCN().to(device), networks.ValueGCN().to(device)
+        return actor().to(device), critic().to(device)
     raise ValueError(training_method)
 
 
@@ -52,7 +56,7 @@ def log_epoch(writer, object_path):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("training_method", nargs="?", default="DQN", choices=["DQN", "A2C"])
-    ap.add_argument("model_name", nargs="?", default="GCN")
+    ap.add_argument("model_name", nargs="?", default="GCN", help="GCN or GG-NN")
     ap.add_argument("--data-root", default="../data")
     ap.add_argument("--epochs", type=int, default=None, help="default: EXPLORE / epoch like the reference")
     ap.add_argument("--epoch-steps", type=int, default=None, help="override the trainer's `epoch` (environment steps per epoch)")

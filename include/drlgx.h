@@ -347,6 +347,33 @@ int drlgx_gcn_backward(void *hip_stream, int n_nodes, int n_edges, int in_dim, i
                        const float *W2, const float *Wf, const float *dropout_mask, const float *d_out,
                        float *dW1, float *db1, float *dW2, float *db2, float *dWf, float *dbf, void *ws_dev);
 
+/* ---- GG-NN policy (scripts/Networks.py:73-122 over PyG 1.x GatedGraphConv(1000, 3)) ------------ */
+
+/* Forward of the GGNN / PolicyGGNN / ValueGGNN trunk (scripts/Networks.py:73-122): h_0 = [x | 0] (in_dim <= 8 columns, zero-padded
+ * to hidden); n_layers times  a = (A h) weight[l],  h = GRUCell(a, h)  with (A h)[i] = the sum over the edges e into i
+ * (edge_index[1][e] = i) of edge_attr[e] h[edge_index[0][e]] - raw weights, no self loops added, no normalisation - and the GRU
+ * cell of torch.nn.GRUCell (w_ih / w_hh [3 hidden][hidden], b_ih / b_hh [3 hidden], gate order r, z, n); then
+ * out = (relu(h) [* dropout mask]) Wf^T + bf.  All pointers DEVICE, fp32 (edge_index int64 as PyG); weight, b_ih, b_hh and
+ * the mask 16-byte aligned.  n_graphs > 0: the batch's graph boundaries as drlgx_gcn_forward_batched takes them (both CSRs in one
+ * launch while no graph has more than 2 048 edges); n_graphs <= 0: the generic CSR build.  Same results bit for bit.
+ * ws_dev: workspace of drlgx_ggnn_workspace_bytes(); it keeps what the backward call needs (both CSRs and per layer h, A h,
+ * a and the gates r, z, n, W_hn h + b_hn).  DRLGX_E_INVALID: in_dim > 8, in_dim > hidden, hidden & 3, n_layers < 1 (or > 16),
+ * null pointers. */
+size_t drlgx_ggnn_workspace_bytes(int n_nodes, int n_edges, int hidden, int n_layers, int out_dim);
+int drlgx_ggnn_forward(void *hip_stream, int n_nodes, int n_edges, int in_dim, int hidden, int n_layers, int out_dim,
+                       const float *x, const int64_t *edge_index, const float *edge_attr,
+                       const float *weight /*[L,h,h]*/, const float *w_ih /*[3h,h]*/, const float *w_hh,
+                       const float *b_ih, const float *b_hh, const float *Wf, const float *bf,
+                       const float *dropout_mask /* [n_nodes*hidden] or NULL */, float *out, void *ws_dev,
+                       int n_graphs, const int32_t *node_off, const int32_t *edge_off, int max_edges_per_graph);
+/* Backward of the same trunk (scripts/Networks.py:73-122), after drlgx_ggnn_forward on the same workspace: given d(out) writes
+ * (not accumulates) the gradients of all seven parameter tensors; rows in_dim.. of d_weight[0] are zeros.  Deterministic. */
+int drlgx_ggnn_backward(void *hip_stream, int n_nodes, int n_edges, int in_dim, int hidden, int n_layers, int out_dim,
+                        const float *x, const int64_t *edge_index, const float *edge_attr, const float *weight,
+                        const float *w_ih, const float *w_hh, const float *Wf, const float *dropout_mask, const float *d_out,
+                        float *d_weight, float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh,
+                        float *dWf, float *dbf, void *ws_dev);
+
 /* ---- DQN update (scripts/policy.py:137-178, :234-253): the pieces between the two GCN calls ---------------- */
 
 /* Mini-batch collation of replay graphs held in a device pool = torch_geometric DataLoader(s_j_batch, batch_size=BATCH)
