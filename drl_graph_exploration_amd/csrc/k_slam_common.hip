@@ -5,6 +5,7 @@
 // SimBox: k_slam.hip, k_inc.hip).
 #pragma once
 #include "k_sweep.hip"
+#include "arrow_carve.h"
 namespace kslam {
 #pragma clang fp contract(fast)
 // ---- capacities of the SLAM kernels (one 512-thread workgroup per instance, the whole dynamic LDS) ----
@@ -15,11 +16,8 @@ constexpr int kLdsBudget = 160 * 1024;
 // ~65 us for the dense solve at 41).
 constexpr int kFastTiles = 8;  // N = 128: <= 42 poses
 constexpr int kDenseTiles = 10;
-// The pose-chain solver's landmark system: <= 63 landmarks (N <= 128) packed in LDS; beyond, swept from the workspace with up to
-// kArrowRegTiles register tiles per wave (N <= 256, <= 127 landmarks) or, larger still, every tile streamed (k_sweep_ws.hip)
-constexpr int kFastTilesArrow = 8;
+// (the pose-chain solver's capacities kFastTilesArrow and kArrowRegTiles: arrow_carve.h, with its layout)
 static_assert(kFastTilesArrow == 8, "inc_plan (k_inc.hip) spells the reach of k_step_arrow out as 16 * 8");
-constexpr int kArrowRegTiles = 20;
 
 constexpr int REC = 12;  // per-factor record: [0..5] Jx (2x3) -> later G (3x2); [6..9] Jl (2x2) -> later partial; [10..11] e
 // (12 doubles put the 64-bit accesses of a half-wave that walks consecutive records on 8 banks; a stride of 13 is

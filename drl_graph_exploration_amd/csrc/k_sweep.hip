@@ -15,7 +15,7 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // doubles of the LDS region of a packed N x N system swept by sweep_packed_fast: the packed lower triangle, or the sweep's
 // panels (two pivot-column panels, two W panels, two E tiles, two diagonal-tile dumps) that alias it
 // (+ 6 N + 64 behind the triangle: SlamCtx::front parks 18 doubles per pose there - up to N = 128 the panels' size covers it)
-__host__ __device__ inline size_t sweep_region_doubles(size_t N) {
+__host__ __device__ constexpr size_t sweep_region_doubles(size_t N) {
   const size_t a = N * (N + 1) / 2 + 6 * N + 64, b = 64 * N + 1024;
   return a > b ? a : b;
 }
