@@ -6,16 +6,12 @@
 #pragma once
 #include "k_sweep.hip"
 #include "arrow_carve.h"
+#include "slam_carve.h"
 namespace kslam {
 #pragma clang fp contract(fast)
 // ---- capacities of the SLAM kernels (one 512-thread workgroup per instance, the whole dynamic LDS) ----
 constexpr int kLdsBudget = 160 * 1024;
-// The landmark-first dense solve (k_slam.hip) serves systems of up to kDenseTiles tile rows (N = 160: 53 poses).  Up to
-// kFastTiles the sweep gives every wave ONE tile row; with nine and ten rows (43 .. 53 poses) two light rows share a wave
-// (sweep_packed_fast).  That keeps such updates off the pose-chain solver (k_slam_arrow.hip: ~230 us at 46 poses against
-// ~65 us for the dense solve at 41).
-constexpr int kFastTiles = 8;  // N = 128: <= 42 poses
-constexpr int kDenseTiles = 10;
+// (the dense solver's capacities kFastTiles and kDenseTiles: slam_carve.h, with its layout)
 // (the pose-chain solver's capacities kFastTilesArrow and kArrowRegTiles: arrow_carve.h, with its layout)
 static_assert(kFastTilesArrow == 8, "inc_plan (k_inc.hip) spells the reach of k_step_arrow out as 16 * 8");
 

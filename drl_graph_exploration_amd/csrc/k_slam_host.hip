@@ -1,24 +1,13 @@
-// Host side of the SLAM stage: what the dense solver (k_slam.hip) needs in LDS for given capacities - the pose-chain solver's
-// LDS and workspace layout is arrow_carve.h -, which of the kernels serves an engine, and the launch of the stand-alone SLAM stage (called by drlgx_engine.cpp and
+// Host side of the SLAM stage: which capacities the dense solver (k_slam.hip; its LDS layout: slam_carve.h) and the pose-chain
+// solver (LDS and workspace layout: arrow_carve.h) serve, which of the kernels serves an engine, and the launch of the stand-alone SLAM stage (called by drlgx_engine.cpp and
 // by the host functions of k_step.hip).
 #pragma once
 #include <algorithm>
 #include "k_slam.hip"
 #include "k_slam_arrow.hip"
-namespace kslam {
-// LDS needed by the always-resident small arrays of the fast path
-size_t slam_dim(int P_max) { return 16 * (((size_t)3 * P_max + 1 + 15) / 16); }
-size_t slam_small_bytes(int P_max, int L_max, int M_max) {  // (SlamCtx::setup)
-  return (size_t)P_max * 64 + (size_t)L_max * 16 + (size_t)L_max * 64 + (size_t)L_max * 8 * ((P_max + 63) / 64) +
-         (size_t)(P_max + 2) * 4 + (size_t)(L_max + 2) * 8 + (size_t)M_max * 7 + (size_t)L_max * 2 + 224;
-}
-}  // namespace kslam
-
 // true when the fused LDS-resident kernel applies to trajectories of up to P_max poses
 bool drlgx_slam_in_lds(int P_max, int L_max, int M_max) {
-  const size_t n = kslam::slam_dim(P_max), nf = std::max<size_t>(n, 16 * kslam::kFastTiles);
-  return n <= (size_t)16 * kslam::kDenseTiles &&
-         kslam::slam_small_bytes(P_max, L_max, M_max) + kslam::sweep_region_doubles(nf) * 8 <= (size_t)kslam::kLdsBudget;
+  return kslam::SlamCarve::fits(P_max, L_max, M_max, 0, kslam::kLdsBudget);
 }
 // capacities the SLAM kernels can serve at all (checked by drlgx_create)
 bool drlgx_slam_capacity_ok(int P_max, int L_max, int M_max) {

@@ -242,10 +242,8 @@ __global__ __launch_bounds__(kslam::kThreads) void k_step_arrow_loop(DRLGX_KS_PA
 bool drlgx_step_fusable(const DrlgxState &S, int p_bound) {
   int chunk = 0;
   const int Pb = p_bound < S.P_max ? p_bound : S.P_max;
-  const size_t nf = std::max<size_t>(kslam::slam_dim(Pb), 16 * kslam::kFastTiles);
   // (the SLAM stage sits behind the simulator's LDS: its front end runs beside the simulator wave)
-  return drlgx_slam_in_lds(Pb, S.L_max, S.M_max) &&
-         kstep::sim_lds_bytes(S.LG, Pb) + kslam::slam_small_bytes(Pb, S.L_max, S.M_max) + kslam::sweep_region_doubles(nf) * 8 <= (size_t)kslam::kLdsBudget &&
+  return kslam::SlamCarve::fits(Pb, S.L_max, S.M_max, kstep::sim_lds_bytes(S.LG, Pb), kslam::kLdsBudget) &&
          drlgx_map_lds_bytes(S, &chunk, Pb) <= (size_t)kslam::kLdsBudget;
 }
 
