@@ -42,6 +42,7 @@ SYMBOLS = [
     "drlgx_replay_collate", "drlgx_replay_collate_pair", "drlgx_dqn_targets", "drlgx_dqn_loss_grad", "drlgx_dqn_arena_bytes", "drlgx_dqn_arena_views", "drlgx_dqn_prepare", "drlgx_dqn_forward_backward", "drlgx_replay_cache_csr", "drlgx_gcn_collate_csr", "drlgx_gcn_forward_prebuilt", "drlgx_adam_step", "drlgx_adam_step_scaled", "drlgx_normalise_rewards",
     "drlgx_segment_softmax", "drlgx_segment_softmax_backward", "drlgx_mean_pool", "drlgx_mean_pool_backward",
     "drlgx_ggnn_workspace_bytes", "drlgx_ggnn_forward", "drlgx_ggnn_backward",
+    "drlgx_unet_workspace_bytes", "drlgx_unet_forward", "drlgx_unet_backward", "drlgx_unet_topk", "drlgx_unet_augment_filter", "drlgx_unet_kept_nodes",
 ]
 
 
@@ -121,6 +122,15 @@ def lib():
     L.drlgx_ggnn_workspace_bytes.argtypes = [C.c_int] * 5
     L.drlgx_ggnn_forward.argtypes = [vp] + [C.c_int] * 6 + [vp] * 13 + [C.c_int, vp, vp, C.c_int]
     L.drlgx_ggnn_backward.argtypes = [vp] + [C.c_int] * 6 + [vp] * 17
+    L.drlgx_unet_workspace_bytes.restype = C.c_size_t
+    L.drlgx_unet_workspace_bytes.argtypes = [C.c_int] * 6 + [C.c_double, C.c_int]
+    L.drlgx_unet_forward.argtypes = [vp] + [C.c_int] * 5 + [C.c_double, C.c_int] + [vp] * 3 + [C.POINTER(vp)] + [vp] * 3 + [C.c_size_t, C.c_int, vp, vp,
+                                                                                                                       C.c_int]
+    L.drlgx_unet_backward.argtypes = [vp] + [C.c_int] * 5 + [C.c_double, C.c_int] + [vp] * 3 + [C.POINTER(vp), vp, vp, C.POINTER(vp), vp, C.c_size_t,
+                                                                                                C.c_int, C.c_int]
+    L.drlgx_unet_kept_nodes.argtypes = [vp] + [C.c_int] * 4 + [C.c_double, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]
+    L.drlgx_unet_topk.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_double, vp, vp, vp, vp]
+    L.drlgx_unet_augment_filter.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.drlgx_replay_collate.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.drlgx_replay_collate_pair.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
     L.drlgx_gcn_forward_batched.argtypes = [vp] + [C.c_int] * 5 + [vp] * 12 + [C.c_int, vp, vp, C.c_int]

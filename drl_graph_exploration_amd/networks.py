@@ -428,6 +428,216 @@ class ValueGGNN(_GGNNBase):
         return (s / cnt.clamp(min=1).unsqueeze(1)).mean(dim=1)  # global_mean_pool(x, batch).mean(dim=1)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# g-U-Net (scripts/Networks.py:125-449 over PyG 1.x GraphUNet / TopKPooling): drlgx_unet_forward / drlgx_unet_backward
+# (csrc/k_unet.hip).  The 5 depth + 4 trunk tensors go in state_dict order: down_convs.{0..depth}.{weight [in, out], bias},
+# pools.{0..depth-1}.weight [1, C], up_convs.{0..depth-1}.{weight, bias}, fully_con1.{weight, bias}.
+# `segs` here is (n_graphs, node_off, edge_off, host bound on the NODES of one graph); None: the input is one graph.
+# ---------------------------------------------------------------------------------------------------------------------
+def _unet_call_forward(L, x, edge_index, edge_attr, params, depth, ratio, mask, segs):
+    N, in_dim = x.shape
+    E = edge_index.shape[1]
+    hidden, out_dim = params[0].shape[1], params[-2].shape[0]
+    n_graphs, node_off, edge_off, max_nodes = (int(segs[0]), segs[1], segs[2], int(segs[3])) if segs is not None else (0, None, None, N)
+    dims = (N, E, in_dim, hidden, int(depth), float(ratio), out_dim)
+    nbytes = L.drlgx_unet_workspace_bytes(N, E, n_graphs, max_nodes, hidden, int(depth), float(ratio), out_dim)
+    if nbytes == 0:
+        raise _lib.DrlgxError("drlgx_unet_workspace_bytes: invalid sizes %r, or a graph of more than 4096 nodes (%d)" % (dims, max_nodes))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(N, out_dim, dtype=torch.float32, device=x.device)
+    ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    _lib.check(L.drlgx_unet_forward(C.c_void_p(_lib.stream_ptr(x.device)), *dims, _p(x), _p(edge_index), _p(edge_attr), ptrs, _p(mask), _p(out),
+                                    _p(ws), nbytes, n_graphs, _p(node_off), _p(edge_off), max_nodes))
+    return out, ws, dims + (n_graphs, max_nodes)
+
+
+def _unet_call_backward(L, saved, d_out, grads):
+    x, edge_index, edge_attr, params, mask, ws, dims = saved
+    n = len(params)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in params])
+    gptrs = (C.c_void_p * n)(*[t.data_ptr() for t in grads])
+    _lib.check(L.drlgx_unet_backward(C.c_void_p(_lib.stream_ptr(x.device)), *dims[:7], _p(x), _p(edge_index), _p(edge_attr), ptrs, _p(mask),
+                                     _p(d_out), gptrs, _p(ws), ws.numel(), dims[7], dims[8]))
+
+
+class _UNetTrunk(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, edge_index, edge_attr, mask, segs, depth, ratio, *params):
+        if not x.is_cuda:
+            raise _lib.DrlgxError("drlgx g-U-Net kernels need HIP tensors (no CPU fallback)")
+        L = _lib.lib()
+        x = x.contiguous().float()
+        edge_index = edge_index.contiguous().long()
+        edge_attr = edge_attr.contiguous().float()
+        params = tuple(t.detach().contiguous().float() for t in params)
+        if mask is not None:
+            mask = mask.contiguous().float()
+        out, ws, dims = _unet_call_forward(L, x, edge_index, edge_attr, params, depth, ratio, mask, segs)
+        ctx.saved = (x, edge_index, edge_attr, params, mask, ws, dims)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        params = ctx.saved[3]
+        grads = tuple(torch.empty_like(p) for p in params)
+        _unet_call_backward(_lib.lib(), ctx.saved, d_out.contiguous().float(), grads)
+        return (None,) * 7 + grads
+
+
+def unet_forward_raw(x, edge_index, edge_attr, params, depth, ratio=0.5, mask=None, segs=None):
+    """The trunk without an autograd graph: `params` = the 5 depth + 4 fp32 HIP tensors in state_dict order.  Returns (out, saved);
+    `saved` is what `unet_backward_raw` needs (the workspace holds every level's CSRs, kept sets, scores and panels)."""
+    if not x.is_cuda:
+        raise _lib.DrlgxError("drlgx g-U-Net kernels need HIP tensors (no CPU fallback)")
+    params = tuple(t.detach() for t in params)
+    out, ws, dims = _unet_call_forward(_lib.lib(), x, edge_index, edge_attr, params, depth, ratio, mask, segs)
+    return out, (x, edge_index, edge_attr, params, mask, ws, dims)
+
+
+def unet_backward_raw(saved, d_out, grads):
+    """Gradients of the 5 depth + 4 parameter tensors written (not accumulated) into `grads` (the parameters' order and shapes)."""
+    _unet_call_backward(_lib.lib(), saved, d_out, grads)
+
+
+def unet_kept_nodes(saved, level):
+    """The nodes the forward behind `saved` kept at `level` (1..depth): int32 ids of the level above, ascending per graph."""
+    x, ws, (N, E, in_dim, hidden, depth, ratio, out_dim, n_graphs, max_nodes) = saved[0], saved[5], saved[6]
+    perm = torch.empty(N, dtype=torch.int32, device=x.device)
+    count = C.c_int(0)
+    _lib.check(_lib.lib().drlgx_unet_kept_nodes(C.c_void_p(_lib.stream_ptr(x.device)), N, E, hidden, depth, ratio, out_dim, _p(ws), ws.numel(),
+                                                n_graphs, max_nodes, int(level), _p(perm), C.byref(count)))
+    return perm[:count.value]
+
+
+def unet_trunk(x, edge_index, edge_attr, params, depth, ratio=0.5, mask=None, segs=None):
+    return _UNetTrunk.apply(x, edge_index, edge_attr, mask, segs, depth, ratio, *params)
+
+
+def unet_segments(data, batch=None):
+    """(n_graphs, node_off, edge_off, largest node count of a graph) for the g-U-Net calls, or None (one graph): from the batch's
+    own graph boundaries, else from a PyG batch vector (graphs contiguous, edges grouped by graph).  The host-side node bound is
+    `data.max_graph_nodes` where the caller knows it; otherwise it is read from the device once and kept on `data`."""
+    segs = graph_segments(data)
+    if segs is not None:
+        n_graphs, node_off, edge_off = segs[0], segs[1], segs[2]
+    elif batch is not None and batch.numel() > 0 and batch.is_cuda:
+        n_graphs = int(batch[-1].item()) + 1
+        if n_graphs == 1:
+            return None
+        z = torch.zeros(1, dtype=torch.long, device=batch.device)
+        counts = torch.bincount(batch, minlength=n_graphs)
+        ecounts = torch.bincount(batch[data.edge_index[0]], minlength=n_graphs)
+        node_off, edge_off = torch.cat([z, counts.cumsum(0)]).int(), torch.cat([z, ecounts.cumsum(0)]).int()
+    else:
+        return None
+    mx = getattr(data, "max_graph_nodes", None)
+    if mx is None:
+        mx = int((node_off[1:] - node_off[:-1]).max().item()) if n_graphs > 0 else 0
+        try:
+            data.max_graph_nodes = mx
+        except AttributeError:
+            pass
+    return (n_graphs, node_off, edge_off, int(mx))
+
+
+class TopKPoolingParams(torch.nn.Module):
+    """Parameter holder with PyG-1.x TopKPooling's layout and init: weight [1, C] uniform(-1/sqrt(C), 1/sqrt(C))."""
+
+    def __init__(self, in_channels, ratio=0.5):
+        super().__init__()
+        self.in_channels, self.ratio = in_channels, ratio
+        self.weight = torch.nn.Parameter(torch.empty(1, in_channels))
+        bound = 1.0 / math.sqrt(in_channels)
+        with torch.no_grad():
+            self.weight.uniform_(-bound, bound)
+
+
+class _GraphUNetBase(torch.nn.Module):
+    OUT = 1
+
+    def __init__(self, in_channels, hidden_channels, out_channels, depth, pool_ratios=0.5, sum_res=True, act=torch.nn.functional.relu):
+        super().__init__()
+        if not sum_res:
+            raise ValueError("g-U-Net on the HIP path sums the residual (sum_res=True), as the reference builds it")
+        if act not in (torch.nn.functional.relu, torch.relu):
+            raise ValueError("g-U-Net on the HIP path has relu activations only")
+        if not isinstance(depth, int) or depth < 1 or depth > 4:
+            raise ValueError("g-U-Net depth must be 1..4, got %r" % (depth,))
+        ratios = [float(r) for r in pool_ratios] if isinstance(pool_ratios, (list, tuple)) else [float(pool_ratios)] * depth
+        if len(ratios) != depth or any(r != ratios[0] for r in ratios) or not 0.0 < ratios[0] <= 1.0:
+            raise ValueError("g-U-Net on the HIP path takes one pool ratio in (0, 1] for every level, got %r" % (pool_ratios,))
+        if out_channels != hidden_channels:
+            raise ValueError("g-U-Net on the HIP path needs out_channels == hidden_channels (the reference: 1000, 1000)")
+        if not 0 < in_channels <= 8 or hidden_channels % 4:
+            raise ValueError("g-U-Net on the HIP path takes at most 8 input features and a hidden width that is a multiple of 4")
+        self.in_channels, self.hidden_channels, self.out_channels, self.depth = in_channels, hidden_channels, out_channels, depth
+        self.pool_ratios, self.sum_res, self.act = ratios, sum_res, act
+        ch = hidden_channels
+        self.down_convs = torch.nn.ModuleList([GCNConvParams(in_channels, ch, improved=True)])
+        self.pools = torch.nn.ModuleList()
+        for i in range(depth):
+            self.pools.append(TopKPoolingParams(ch, ratios[i]))
+            self.down_convs.append(GCNConvParams(ch, ch, improved=True))
+        self.up_convs = torch.nn.ModuleList([GCNConvParams(ch, ch, improved=True) for _ in range(depth - 1)] + [GCNConvParams(ch, out_channels, improved=True)])
+        self.fully_con1 = torch.nn.Linear(out_channels, self.OUT)
+
+    def trunk_parameters(self):
+        """The 5 depth + 4 tensors in the order of drlgx_unet_forward / _backward (= state_dict order)."""
+        return tuple(self.parameters())
+
+    def _trunk(self, data, p, batch):
+        x = data.x
+        if not x.is_cuda:
+            raise _lib.DrlgxError("drlgx g-U-Net kernels need HIP tensors (no CPU fallback)")
+        mask = _dropout_mask(x.shape[0], self.out_channels, float(p), x.device)
+        return unet_trunk(x, data.edge_index, data.edge_attr, self.trunk_parameters(), self.depth, self.pool_ratios[0], mask,
+                          unet_segments(data, batch))
+
+    def __repr__(self):
+        return "%s(%d, %d, %d, depth=%d, pool_ratios=%r)" % (type(self).__name__, self.in_channels, self.hidden_channels, self.out_channels,
+                                                             self.depth, self.pool_ratios)
+
+
+class GraphUNet(_GraphUNetBase):
+    """scripts/Networks.py:125-230 (DQN head: one Q value per node)."""
+
+    def forward(self, data, prob, batch=None):
+        return self._trunk(data, prob, batch)
+
+
+class PolicyGraphUNet(_GraphUNetBase):
+    """scripts/Networks.py:233-341 (A2C actor: softmax over the masked (frontier) nodes of every graph of the ORIGINAL batch)."""
+
+    def forward(self, data, mask, batch=None):
+        q = self._trunk(data, 0.5, batch)  # F.dropout(x): p = 0.5 even at inference
+        segs = graph_segments(data)
+        if segs is not None and mask.dtype == torch.bool:
+            n_masked = getattr(data, "n_masked", None)
+            return _SegmentSoftmax.apply(q.view(-1), mask, segs[1], int(mask.sum()) if n_masked is None else int(n_masked))
+        if batch is None:
+            batch = torch.zeros(q.shape[0], dtype=torch.long, device=q.device)
+        q = torch.masked_select(q.view(-1), mask)
+        b = torch.masked_select(batch, mask)
+        return segment_softmax(q, b, int(batch.max().item()) + 1 if batch.numel() else 0)
+
+
+class ValueGraphUNet(_GraphUNetBase):
+    """scripts/Networks.py:344-449 (A2C critic: Linear 1000->100, global mean pool over the original batch, mean over the 100)."""
+    OUT = 100
+
+    def forward(self, data, mask, batch=None):
+        h = self._trunk(data, 0.5, batch)
+        segs = graph_segments(data)
+        if segs is not None:
+            return _MeanPool.apply(h, segs[1])
+        if batch is None:
+            batch = torch.zeros(h.shape[0], dtype=torch.long, device=h.device)
+        g = int(batch.max().item()) + 1
+        s = torch.zeros(g, h.shape[1], dtype=h.dtype, device=h.device).index_add_(0, batch, h)
+        cnt = torch.zeros(g, dtype=h.dtype, device=h.device).index_add_(0, batch, torch.ones_like(batch, dtype=h.dtype))
+        return (s / cnt.clamp(min=1).unsqueeze(1)).mean(dim=1)  # global_mean_pool(x, batch).mean(dim=1)
+
+
 class GraphData(object):
     """Minimal stand-in for torch_geometric.data.Data / Batch (x, edge_index, edge_attr, batch, .to())."""
 

@@ -3,7 +3,8 @@ reference's element-wise gradient clamp in front of it (scripts/policy.py:250-25
 in ONE kernel launch (csrc/k_train.hip: drlgx_adam_step) instead of a dozen framework kernels per step.
 
 Same call surface as the torch optimiser the reference constructs (`zero_grad()`, `step()`, `state_dict()`); parameters
-must be fp32 HIP tensors (at most 8 of them - the GCN has six).
+must be fp32 HIP tensors.  A launch takes up to eight tensors (the GCN has six, the GG-NN seven): a longer list - a depth-3
+g-U-Net has nineteen - is stepped in groups of eight, one launch per group over the same flat gradient bucket.
 """
 import ctypes as C
 
@@ -73,10 +74,12 @@ class GradientBucket(object):
 
 
 class FusedAdam(object):
+    GROUP = 8  # tensors per drlgx_adam_step launch
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_clamp=0.0):
         self.params = [p for p in params]
-        if not self.params or len(self.params) > 8:
-            raise ValueError("FusedAdam takes 1..8 parameter tensors")
+        if not self.params:
+            raise ValueError("FusedAdam takes at least one parameter tensor")
         for p in self.params:
             if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                 raise _lib.DrlgxError("FusedAdam needs contiguous fp32 HIP tensors (no CPU fallback)")
@@ -102,17 +105,20 @@ class FusedAdam(object):
 
     def step(self, grad_scale=1.0):
         """grad_scale: factor on the gradient in front of the clamp (GradientBucket.finish: 1 / world size)."""
-        n = len(self.params)
         self.step_count += 1
         vp = C.c_void_p
-        arr = lambda ts: (vp * n)(*[t.data_ptr() for t in ts])  # noqa: E731
         grads = self.grads()
-        sizes = (C.c_int64 * n)(*[p.numel() for p in self.params])
         dev = self.params[0].device
         stream = _lib.stream_ptr(dev)
-        _lib.check(_lib.lib().drlgx_adam_step_scaled(vp(stream), n, arr([p.data for p in self.params]), arr(grads), arr(self.exp_avg),
-                                                     arr(self.exp_avg_sq), sizes, self.param_groups[0]["lr"], self.betas[0],
-                                                     self.betas[1], self.eps, self.step_count, self.grad_clamp, float(grad_scale)))
+        for lo in range(0, len(self.params), self.GROUP):  # 1..8 tensors: the one launch
+            hi = min(lo + self.GROUP, len(self.params))
+            n = hi - lo
+            arr = lambda ts: (vp * n)(*[t.data_ptr() for t in ts])  # noqa: E731
+            sizes = (C.c_int64 * n)(*[p.numel() for p in self.params[lo:hi]])
+            _lib.check(_lib.lib().drlgx_adam_step_scaled(vp(stream), n, arr([p.data for p in self.params[lo:hi]]), arr(grads[lo:hi]),
+                                                         arr(self.exp_avg[lo:hi]), arr(self.exp_avg_sq[lo:hi]), sizes,
+                                                         self.param_groups[0]["lr"], self.betas[0], self.betas[1], self.eps, self.step_count,
+                                                         self.grad_clamp, float(grad_scale)))
 
     def state_dict(self):
         return {"step": self.step_count, "exp_avg": [t.clone() for t in self.exp_avg], "exp_avg_sq": [t.clone() for t in self.exp_avg_sq],

@@ -374,6 +374,63 @@ int drlgx_ggnn_backward(void *hip_stream, int n_nodes, int n_edges, int in_dim, 
                         float *d_weight, float *d_w_ih, float *d_w_hh, float *d_b_ih, float *d_b_hh,
                         float *dWf, float *dbf, void *ws_dev);
 
+/* ---- g-U-Net policy (scripts/Networks.py:125-449 over PyG 1.x GraphUNet / TopKPooling) --------- */
+
+/* Forward of the GraphUNet / PolicyGraphUNet / ValueGraphUNet trunk with sum_res and relu:
+ *   x_0 = relu(conv_d0(x, A_0));  for l = 1..depth:  B = offdiag((A_{l-1} + I)^2),  s = tanh(x_{l-1} . p_l / |p_l|),  perm_l = per
+ *   graph the k = ceil(pool_ratio n_g) nodes of largest s (equal scores: the lower node index; kept nodes stay in ascending index,
+ *   so pooled batches stay grouped by graph),  A_l = B[perm_l, perm_l] relabelled,  x_l = relu(conv_dl(x_{l-1}[perm_l] s[perm_l], A_l));
+ *   for i = 0..depth-1, j = depth-1-i:  x = relu(conv_ui(x_j + up, A_j)), up[perm_{j+1}] = x (the last relu is the trunk's own and
+ *   carries the dropout mask);  out = x Wf^T + bf.
+ * M[edge_index[0][e], edge_index[1][e]] = edge_attr[e], duplicates sum, (M M)[i][j] = sum_k M[i][k] M[k][j]; the added self loops
+ * weigh 1; B keeps every structurally non-zero off-diagonal entry.  Every conv is GCNConv(improved=True) as drlgx_gcn_forward
+ * computes it.  Edge weights are data: no gradient.  ceil is taken of the double product.
+ * params: HOST array of 5 depth + 4 DEVICE pointers in state_dict order - down_convs.{0..depth}.{weight [in][hidden], bias},
+ * pools.{0..depth-1}.weight [hidden], up_convs.{0..depth-1}.{weight [hidden][hidden], bias}, fully_con1.{weight [out_dim][hidden],
+ * bias} - all fp32 and 16-byte aligned, as the mask.  Graph boundaries as drlgx_gcn_forward_batched takes them (DEVICE int32
+ * [n_graphs + 1]; edges of graph g in [edge_off[g], edge_off[g+1]), an edge that leaves its graph is ignored); n_graphs = 0: the
+ * whole input is one graph.  max_graph_nodes: a HOST bound on the nodes of one graph (at most 4 096: the augment keeps dense
+ * rows of a graph in LDS).
+ * ws_dev: workspace of drlgx_unet_workspace_bytes() for the same sizes, ws_bytes its size; it keeps what the backward call
+ * needs (per level both CSRs, the pooled edge list, scores, kept sets, the convs' aggregated inputs and relu outputs).
+ * The levels' sizes are read back from the device once per call (the call synchronises the stream).
+ * DRLGX_E_INVALID: in_dim > 8, hidden & 3, depth outside 1..4, pool_ratio outside (0, 1], null or misaligned pointers, node_off
+ * that does not end at n_nodes.  DRLGX_E_CAPACITY: ws_bytes too small (nothing is written), a graph larger than max_graph_nodes
+ * or than 4 096 nodes (only the level offsets have been written). */
+size_t drlgx_unet_workspace_bytes(int n_nodes, int n_edges, int n_graphs, int max_graph_nodes, int hidden, int depth, double pool_ratio,
+                                  int out_dim);
+int drlgx_unet_forward(void *hip_stream, int n_nodes, int n_edges, int in_dim, int hidden, int depth, double pool_ratio, int out_dim,
+                       const float *x, const int64_t *edge_index, const float *edge_attr, const float *const *params,
+                       const float *dropout_mask /* [n_nodes*hidden] or NULL */, float *out, void *ws_dev, size_t ws_bytes,
+                       int n_graphs, const int32_t *node_off, const int32_t *edge_off, int max_graph_nodes);
+/* Backward of the same trunk, after drlgx_unet_forward on the same workspace with the same sizes: given d(out) writes (not
+ * accumulates) the gradients of all 5 depth + 4 parameter tensors into grads (HOST array of DEVICE pointers, params' order and
+ * shapes), d p_l with the term through |p_l|.  Deterministic. */
+int drlgx_unet_backward(void *hip_stream, int n_nodes, int n_edges, int in_dim, int hidden, int depth, double pool_ratio, int out_dim,
+                        const float *x, const int64_t *edge_index, const float *edge_attr, const float *const *params,
+                        const float *dropout_mask, const float *d_out, float *const *grads, void *ws_dev, size_t ws_bytes,
+                        int n_graphs, int max_graph_nodes);
+/* The nodes a forward kept at `level` (1..depth), from its workspace: ids of level - 1's nodes, ascending per graph, into perm_out
+ * (DEVICE int32, room for n_nodes); *count_host receives their number.  Same sizes as the forward call.  Synchronises. */
+int drlgx_unet_kept_nodes(void *hip_stream, int n_nodes, int n_edges, int hidden, int depth, double pool_ratio, int out_dim, void *ws_dev,
+                          size_t ws_bytes, int n_graphs, int max_graph_nodes, int level, int32_t *perm_out, int *count_host);
+/* The selection alone: per graph the k = ceil(pool_ratio n_g) nodes of largest score, equal scores to the lower index, written
+ * in ascending node index.  Out (DEVICE int32): pooled_node_off [n_graphs + 1], pooled_edge_off [n_graphs + 1] or NULL (the
+ * prefix of k_g (k_g - 1): where drlgx_unet_augment_filter puts each graph's entries), perm [sum of k_g] (node ids),
+ * inverse [n_nodes] or NULL (pooled id of a node, -1 if dropped).  No sort, no atomics: deterministic. */
+int drlgx_unet_topk(void *hip_stream, int n_nodes, int n_graphs, const int32_t *node_off, const float *scores, double pool_ratio,
+                    int32_t *pooled_node_off, int32_t *pooled_edge_off, int32_t *perm, int32_t *inverse);
+/* Augment and filter alone: per graph offdiag((A + I)^2) restricted to the kept nodes `perm` (ascending per graph, as
+ * drlgx_unet_topk writes them) and relabelled to pooled ids.  Graph g's entries go to pooled_edge_index [2][pooled_capacity]
+ * (int64) / pooled_edge_attr from slot pooled_edge_off[g] on, sorted by (row, column), each (row, column) once; the unused
+ * slots up to pooled_edge_off[g+1] get -1 / 0 (the GCN's CSR builders ignore them); pooled_edge_count [n_graphs] (or NULL)
+ * receives the entries per graph.  A graph's slot range must hold k_g (k_g - 1) entries; what does not fit is not written.
+ * DRLGX_E_CAPACITY: max_graph_nodes > 4 096. */
+int drlgx_unet_augment_filter(void *hip_stream, int n_nodes, int n_edges, const int64_t *edge_index, const float *edge_attr, int n_graphs,
+                              const int32_t *node_off, const int32_t *edge_off, int max_graph_nodes, const int32_t *perm,
+                              const int32_t *pooled_node_off, const int32_t *pooled_edge_off, int64_t pooled_capacity,
+                              int64_t *pooled_edge_index, float *pooled_edge_attr, int32_t *pooled_edge_count);
+
 /* ---- DQN update (scripts/policy.py:137-178, :234-253): the pieces between the two GCN calls ---------------- */
 
 /* Mini-batch collation of replay graphs held in a device pool = torch_geometric DataLoader(s_j_batch, batch_size=BATCH)
