@@ -33,7 +33,7 @@ SYMBOLS = [
     "drlgx_create", "drlgx_destroy", "drlgx_set_stream", "drlgx_synchronize", "drlgx_strerror", "drlgx_last_error",
     "drlgx_status_host", "drlgx_status_fetch_host", "drlgx_reset_host", "drlgx_step", "drlgx_utility", "drlgx_uncertainty_em", "drlgx_explored", "drlgx_metrics", "drlgx_cov_array",
     "drlgx_stage_reset_host", "drlgx_stage_set_prior_information_host", "drlgx_stage_set_prior_pose_host", "drlgx_stage_move", "drlgx_stage_measure", "drlgx_stage_add_measurements", "drlgx_stage_optimize",
-    "drlgx_stage_update_map", "drlgx_set_planner_parameter", "drlgx_set_fixed_landmarks_host", "drlgx_fm2_update", "drlgx_step_plan", "drlgx_step_plans",
+    "drlgx_stage_update_map", "drlgx_set_planner_parameter", "drlgx_set_fixed_landmarks_host", "drlgx_fm2_update", "drlgx_step_plan", "drlgx_step_plans", "drlgx_step_plans_traced",
     "drlgx_line_plan", "drlgx_lookahead", "drlgx_lookahead_bounded", "drlgx_graph_capacity", "drlgx_graph", "drlgx_get_counts_host", "drlgx_counts",
     "drlgx_get_poses_host", "drlgx_get_landmarks_host", "drlgx_get_cov_traces_host", "drlgx_vm_shape",
     "drlgx_get_virtual_map_host", "drlgx_get_ground_truth_host", "drlgx_get_adjacency_host", "drlgx_get_factors_host",
@@ -42,6 +42,7 @@ SYMBOLS = [
     "drlgx_replay_collate", "drlgx_replay_collate_pair", "drlgx_dqn_targets", "drlgx_dqn_loss_grad", "drlgx_dqn_arena_bytes", "drlgx_dqn_arena_views", "drlgx_dqn_prepare", "drlgx_dqn_forward_backward", "drlgx_replay_cache_csr", "drlgx_gcn_collate_csr", "drlgx_gcn_forward_prebuilt", "drlgx_adam_step", "drlgx_adam_step_scaled", "drlgx_normalise_rewards",
     "drlgx_segment_softmax", "drlgx_segment_softmax_backward", "drlgx_mean_pool", "drlgx_mean_pool_backward",
     "drlgx_ggnn_workspace_bytes", "drlgx_ggnn_forward", "drlgx_ggnn_backward",
+    "drlgx_greedy_plans",
     "drlgx_unet_workspace_bytes", "drlgx_unet_forward", "drlgx_unet_backward", "drlgx_unet_topk", "drlgx_unet_augment_filter", "drlgx_unet_kept_nodes",
 ]
 
@@ -74,6 +75,8 @@ def lib():
     L.drlgx_step.argtypes = [vp, vp, vp]
     L.drlgx_step_plan.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.drlgx_step_plans.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    L.drlgx_step_plans_traced.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp]
+    L.drlgx_greedy_plans.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 5 + [C.c_int, C.c_int, vp, vp, vp]
     L.drlgx_stage_reset_host.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint32), dp]
     L.drlgx_stage_set_prior_information_host.argtypes = [vp, C.c_int, dp]
     L.drlgx_stage_set_prior_pose_host.argtypes = [vp, C.c_int, dp]

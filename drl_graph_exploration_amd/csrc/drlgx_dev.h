@@ -729,6 +729,9 @@ void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc
                              const double *actions, const int32_t *n_actions, const double *sig, size_t sig_stride, double *scratch,
                              size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride, int32_t *n_out);
 void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, double *out);
+// behind action index a of the chosen plans: the per-action record and the device-side stop at done (k_plan_record)
+void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,
+                              int max_steps, double *trace, int32_t *done);
 void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length, double *angle);
 void drlgx_launch_line_plan(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *goal,
                             double *actions, int32_t *n_actions);

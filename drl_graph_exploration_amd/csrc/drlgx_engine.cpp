@@ -861,6 +861,23 @@ int drlgx_step_plans(drlgx_engine *e, const double *actions_dev, const int32_t *
   return check_launch(e);
 }
 
+// The evaluation script's form of that loop (scripts/test.py:128-152): one launch per action index - the form whose intermediate
+// maps are defined - with k_plan_record behind each: the metrics of every executed action, and an env that is done leaves its plan
+// there (the record cuts n_actions_dev, which the later indices' launches read).  The host's pose bounds advance per launched index:
+// an upper bound also for the envs that stop early.
+int drlgx_step_plans_traced(drlgx_engine *e, const double *actions_dev, int32_t *n_actions_dev, int max_n_actions, double sigma0,
+                            double done_explored, int max_steps, double *trace_dev, int32_t *done_dev) {
+  DRLGX_ENTER(e);
+  if (!e || !actions_dev || !n_actions_dev || !trace_dev || !done_dev || max_n_actions < 0 || max_n_actions > e->S.A_max)
+    return DRLGX_E_INVALID;
+  for (int a = 0; a < max_n_actions; ++a) {
+    const int r = drlgx_step_plan(e, actions_dev, n_actions_dev, a, 0);
+    if (r) return r;
+    drlgx_launch_plan_record(e->S, e->stream, sigma0, a, n_actions_dev, done_explored, max_steps, trace_dev, done_dev);
+  }
+  return check_launch(e);
+}
+
 // ---- staged form of the belief step: one call per call of SS2D.__init__ / SS2D.simulate (scripts/envs/pyss2d.py) -------
 int drlgx_stage_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const uint32_t *seeds, const double *start) {
   DRLGX_ENTER(e);

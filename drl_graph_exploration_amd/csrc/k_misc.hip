@@ -231,13 +231,14 @@ __global__ void k_line_plan(DrlgxState S, int n_cand, const int32_t *cand_env, c
   if (n > S.A_max) atomicMin(S.status, DRLGX_E_CAPACITY);
 }
 
-// The metric trio of the reference's evaluation script, one 256-thread workgroup per environment:
-//   out[3 e + 0] landmark error   (exploration_env.py:170-177): (sum_j |gt[key_j] - est_j| + sigma0 (n_gt - L)) / n_gt
-//   out[3 e + 1] map entropy      (scripts/test.py:61-74): -sum_v p ln p + 0.5 ln(0.5) (V - interior cells)
-//   out[3 e + 2] max localisation uncertainty (exploration_env.py:190-194): max over the poses of tr(marginal covariance)
-__global__ __launch_bounds__(256) void k_metrics(DrlgxState S, double sigma0, double *out) {
-  __shared__ double red[3][4];
-  const int e = blockIdx.x, tid = threadIdx.x;
+// The metric trio of the reference's evaluation script for environment e, by one 256-thread workgroup (red: its 3 x 4 doubles of
+// LDS); thread 0 returns with the values in m[0..2], the other threads' m is undefined:
+//   m[0] landmark error   (exploration_env.py:170-177): (sum_j |gt[key_j] - est_j| + sigma0 (n_gt - L)) / n_gt
+//   m[1] map entropy      (scripts/test.py:61-74): -sum_v p ln p + 0.5 ln(0.5) (V - interior cells)
+//   m[2] max localisation uncertainty (exploration_env.py:190-194): max over the poses of tr(marginal covariance)
+// k_metrics and k_plan_record both call it: one reduction order, the same bits.
+__device__ __forceinline__ void metrics_of(const DrlgxState &S, int e, double sigma0, double (*red)[4], double (&m)[3]) {
+  const int tid = threadIdx.x;
   const int *cnt = S.cnt + (size_t)e * DRLGX_CNT_STRIDE;
   const int P = cnt[C_P], L = cnt[C_L];
   const double *gt = S.gt_lm + (size_t)S.parent[e] * S.LG * 2;
@@ -267,9 +268,97 @@ __global__ __launch_bounds__(256) void k_metrics(DrlgxState S, double sigma0, do
     const int n_gt = S.cfg.num_landmarks;
     const double es = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     const double hs = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    out[3 * e] = (es + sigma0 * (n_gt - L)) / n_gt;
-    out[3 * e + 1] = -hs + 0.5 * log(0.5) * (double)(S.V - S.count_explored);
-    out[3 * e + 2] = fmax(fmax(red[2][0], red[2][1]), fmax(red[2][2], red[2][3]));
+    m[0] = (es + sigma0 * (n_gt - L)) / n_gt;
+    m[1] = -hs + 0.5 * log(0.5) * (double)(S.V - S.count_explored);
+    m[2] = fmax(fmax(red[2][0], red[2][1]), fmax(red[2][2], red[2][3]));
+  }
+}
+
+// out[3 e + 0 .. 2] = the trio of every environment, one workgroup each
+__global__ __launch_bounds__(256) void k_metrics(DrlgxState S, double sigma0, double *out) {
+  __shared__ double red[3][4];
+  const int e = blockIdx.x;
+  double m[3];
+  metrics_of(S, e, sigma0, red, m);
+  if (threadIdx.x == 0) {
+    out[3 * e] = m[0];
+    out[3 * e + 1] = m[1];
+    out[3 * e + 2] = m[2];
+  }
+}
+
+// The evaluation loop's per-action record (scripts/test.py:128-152), launched behind action index a of the chosen plans, one
+// workgroup per environment; an env whose plan has ended (a >= n_actions[e]) is left alone.  trace[e][a] = (the trio of k_metrics,
+// VirtualMap::explored as k_utility's mode 1 computes it), then ExplorationEnv.step's terminal test (exploration_env.py:107-110):
+// when it holds the env is flagged done and its plan is cut behind this action, so that the launches of the later action indices
+// skip it (LaunchSel::on reads n_actions).
+__global__ __launch_bounds__(256) void k_plan_record(DrlgxState S, double sigma0, int a, int32_t *n_actions, double done_explored,
+                                                     int max_steps, double *trace, int32_t *done) {
+  __shared__ double red[3][4];
+  const int e = blockIdx.x;
+  if (a >= n_actions[e]) return;  // (the whole workgroup: nobody waits at metrics_of's barrier)
+  double m[3];
+  metrics_of(S, e, sigma0, red, m);
+  if (threadIdx.x == 0) {
+    double *t = trace + ((size_t)e * S.A_max + a) * 4;
+    const double explored = S.red[(size_t)e * DRLGX_RED_STRIDE + R_EXPL] / (double)S.count_explored;
+    t[0] = m[0];
+    t[1] = m[1];
+    t[2] = m[2];
+    t[3] = explored;
+    if (explored > done_explored || S.cnt[(size_t)e * DRLGX_CNT_STRIDE + C_STEP] > max_steps) {
+      done[e] = 1;
+      n_actions[e] = a + 1;
+    }
+  }
+}
+
+// numpy's arg-max order over (value, index) pairs: a NaN beats every number, among equals (and among NaNs) the lower index wins;
+// index < 0 = no element
+__device__ __forceinline__ bool pick_beats(float v, int i, float bv, int bi) {
+  if (i < 0) return false;
+  if (bi < 0) return true;
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > bv || (v == bv && i < bi);
+}
+
+// The greedy decision of the evaluation loop (scripts/test.py:110-119), one wave per environment: choice[e] = np.argmax over the
+// env's frontier segment score[seg_begin[e] .. + n_frontier[e]) and the line plan of that frontier slot out of the padded plans of
+// Engine.graph(plan=True), zero-filled behind its length.  An inactive env or one without frontiers: choice -1, an empty plan.
+// Lanes stride over the segment, then a butterfly over (value, index): registers only.
+__global__ __launch_bounds__(64) void k_greedy_plans(const float *score, int n_score, const int32_t *seg_begin, const int32_t *n_frontier,
+                                                     const uint8_t *active, const double *actions_pad, const int32_t *n_act_pad,
+                                                     int max_frontier, int max_actions, int32_t *choice, double *actions_out,
+                                                     int32_t *n_actions_out) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const int b = seg_begin[e];
+  // (a segment that is not inside score[0, n_score) is a caller's error: it is cut there instead of read)
+  const int n = (active && !active[e]) || b < 0 ? 0 : min(min(n_frontier[e], max_frontier), n_score - b);
+  const float *q = score + b;
+  float bv = 0.f;
+  int bi = -1;
+  for (int i = lane; i < n; i += 64) {
+    const float v = q[i];
+    if (pick_beats(v, i, bv, bi)) { bv = v; bi = i; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (pick_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  int na = 0;
+  const double *src = actions_pad;
+  if (bi >= 0) {
+    const size_t slot = (size_t)e * max_frontier + bi;
+    na = min(max(n_act_pad[slot], 0), max_actions);
+    src += slot * max_actions * 3;
+  }
+  double *dst = actions_out + (size_t)e * max_actions * 3;
+  for (int k = lane; k < 3 * max_actions; k += 64) dst[k] = k < 3 * na ? src[k] : 0.0;
+  if (lane == 0) {
+    choice[e] = bi;
+    n_actions_out[e] = na;
   }
 }
 
@@ -300,6 +389,10 @@ __global__ __launch_bounds__(256) void k_cov_array(DrlgxState S, double *length,
 
 void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, double *out) {
   hipLaunchKernelGGL(k_metrics, dim3(S.n_envs), dim3(256), 0, st, S, sigma0, out);
+}
+void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,
+                              int max_steps, double *trace, int32_t *done) {
+  hipLaunchKernelGGL(k_plan_record, dim3(S.n_envs), dim3(256), 0, st, S, sigma0, a, n_actions, done_explored, max_steps, trace, done);
 }
 void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length, double *angle) {
   hipLaunchKernelGGL(k_cov_array, dim3((S.V + 255) / 256, S.n_envs), dim3(256), 0, st, S, length, angle);
@@ -336,4 +429,16 @@ void drlgx_launch_line_plan(const DrlgxState &S, hipStream_t st, int n_cand, con
                             double *actions, int32_t *n_actions) {
   hipLaunchKernelGGL(k_line_plan, dim3((n_cand + 127) / 128), dim3(128), 0, st, S, n_cand, cand_env, goal, actions,
                      n_actions);
+}
+
+int drlgx_greedy_plans(void *hip_stream, int n_envs, const float *score, int n_score, const int32_t *seg_begin, const int32_t *n_frontier,
+                       const uint8_t *active, const double *actions_pad, const int32_t *n_act_pad, int max_frontier, int max_actions,
+                       int32_t *choice, double *actions_out, int32_t *n_actions_out) {
+  if (n_envs <= 0 || !score || n_score < 0 || !seg_begin || !n_frontier || !actions_pad || !n_act_pad || max_frontier <= 0 || max_actions <= 0 ||
+      !choice || !actions_out || !n_actions_out)
+    return DRLGX_E_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  hipLaunchKernelGGL(k_greedy_plans, dim3(n_envs), dim3(64), 0, st, score, n_score, seg_begin, n_frontier, active, actions_pad, n_act_pad,
+                     max_frontier, max_actions, choice, actions_out, n_actions_out);
+  return hipGetLastError() == hipSuccess ? DRLGX_OK : DRLGX_E_HIP;
 }

@@ -132,6 +132,50 @@ class Engine(object):
         self.use_torch_stream()
         self._chk(self.L.drlgx_step_plans(self.h, _p(actions), _p(n_actions), int(max_n_actions), 1 if map_last_only else 0))
 
+    def step_plans_traced(self, actions, n_actions, max_n_actions, sigma0=1.0, done_explored=0.85, max_steps=5000):
+        """Every env's plan as the reference's evaluation loop executes it (drlgx_step_plans_traced, scripts/test.py:128-152): per
+        executed action the row (landmark error, map entropy, max localisation uncertainty, explored), and an env stops behind
+        the action at which `explored > done_explored or step > max_steps` holds - on the device.  Returns device tensors
+        (trace [n_envs, max_actions, 4] f64, pre-filled with NaN: rows beyond an env's executed actions keep it; n_executed
+        [n_envs] i32; done [n_envs] i32).  `n_actions` is left as it is."""
+        self.use_torch_stream()
+        A = self.cfg.max_actions
+        if not (actions.is_cuda and actions.dtype == torch.float64 and actions.is_contiguous() and
+                tuple(actions.shape) == (self.n_envs, A, 3)):
+            raise ValueError("actions: contiguous CUDA float64 [n_envs, max_actions, 3]")
+        n_exec = n_actions.to(torch.int32).clamp(0, A).contiguous().clone()
+        if n_exec.numel() != self.n_envs:
+            raise ValueError("n_actions: [n_envs]")
+        trace = torch.full((self.n_envs, A, 4), float("nan"), dtype=torch.float64, device=self.device)
+        done = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        self._chk(self.L.drlgx_step_plans_traced(self.h, _p(actions), _p(n_exec), int(max_n_actions), float(sigma0),
+                                                 float(done_explored), int(max_steps), _p(trace), _p(done)))
+        return trace, n_exec, done
+
+    @staticmethod
+    def greedy_plans(score, seg_begin, n_frontier, actions_pad, n_act_pad, active=None):
+        """The greedy decision of every env on the device (drlgx_greedy_plans; stateless - it runs on torch's current stream of the
+        tensors' device and needs no engine handle): the first arg-max of `score` (f32) over the env's
+        frontier segment [seg_begin[e], + n_frontier[e]) in numpy's order (a NaN first) and that frontier's plan out of
+        `graph(plan=True)`'s actions_pad [n_envs, Fmax, A, 3] / n_act_pad [n_envs, Fmax].  Returns (choice [n_envs] i32, -1 for
+        an inactive env or one without frontiers; actions [n_envs, A, 3] f64, zero behind the plan; n_actions [n_envs] i32)."""
+        n, mf, A = actions_pad.shape[0], actions_pad.shape[1], actions_pad.shape[2]
+        dev = actions_pad.device
+        if score.dtype != torch.float32 or actions_pad.dtype != torch.float64 or n_act_pad.dtype != torch.int32:
+            raise ValueError("score float32, actions_pad float64, n_act_pad int32")
+        if tuple(n_act_pad.shape) != (n, mf) or seg_begin.numel() != n or n_frontier.numel() != n:
+            raise ValueError("greedy_plans: shapes disagree")
+        score, actions_pad, n_act_pad = score.contiguous(), actions_pad.contiguous(), n_act_pad.contiguous()
+        seg_begin, n_frontier = seg_begin.to(torch.int32).contiguous(), n_frontier.to(torch.int32).contiguous()
+        if active is not None:
+            active = active.to(torch.uint8).contiguous()
+        choice = torch.empty(n, dtype=torch.int32, device=dev)
+        acts = torch.empty(n, A, 3, dtype=torch.float64, device=dev)
+        n_act = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().drlgx_greedy_plans(C.c_void_p(_lib.stream_ptr(dev)), n, _p(score), score.numel(), _p(seg_begin), _p(n_frontier), _p(active),
+                                             _p(actions_pad), _p(n_act_pad), mf, A, _p(choice), _p(acts), _p(n_act)))
+        return choice, acts, n_act
+
     def stage_reset(self, env_ids, seeds, starts):
         env_ids = np.ascontiguousarray(env_ids, dtype=np.int32)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)

@@ -10,6 +10,7 @@ device tensor over environments (or over (environment, frontier) candidates):
     actions_all_goals()  (:134-143)  line plan to every frontier of every env
     rewards_all_goals()  (:145-162)  look-ahead reward of every plan + the per-decision np.interp normalisation / loop_clo
     step(...)            (:98-105)   executes one chosen plan per env (ragged lengths -> active masks)
+    step_traced(...)     the same plans as scripts/test.py:128-152 executes them: a metric row per action, stop at done
     status() / done()    (:164-168, :107-110)
 
 There is no CPU path here: the engine raises if no HIP device is visible.
@@ -75,7 +76,10 @@ class VecExplorationEnv(object):
         self.engine = Engine(self.cfg, n_envs, n_rollouts, device)
         self.device = self.engine.device
         self.np_random = np.random.RandomState(seed)
-        self.env_index = np.arange(n_envs, dtype=np.int64) + int(env_index)  # one TEST seed per env
+        if np.ndim(env_index) == 0:
+            self.env_index = np.arange(n_envs, dtype=np.int64) + int(env_index)  # one TEST seed per env
+        else:  # (the seeds listed one by one)
+            self.env_index = np.array(env_index, dtype=np.int64).reshape(n_envs)
         self._starts = None if starts is None else np.asarray(starts, dtype=np.float64).reshape(n_envs, 3)
         self._max_steps = 5000
         self.dist = torch.zeros(n_envs, dtype=torch.float64, device=self.device)
@@ -220,6 +224,24 @@ class VecExplorationEnv(object):
             self.engine.check_status()
         self._graph = None
         return self._get_obs(), self.done(), {}
+
+    def step_traced(self, acts, nact, kmax=None, sigma0=1.0):
+        """Execute `nact[i]` actions of `acts[i]` in every env the way the reference's evaluation loop does
+        (scripts/test.py:128-152, Engine.step_plans_traced): the metrics of every executed action are recorded and an env leaves
+        its plan behind the action at which done() holds (`explored > 0.85 or step > max_steps`), all on the device.  Returns
+        device tensors (trace [n_envs, max_actions, 4], n_executed [n_envs] i32, done [n_envs] i32) and no synchronisation: the
+        caller reads them - and the status word - with one `engine.fetch`.  kmax: a host bound of nact (None: read from the device)."""
+        if kmax is None:
+            kmax = int(nact.max().item()) if nact.numel() else 0
+        if acts.shape[1] < self.cfg.max_actions:  # drlgx_step_plan strides the plans by the engine's max_actions
+            acts = torch.cat([acts, acts.new_zeros(acts.shape[0], self.cfg.max_actions - acts.shape[1], 3)], dim=1)
+        acts = acts.contiguous()
+        trace, n_exec, done = self.engine.step_plans_traced(acts, nact, min(int(kmax), self.cfg.max_actions), sigma0=sigma0,
+                                                            done_explored=0.85, max_steps=self._max_steps)
+        live = torch.arange(acts.shape[1], device=self.device)[None, :] < n_exec[:, None]  # the EXECUTED actions only
+        self.dist += (torch.sqrt(acts[:, :, 0] ** 2 + acts[:, :, 1] ** 2) * live).sum(dim=1)
+        self._graph = None
+        return trace, n_exec, done
 
     def status(self):
         return self.engine.explored()

@@ -120,6 +120,17 @@ int drlgx_step_plan(drlgx_engine *e, const double *actions_dev, const int32_t *n
  * index; bit-equal either way. */
 int drlgx_step_plans(drlgx_engine *e, const double *actions_dev, const int32_t *n_actions_dev, int max_n_actions,
                      int map_last_only);
+/* The same loop as the reference's evaluation script runs it (scripts/test.py:128-152): per executed action a record of the
+ * metrics, and the episode ends in the MIDDLE of a plan when ExplorationEnv.step reports done.  For every action index a in
+ * [0, max_n_actions): what drlgx_step_plan(e, actions, n_actions, a, 0) launches (the map is rebuilt at every action), then one
+ * record launch: for every env with a < n_actions[e], trace_dev[e][a] = (landmark error, map entropy, max localisation
+ * uncertainty - the bits of drlgx_metrics with this sigma0 -, explored - the bits of drlgx_explored), and when
+ * explored > done_explored || step > max_steps (exploration_env.py:107-110) done_dev[e] = 1 and n_actions_dev[e] = a + 1, so
+ * that the later action indices skip the env without a host round trip.  After the call n_actions_dev (IN and OUT) holds the
+ * number of actions each env executed; rows of trace_dev beyond it are not written.  done_dev is only ever set: the caller
+ * zeroes it.  trace_dev double [n_envs][max_actions][4], done_dev int32 [n_envs]. */
+int drlgx_step_plans_traced(drlgx_engine *e, const double *actions_dev, int32_t *n_actions_dev, int max_n_actions, double sigma0,
+                            double done_explored, int max_steps, double *trace_dev, int32_t *done_dev);
 
 /* ---- staged form of the belief step -----------------------------------------------------------
  * The reference's pybind classes are driven call by call (scripts/envs/pyss2d.py:102-138 SS2D.__init__, :171-206
@@ -548,6 +559,21 @@ int drlgx_segment_softmax_backward(void *hip_stream, int n_graphs, const int32_t
 int drlgx_mean_pool(void *hip_stream, int n_graphs, const int32_t *node_off, const float *h, int n_cols, float *v_out);
 int drlgx_mean_pool_backward(void *hip_stream, int n_graphs, const int32_t *node_off, const float *d_v, int n_cols,
                              float *d_h);
+
+/* ---- evaluation driver --------------------------------------------------------------------------------------------- */
+
+/* The greedy decision of the reference's evaluation loop (scripts/test.py:110-119) for every env, on the device, one wave per
+ * env: choice[e] = np.argmax(score[seg_begin[e] : seg_begin[e] + n_frontier[e]]) - the first maximum, a NaN before every number,
+ * the first NaN - and the line plan to that frontier slot out of the padded plans drlgx_line_plan emits over all
+ * n_envs x max_frontier slots: actions_out[e] = actions_pad[e][choice[e]] with the actions beyond n_act_pad[e][choice[e]]
+ * written as zeros, n_actions_out[e] = that length.  An env with active[e] == 0 (active_dev NULL = all active) or without
+ * frontiers gets choice -1, n_actions_out 0 and a zero plan.  score: float32 [n_score], covering every segment (for DQN the
+ * per-node read-out with seg_begin = node_off[e + 1] - n_frontier[e], for A2C the compact soft-max output with seg_begin = the
+ * exclusive prefix sum of n_frontier).  actions_pad double [n_envs][max_frontier][max_actions][3], n_act_pad int32
+ * [n_envs][max_frontier], actions_out double [n_envs][max_actions][3].  All pointers DEVICE. */
+int drlgx_greedy_plans(void *hip_stream, int n_envs, const float *score, int n_score, const int32_t *seg_begin, const int32_t *n_frontier,
+                       const uint8_t *active_dev, const double *actions_pad, const int32_t *n_act_pad, int max_frontier,
+                       int max_actions, int32_t *choice, double *actions_out, int32_t *n_actions_out);
 
 #ifdef __cplusplus
 }
