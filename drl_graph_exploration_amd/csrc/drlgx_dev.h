@@ -725,9 +725,19 @@ void drlgx_launch_utility(const DrlgxState &S, hipStream_t st, const double *dis
 void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, const int32_t *env_ids, int n_env, double *sig, size_t sig_stride,
                             int n_max);
 size_t drlgx_fm2_scratch_doubles(const DrlgxState &S, int nm_max);
+// flag[0] (zeroed by the caller) = DRLGX_E_INVALID / DRLGX_E_CAPACITY if a candidate names no environment, has more than max_actions
+// actions or more than nm_max predicted measurements
+void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *actions,
+                            const int32_t *n_actions, int nm_max, int *flag);
 void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
                              const double *actions, const int32_t *n_actions, const double *sig, size_t sig_stride, double *scratch,
                              size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride, int32_t *n_out);
+// Leaf evaluation of candidate plans (k_em.hip): nc candidates, one workgroup each; cov = what drlgx_launch_fm2_update left for the
+// same nc candidates ([nc][cov_stride][9]); the candidate arrays and the outputs (any of them null) start at the first of them
+size_t drlgx_em_lds_bytes(const DrlgxState &S);
+void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
+                          const int32_t *n_actions, const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
+                          double *info_out);
 void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, double *out);
 // behind action index a of the chosen plans: the per-action record and the device-side stop at done (k_plan_record)
 void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,

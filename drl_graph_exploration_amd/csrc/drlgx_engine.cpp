@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <unordered_map>
 #include <cstdlib>
@@ -82,6 +83,10 @@ struct drlgx_engine {
   int *fm2_iscratch = nullptr;
   int32_t *fm2_slot = nullptr;
   size_t fm2_sig_stride = 0, fm2_scratch_stride = 0;
+  // drlgx_em_cost (allocated on first use): the covariances and pose counts of one chunk of candidates, the argument check's flag
+  double *em_cov = nullptr;
+  int32_t *em_nout = nullptr;
+  int *em_flag = nullptr;
   // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
   // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
   // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
@@ -932,13 +937,11 @@ int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebui
 
 // FastMarginals2::update for candidate action lists (k_fm2.hip)
 static const int kFm2Chunk = 128, kFm2MaxMeas = 256;
-int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                     double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
-  DRLGX_ENTER(e);
-  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !cov_out_dev || !n_out_dev ||
-      out_stride_poses < e->S.P_max + e->S.A_max)
-    return DRLGX_E_INVALID;
-  if (n_cand == 0) return DRLGX_OK;
+// What both entries below do with their candidates: the workspaces on first use, the prior covariance of every environment, then
+// one update launch per kFm2Chunk candidates.  cov_out / n_out hold all n_cand candidates - or, chunk_out, only the chunk at hand,
+// which after(c0, nc) consumes on the engine's stream before the next chunk's launch overwrites it.
+static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                   double *cov_out, int out_stride_poses, int32_t *n_out, bool chunk_out, const std::function<void(int, int)> &after) {
   const DrlgxState &S = e->S;
   if (!e->fm2_sig) {
     const size_t nmax = (size_t)3 * S.P_max + 2 * S.L_max;
@@ -955,11 +958,59 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
     HIPCHK(e, hipStreamSynchronize(e->stream));
   }
   drlgx_launch_fm2_prior(S, e->stream, nullptr, S.n_envs, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
-  for (int c0 = 0; c0 < n_cand; c0 += kFm2Chunk)
-    drlgx_launch_fm2_update(S, e->stream, c0, std::min(kFm2Chunk, n_cand - c0), cand_env_dev, e->fm2_slot, actions_dev, n_actions_dev,
+  for (int c0 = 0; c0 < n_cand; c0 += kFm2Chunk) {
+    const int nc = std::min(kFm2Chunk, n_cand - c0);
+    // (the launch's first candidate through the pointers: the kernel's own offset stays 0)
+    drlgx_launch_fm2_update(S, e->stream, 0, nc, cand_env_dev + c0, e->fm2_slot, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
                             e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_scratch_stride, e->fm2_iscratch, kFm2MaxMeas,
-                            cov_out_dev, out_stride_poses, n_out_dev);
+                            chunk_out ? cov_out : cov_out + (size_t)c0 * out_stride_poses * 9, out_stride_poses,
+                            chunk_out ? n_out : n_out + c0);
+    after(c0, nc);
+  }
   return check_launch(e);
+}
+
+int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                     double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !cov_out_dev || !n_out_dev ||
+      out_stride_poses < e->S.P_max + e->S.A_max)
+    return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;
+  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, cov_out_dev, out_stride_poses, n_out_dev, false, [](int, int) {});
+}
+
+// The leaf evaluation of EMPlanner2D::optimize2 for candidate action lists: the covariance update above into the engine's scratch,
+// a chunk at a time, and k_em.hip on each chunk.  What the kernels could only report through the status word - a candidate that
+// names no environment, a plan beyond max_actions, more than kFm2MaxMeas predicted measurements - is found out first (one small
+// launch and one read of its flag), so that such a call returns its code and leaves the status word alone.
+int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || (!uncertainty_out_dev && !cost_out_dev) ||
+      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
+    return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;
+  const DrlgxState &S = e->S;
+  if (drlgx_em_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
+  const int stride = S.P_max + S.A_max;
+  if (!e->em_cov) {
+    int r;
+    if ((r = dev_alloc(e, &e->em_cov, (size_t)kFm2Chunk * stride * 9))) return r;
+    if ((r = dev_alloc(e, &e->em_nout, (size_t)kFm2Chunk))) return r;
+    if ((r = dev_alloc(e, &e->em_flag, (size_t)1))) return r;
+  }
+  int flag = 0;
+  HIPCHK(e, hipMemsetAsync(e->em_flag, 0, sizeof(int), e->stream));
+  drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, kFm2MaxMeas, e->em_flag);
+  HIPCHK(e, hipMemcpyAsync(&flag, e->em_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (flag) return flag;
+  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->em_cov, stride, e->em_nout, true, [&](int c0, int nc) {
+    drlgx_launch_em_cost(S, e->stream, nc, cand_env_dev + c0, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0, e->em_cov, stride,
+                         algorithm, uncertainty_out_dev ? uncertainty_out_dev + c0 : nullptr, cost_out_dev ? cost_out_dev + c0 : nullptr,
+                         info_out_dev ? info_out_dev + (size_t)c0 * S.V * 3 : nullptr);
+  });
 }
 
 int drlgx_stage_set_prior_information_host(drlgx_engine *e, int env, const double *information9) {

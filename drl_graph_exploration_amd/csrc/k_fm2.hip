@@ -398,8 +398,45 @@ __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const i
   if (tid == 0 && bad) atomicMin(S.status, DRLGX_E_NUMERIC);
 }
 
+// What k_fm2_update can only report through the status word, found out BEFORE anything is launched that an entry's caller could
+// see: an environment that does not exist, a plan longer than max_actions, more predicted measurements than nm_max.  One thread
+// per candidate walks the same pose chain and the same gates (the expressions of k_fm2_update, in this translation unit: they
+// round alike); flag[0] = the smallest DRLGX_E_* code met (the caller zeroes it).
+__global__ void k_fm2_check(DrlgxState S, int n_cand, const int32_t *cand_env, const double *actions, const int32_t *n_actions, int nm_max,
+                            int *flag) {
+  const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ci >= n_cand) return;
+  const int env = cand_env[ci], K = n_actions[ci];
+  if (env < 0 || env >= S.n_envs || K < 0 || K > S.A_max) {
+    atomicMin(flag, DRLGX_E_INVALID);
+    return;
+  }
+  const drlgx_config &cfg = S.cfg;
+  const int *cnt = S.cnt + (size_t)env * DRLGX_CNT_STRIDE;
+  const int P = cnt[C_P], L = cnt[C_L];
+  const double *ep = S.est_pose + (size_t)env * S.P_max * 4, *el = S.est_lm + (size_t)env * S.L_max * 2;
+  Pose origin{ep[4 * (P - 1)], ep[4 * (P - 1) + 1], ep[4 * (P - 1) + 2], ep[4 * (P - 1) + 3]};
+  int nm = 0;
+  for (int b = 0; b < K; ++b) {
+    const double *a = actions + ((size_t)ci * S.A_max + b) * 3;
+    const Pose ps = compose(origin, make_pose(a[0], a[1], a[2]));
+    for (int j = 0; j < L; ++j) {
+      const P2 lm{el[2 * j], el[2 * j + 1]};
+      const double dx = lm.x - ps.x, dy = lm.y - ps.y, rng = sqrt(dx * dx + dy * dy);
+      const double bearing = bearing_of<false>(ps, lm, nullptr, nullptr);
+      nm += (rng < cfg.max_range && rng > cfg.min_range && bearing < cfg.max_bearing && bearing > cfg.min_bearing) ? 1 : 0;
+    }
+    origin = ps;
+  }
+  if (nm > nm_max) atomicMin(flag, DRLGX_E_CAPACITY);
+}
+
 }  // namespace kfm2
 
+void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *actions,
+                            const int32_t *n_actions, int nm_max, int *flag) {
+  hipLaunchKernelGGL(kfm2::k_fm2_check, dim3((n_cand + 63) / 64), dim3(64), 0, st, S, n_cand, cand_env, actions, n_actions, nm_max, flag);
+}
 void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, const int32_t *env_ids, int n_env, double *sig, size_t sig_stride,
                             int n_max) {
   hipLaunchKernelGGL(kfm2::k_fm2_prior, dim3(n_env), dim3(kfm2::kT), 2 * (size_t)n_max * sizeof(double), st, S, env_ids, n_env, sig,

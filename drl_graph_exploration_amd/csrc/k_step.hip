@@ -25,6 +25,7 @@
 #include "k_slam_arrow.hip"   // pose-chain solver: arrow_body, k_slam_arrow (+ k_sweep_ws.hip, its workspace sweep)
 #include "k_slam_host.hip"    // LDS / workspace sizing, drlgx_launch_slam
 #include "k_map.hip"
+#include "k_em.hip"          // leaf evaluation of candidate plans (kmap's device functions, this unit's -ffp-contract=off)
 
 namespace kstep {
 

@@ -244,6 +244,19 @@ class Engine(object):
         self._chk(self.L.drlgx_fm2_update(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(cov), stride, _p(n_out)))
         return cov, n_out
 
+    def em_cost(self, cand_env, actions, n_actions, algorithm=0, want_info=False):
+        """Expected look-ahead cost of candidate plans (drlgx_em_cost: the leaf evaluation of EMPlanner2D::optimize2, without
+        simulating or re-solving): returns (uncertainty [C], cost [C]) float64 and, with `want_info`, the leaf virtual map's
+        information [C, rows, cols, 3] (xx, xy, yy).  cand_env [C] i32, actions [C, max_actions, 3] f64, n_actions [C] i32 on the
+        device; algorithm 0 = EM_AOPT, 1 = EM_DOPT."""
+        self.use_torch_stream()
+        n = cand_env.numel()
+        unc = torch.empty(n, dtype=torch.float64, device=self.device)
+        cost = torch.empty(n, dtype=torch.float64, device=self.device)
+        info = torch.empty(n, self.rows, self.cols, 3, dtype=torch.float64, device=self.device) if want_info else None
+        self._chk(self.L.drlgx_em_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), int(algorithm), _p(unc), _p(cost), _p(info)))
+        return (unc, cost, info) if want_info else (unc, cost)
+
     def utility(self, dist=None):
         self.use_torch_stream()
         out = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)

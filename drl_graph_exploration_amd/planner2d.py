@@ -58,7 +58,8 @@ class DubinsParameter(object):
 class EMPlanner2D(object):
     """`EMPlanner2D(parameter, sensor_model, control_model)` (src/Planner2D.cpp:73-91) over the engine that the models'
     simulation owns: the calls the DRL scripts make - `calculate_utility` (static), `line_planner`, `simulations_reward` -
-    run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`.  The sampling planners (`optimize`, `optimize2`,
+    run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`; `leaf_cost` is the leaf evaluation of `optimize2`
+    (`drlgx_em_cost`) for an action list the caller supplies.  The sampling planners (`optimize`, `optimize2`,
     `rrt_planner`, the Dubins library) are outside the accelerated path (out of scope)."""
     OptimizationAlgorithm = OptimizationAlgorithm
     OptimizationResult = OptimizationResult
@@ -121,6 +122,26 @@ class EMPlanner2D(object):
         r = float(e.lookahead(ce, acts.to(e.device), n)[0])
         e.check_status()
         return r
+
+    def leaf_cost(self, slam, virtual_map, actions, return_uncertainty=False):
+        """The leaf evaluation of EMPlanner2D::optimize2 (Planner2D.cpp:1095-1104) for ONE action list of the wrapped
+        simulation: updateTrajectory_EM (the FastMarginals2 covariance update, no re-solve), VirtualMap::updateInformation on a
+        copy of the root's virtual map, node->uncertainty = calculateUncertainty_EM, node->cost = costFunction - the expected cost
+        of the plan with the parameter's algorithm, without simulating it and without noise (`drlgx_em_cost`).  The live
+        objects are not modified.  The sampler that builds optimize2's tree stays out of scope: `optimize2` itself raises."""
+        import torch
+        e = self._ses.require_engine()
+        A = e.cfg.max_actions
+        if len(actions) > A:
+            raise ValueError("plan longer than the engine's max_actions")
+        acts = torch.zeros(1, A, 3, dtype=torch.float64)
+        for k, a in enumerate(actions):
+            acts[0, k] = torch.tensor([a.x, a.y, a.theta] if hasattr(a, "x") else list(a), dtype=torch.float64)
+        n = torch.tensor([len(actions)], dtype=torch.int32, device=e.device)
+        ce = torch.zeros(1, dtype=torch.int32, device=e.device)
+        unc, cost = e.em_cost(ce, acts.to(e.device), n, int(self._parameter.algorithm))
+        e.check_status()
+        return (float(cost[0]), float(unc[0])) if return_uncertainty else float(cost[0])
 
     def _out_of_scope(self, *a, **k):
         raise NotImplementedError("sampling planners (EM / RRT / Dubins) are outside the accelerated path")

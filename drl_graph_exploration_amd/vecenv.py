@@ -176,10 +176,21 @@ class VecExplorationEnv(object):
         (self._n_act_h,) = self.engine.fetch(self._n_act)
         return self._actions, self._n_act
 
-    def rewards_all_goals(self, all_actions=None, return_raw=False):
+    def rewards_all_goals(self, all_actions=None, return_raw=False, lookahead="sim"):
         """Look-ahead reward per candidate, normalised per env like exploration_env.py:151-161:
-        nearest frontier is the arg-max -> interp to [-1, 0], loop_clo False; else [-1, 1], loop_clo True."""
+        nearest frontier is the arg-max -> interp to [-1, 0], loop_clo False; else [-1, 1], loop_clo True.
+        lookahead="sim": the stochastic look-ahead (EMPlanner2D::simulations_reward, drlgx_lookahead).  "em": the deterministic
+        expected cost instead - raw = the root's uncertainty (Engine.uncertainty_em) minus the leaf's cost (Engine.em_cost, the
+        leaf evaluation of optimize2) with the planner parameter's algorithm: the sign convention of U_before - U_after."""
+        if lookahead not in ("sim", "em"):
+            raise ValueError("lookahead must be 'sim' or 'em', not %r" % (lookahead,))
         actions, n_act = all_actions if all_actions is not None else (self._actions, self._n_act)
+        if lookahead == "em":
+            alg = int(self.cfg.algorithm)
+            _, cost = self.engine.em_cost(self._cand_env, actions, n_act, alg)
+            raw = self.engine.uncertainty_em(alg)[self._cand_env.long()] - cost
+            r, self.loop_clo = normalise_rewards(raw, self._cand_env.long(), self._cand_first, self.n_envs, self._graph["n_frontier"])
+            return (r, raw) if return_raw else r
         n_act_h = self._n_act_h if all_actions is None else None
         if n_act_h is not None:
             kmax = max(int(n_act_h.max()), 1) if n_act_h.size else 1

@@ -177,6 +177,28 @@ int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebui
  * measurements per candidate (DRLGX_E_CAPACITY beyond). */
 int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                      double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev);
+/* The leaf evaluation of EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1095-1104) for n_cand candidates (environment,
+ * action list) the caller supplies - the sampler that builds the tree is not part of this library:
+ *   updateTrajectory_EM (:472-551): the covariances of drlgx_fm2_update; every pose becomes a core pose of the leaf's map with
+ *     information = cov^-1 (:521-523), the old ones at the current estimate (:1288), one per action at the noise-free predicted pose;
+ *   VirtualMap::updateInformation on a copy of the root's virtual map (:1100-1101; VirtualMap.cpp:256-316, :213-229, :364-378):
+ *     every cell back to I / sigma0^2, the poses in trajectory order, first hit replaces, later hits are fused by covariance
+ *     intersection; the cells' probabilities stay the live environment's;
+ *   calculateUncertainty_EM (:321-341): sum_v 1[p_v > 0.49] tr(info_v^-1) (DRLGX_ALG_EM_AOPT) or sum_v 1[p_v > 0.49] / det(info_v)
+ *     (DRLGX_ALG_EM_DOPT);
+ *   costFunction (:418-420) = uncertainty + distance * distance_weight, distance_weight = w0 - (w0 - w1) #{p_v <
+ *     occupancy_threshold} / V (:1322-1332), distance = sum_k sqrt(x_k^2 + y_k^2 + angle_weight theta_k^2) as drlgx_lookahead
+ *     accumulates it (:1440).
+ * A plan is ranked by that scalar without simulating it, without noise and without re-solving; live environments are not modified.
+ * cand_env_dev int32[n_cand] (several candidates may name one environment); actions_dev double[n_cand*max_actions*3];
+ * n_actions_dev int32[n_cand], 0 <= n <= max_actions; uncertainty_out_dev / cost_out_dev: DEVICE double[n_cand], either may be NULL
+ * but not both; info_out_dev: DEVICE double[n_cand*V*3] (xx, xy, yy per cell, row-major grid: the leaf virtual map's information) or
+ * NULL.  Any n_cand >= 0.  DRLGX_E_INVALID: a bad algorithm, both outputs NULL, a candidate that names no environment or has more
+ * than max_actions actions; DRLGX_E_CAPACITY: more than 256 predicted measurements in one candidate.  The candidates are checked
+ * before anything else is launched (one read of a device flag: this call synchronises once); a refused call leaves the status word
+ * alone. */
+int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev);
 
 /* Simulator2D::addLandmarks(landmarks, num_random, params) with a non-empty list (Simulator2D.cpp:445-464; the ini file's
  * optional [Landmarks] section, scripts/envs/pyss2d.py:107-115): the n_fixed listed points take the ground-truth keys
