@@ -738,6 +738,20 @@ size_t drlgx_em_lds_bytes(const DrlgxState &S);
 void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
                           const int32_t *n_actions, const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
                           double *info_out);
+// The EM planner's tree sampler (k_em_tree.hip): one tree per selected environment, grown from its live belief, which is only read.
+// mode 0: optimize2's stop rule (max_nodes: the planner parameter), 1: rrt_planner's (goal_key / goal_xy).  Per-tree scratch, cap
+// nodes each: act [cap][3] edge odometry, link [cap][2] parent and depth, leaf [cap] the leaves in node order; meta [4] = nodes,
+// leaves, next Halton index, OptimizationResult.  flag[0] (zeroed by the caller): DRLGX_E_INVALID / DRLGX_E_CAPACITY.
+size_t drlgx_em_tree_lds_bytes(int cap);
+void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
+                          int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy, double *act, int *link, int *leaf,
+                          int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out);
+// the action lists root -> leaf in drlgx_em_cost's candidate layout; per_tree_row: row ti of the outputs instead of the running count
+void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
+                            const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions);
+// per tree the first leaf with the strictly smallest cost
+void drlgx_launch_em_pick(hipStream_t st, int n_sel, int A_max, const int *meta, const double *cost, const double *actions,
+                          const int32_t *n_actions, double *plan_out, int32_t *n_actions_out, double *cost_out, int32_t *n_leaves_out);
 void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, double *out);
 // behind action index a of the chosen plans: the per-action record and the device-side stop at done (k_plan_record)
 void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,

@@ -87,6 +87,14 @@ struct drlgx_engine {
   double *em_cov = nullptr;
   int32_t *em_nout = nullptr;
   int *em_flag = nullptr;
+  // drlgx_em_plan / drlgx_rrt_plan (grown on demand): the trees' tables (edge odometry, parent and depth, leaf list, per-tree
+  // results), the leaves as candidates of drlgx_em_cost with their costs; the sampler's own planner parameters
+  double *tree_act = nullptr, *tree_cand_act = nullptr, *tree_cost = nullptr;
+  int *tree_link = nullptr, *tree_leaf = nullptr, *tree_meta = nullptr;
+  int32_t *tree_cand_env = nullptr, *tree_cand_n = nullptr;
+  size_t tree_nodes_cap = 0, tree_sel_cap = 0, tree_cand_cap = 0;
+  double sampler_max_nodes = 0.5, sampler_safe_distance = 0.0;
+  int sampler_dubins = 0;
   // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
   // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
   // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
@@ -984,13 +992,8 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
 // a chunk at a time, and k_em.hip on each chunk.  What the kernels could only report through the status word - a candidate that
 // names no environment, a plan beyond max_actions, more than kFm2MaxMeas predicted measurements - is found out first (one small
 // launch and one read of its flag), so that such a call returns its code and leaves the status word alone.
-int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
-  DRLGX_ENTER(e);
-  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || (!uncertainty_out_dev && !cost_out_dev) ||
-      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
-    return DRLGX_E_INVALID;
-  if (n_cand == 0) return DRLGX_OK;
+static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                       int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
   const DrlgxState &S = e->S;
   if (drlgx_em_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
   const int stride = S.P_max + S.A_max;
@@ -1011,6 +1014,128 @@ int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
                          algorithm, uncertainty_out_dev ? uncertainty_out_dev + c0 : nullptr, cost_out_dev ? cost_out_dev + c0 : nullptr,
                          info_out_dev ? info_out_dev + (size_t)c0 * S.V * 3 : nullptr);
   });
+}
+
+int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || (!uncertainty_out_dev && !cost_out_dev) ||
+      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
+    return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;
+  return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, algorithm, uncertainty_out_dev, cost_out_dev, info_out_dev);
+}
+
+// ---- the EM planner's tree sampler (k_em_tree.hip) ----
+static const int kTreeMaxNodes = 2048, kTreeMeta = 4;
+
+int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_distance, int dubins_control_model_enabled) {
+  DRLGX_ENTER(e);
+  if (!e || !(max_nodes >= 0.0)) return DRLGX_E_INVALID;
+  e->sampler_max_nodes = max_nodes;
+  e->sampler_safe_distance = safe_distance;
+  e->sampler_dubins = dubins_control_model_enabled ? 1 : 0;
+  return DRLGX_OK;
+}
+
+// a scratch array of at least `count` elements: kept while it is large enough, replaced (behind the stream's work) when it is not
+extern "C++" {
+template <typename T>
+static int scratch_reserve(drlgx_engine *e, T **p, size_t count) {
+  if (*p) {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void *)*p), e->allocs.end());
+    HIPCHK(e, hipFree(*p));
+    *p = nullptr;
+  }
+  return dev_alloc(e, p, count);
+}
+}
+
+// Grows the trees and reads their results back: meta_h[n_sel][kTreeMeta] and the flag - the one synchronisation.  Returns the
+// flag's code when a tree was refused.
+static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int cap, int mode,
+                     const int32_t *goal_key_dev, const double *goal_xy_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev,
+                     int32_t *result_out_dev, int32_t *halton_next_out_dev, std::vector<int> &meta_h) {
+  int r;
+  if ((size_t)n_sel > e->tree_sel_cap) {
+    if ((r = scratch_reserve(e, &e->tree_meta, (size_t)n_sel * kTreeMeta + 1))) return r;  // (+ the flag, behind the trees' rows)
+    e->tree_sel_cap = (size_t)n_sel;
+    e->tree_nodes_cap = 0;
+  }
+  const size_t nodes = (size_t)n_sel * cap;
+  if (nodes > e->tree_nodes_cap) {
+    if ((r = scratch_reserve(e, &e->tree_act, nodes * 3))) return r;
+    if ((r = scratch_reserve(e, &e->tree_link, nodes * 2))) return r;
+    if ((r = scratch_reserve(e, &e->tree_leaf, nodes))) return r;
+    e->tree_nodes_cap = nodes;
+  }
+  int *flag_dev = e->tree_meta + (size_t)n_sel * kTreeMeta;
+  HIPCHK(e, hipMemsetAsync(flag_dev, 0, sizeof(int), e->stream));
+  drlgx_launch_em_tree(e->S, e->stream, n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, goal_key_dev, goal_xy_dev,
+                       e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev, nodes_out_dev, n_nodes_out_dev, result_out_dev,
+                       halton_next_out_dev);
+  if ((r = check_launch(e))) return r;
+  meta_h.resize((size_t)n_sel * kTreeMeta + 1);
+  HIPCHK(e, hipMemcpyAsync(meta_h.data(), e->tree_meta, meta_h.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return meta_h.back();
+}
+
+static bool tree_args_ok(const drlgx_engine *e, int n_sel, const void *env_sel, const void *halton_start, int cap, const void *plan_out,
+                         const void *n_actions_out) {
+  return e && n_sel >= 0 && env_sel && halton_start && plan_out && n_actions_out && cap >= 1 && cap <= kTreeMaxNodes &&
+         e->sampler_safe_distance == 0.0 && !e->sampler_dubins;
+}
+
+int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                  int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
+                  int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
+  DRLGX_ENTER(e);
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev) ||
+      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
+    return DRLGX_E_INVALID;
+  if (n_sel == 0) return DRLGX_OK;
+  const DrlgxState &S = e->S;
+  std::vector<int> meta;
+  int r = tree_grow(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, 0, nullptr, nullptr, nodes_out_dev, n_nodes_out_dev,
+                    result_out_dev, halton_next_out_dev, meta);
+  if (r) return r;
+  size_t n_cand = 0;
+  for (int i = 0; i < n_sel; ++i) n_cand += (size_t)meta[(size_t)i * kTreeMeta + 1];
+  if (n_cand > (size_t)0x7fffffff) return DRLGX_E_CAPACITY;
+  if (n_cand > e->tree_cand_cap) {
+    if ((r = scratch_reserve(e, &e->tree_cand_act, n_cand * S.A_max * 3))) return r;
+    if ((r = scratch_reserve(e, &e->tree_cand_env, n_cand))) return r;
+    if ((r = scratch_reserve(e, &e->tree_cand_n, n_cand))) return r;
+    if ((r = scratch_reserve(e, &e->tree_cost, n_cand))) return r;
+    e->tree_cand_cap = n_cand;
+  }
+  drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 0,
+                         e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
+  if ((r = check_launch(e))) return r;
+  if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, algorithm, nullptr, e->tree_cost, nullptr)))
+    return r;
+  drlgx_launch_em_pick(e->stream, n_sel, S.A_max, e->tree_meta, e->tree_cost, e->tree_cand_act, e->tree_cand_n, plan_out_dev,
+                       n_actions_out_dev, cost_out_dev, n_leaves_out_dev);
+  return check_launch(e);
+}
+
+int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *goal_key_dev, const double *goal_xy_dev,
+                   const int32_t *halton_start_dev, int max_tree_nodes, double *plan_out_dev, int32_t *n_actions_out_dev,
+                   int32_t *result_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
+  DRLGX_ENTER(e);
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev) || !goal_key_dev ||
+      !goal_xy_dev)
+    return DRLGX_E_INVALID;
+  if (n_sel == 0) return DRLGX_OK;
+  std::vector<int> meta;
+  int r = tree_grow(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, 1, goal_key_dev, goal_xy_dev, nodes_out_dev, n_nodes_out_dev,
+                    result_out_dev, halton_next_out_dev, meta);
+  if (r) return r;
+  drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 1,
+                         nullptr, plan_out_dev, n_actions_out_dev);
+  return check_launch(e);
 }
 
 int drlgx_stage_set_prior_information_host(drlgx_engine *e, int env, const double *information9) {

@@ -1,0 +1,407 @@
+// The EM planner's tree sampler: the growth loop that EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1058-1092) and
+// EMPlanner2D::rrt_planner (:866-922) share, for the non-Dubins control model at safe_distance = 0 (isSafe is then always true and
+// the `failed > 1000` counters cannot fire) -
+//   initialize (:1281-1357)      root = the current pose estimate, distance 0; max_nodes_ = floor(#{p_v < occupancy_threshold} max_nodes)
+//   sampleNode (:101-125)        Halton point number count++ in bases 2, 3, 5: x, y over the MAP's box, theta = 2 pi h2
+//   nearestNode (:267-276, Distance.cpp:5-9, :24-35)   arg-min of range^2 + (angle_weight bearing)^2, the bearing taken from the tree
+//                                node's frame to the sample's position; strict <, so the lowest node index wins a tie
+//   connectNode (:188-216, :250-258)   angle = relative bearing of the sample in the parent's frame, len = min(d, max_edge_length),
+//                                child = parent * Pose2(angle, (len cos, len sin)), edge odometry (len cos angle, len sin angle, angle),
+//                                distance = parent.distance + sqrt(sqDistanceBetweenPoses(child, parent, angle_weight))
+// and the two stop rules: optimize2 stops after max_nodes_ accepted nodes; rrt_planner stops when a new node lies within
+// max_edge_length of the goal Pose2(gx, gy, pi) (isReached, :88-99) and then connects the goal to that node.
+//
+// The chain of accepted nodes is strictly sequential - node k + 1 is attached to the nearest of nodes 0 .. k - and the only parallel
+// work per sample is that arg-min.  ONE WAVE owns a tree: the node table (x y c s distance | parent depth children) lives in LDS,
+// lanes stride over the nodes and reduce (distance, index) by butterfly with the lowest index on equal distance, every lane then
+// holds the winner and computes the same child; lane 0 stores it.  A single wave needs no cross-wave exchange per sample (a
+// 256-thread workgroup pays two barriers and an LDS round per sample to save at most three strides of the arg-min at a few hundred
+// nodes; DESIGN.md section 4 has the comparison).  Every loop is bounded by the node capacity `cap`: each turn of the growth loop
+// accepts exactly one node, so a tree that cannot finish ends with a capacity result instead of spinning.
+//
+// The live belief is only read.  Built with -ffp-contract=off: the nearest-node comparison is a gate.
+#include "drlgx_dev.h"
+
+#ifndef DRLGX_EM_TREE_THREADS
+#define DRLGX_EM_TREE_THREADS 64
+#endif
+
+namespace kemt {
+
+constexpr int kT = DRLGX_EM_TREE_THREADS;
+constexpr int kWaves = kT / 64;
+constexpr int kNd = 5, kNi = 3;  // per node: x y c s distance | parent depth children
+constexpr int kNodeOut = 8;      // doubles per node of nodes_out
+enum { M_NODES = 0, M_LEAVES = 1, M_HALTON = 2, M_RESULT = 3, M_STRIDE = 4 };
+enum { R_SAMPLING_FAILURE = 0, R_SUCCESS = 3 };  // EMPlanner2D::OptimizationResult
+
+__host__ __device__ inline size_t lds_bytes(int cap) {
+  return (size_t)cap * (kNd * sizeof(double) + kNi * sizeof(int)) + 2 * kWaves * sizeof(double) + 64;
+}
+
+// Radical inverse of `index` in `base`: sum_k d_k base^-(k+1) over ALL digits d_k of the index (the Halton sequence's definition).
+// 32 digits cover every int in base 2.
+__device__ __forceinline__ double radical_inverse(int index, int base) {
+  double f = 1.0, r = 0.0;
+  for (int k = 0; k < 32 && index > 0; ++k) {
+    f = f / (double)base;
+    r = r + f * (double)(index % base);
+    index /= base;
+  }
+  return r;
+}
+
+// sqDistanceBetweenPoses(pose1, pose2 at pt, angle_weight) (Distance.cpp:5-9)
+__device__ __forceinline__ double sq_distance(const Pose &p1, const P2 &pt, double angle_weight, double &bearing) {
+  const double range = range_of<false>(p1, pt, nullptr, nullptr);
+  bearing = bearing_of<false>(p1, pt, nullptr, nullptr);
+  const double wb = bearing * angle_weight;
+  return range * range + wb * wb;
+}
+
+// (distance, index) of the whole workgroup's minimum, lowest index on equal distance, in every thread
+__device__ __forceinline__ void argmin_all(double &d, int &idx, double *red_d, int *red_i) {
+  for (int m = 1; m < 64; m <<= 1) {
+    const double od = __shfl_xor(d, m, 64);
+    const int oi = __shfl_xor(idx, m, 64);
+    if (od < d || (od == d && oi < idx)) {
+      d = od;
+      idx = oi;
+    }
+  }
+  if (kWaves > 1) {
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();  // (the previous round's readers are done)
+    if ((threadIdx.x & 63) == 0) {
+      red_d[wave] = d;
+      red_i[wave] = idx;
+    }
+    __syncthreads();
+    d = red_d[0];
+    idx = red_i[0];
+    for (int w = 1; w < kWaves; ++w)
+      if (red_d[w] < d || (red_d[w] == d && red_i[w] < idx)) {
+        d = red_d[w];
+        idx = red_i[w];
+      }
+  }
+}
+
+// mode 0: optimize2's stop rule; 1: rrt_planner's.  goal_key / goal_xy: mode 1 only.  nodes_out (null: not wanted): per tree
+// [cap][8] = x y theta parent distance | the edge odometry from the parent (x y theta).  flag[0] (zeroed by the caller): the smallest DRLGX_E_* code any tree met.
+__global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
+                                                int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy,
+                                                double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out,
+                                                int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out) {
+  extern __shared__ __attribute__((aligned(16))) double tree_smem[];
+  const int tid = threadIdx.x, lane = tid & 63, ti = blockIdx.x;
+  if (ti >= n_sel) return;
+  const int env = env_sel[ti];
+  int *mt = meta + (size_t)ti * M_STRIDE;
+  if (env < 0 || env >= S.n_envs) {
+    if (tid == 0) {
+      atomicMin(flag, DRLGX_E_INVALID);
+      mt[M_NODES] = mt[M_LEAVES] = 0;
+    }
+    return;
+  }
+  const drlgx_config &cfg = S.cfg;
+  const int *cnt = S.cnt + (size_t)env * DRLGX_CNT_STRIDE;
+  const int P = cnt[C_P], L = cnt[C_L];
+  if (P < 1 || P > S.P_max || L < 0 || L > S.L_max || cap < 1) {
+    if (tid == 0) {
+      atomicMin(flag, DRLGX_E_INVALID);
+      mt[M_NODES] = mt[M_LEAVES] = 0;
+    }
+    return;
+  }
+  double *nd = tree_smem;                                  // [cap][kNd]
+  double *red_d = nd + (size_t)cap * kNd;                  // [kWaves]
+  int *ni = reinterpret_cast<int *>(red_d + 2 * kWaves);   // [cap][kNi]
+  int *red_i = reinterpret_cast<int *>(red_d + kWaves);    // [kWaves]
+  const double *ep = S.est_pose + (size_t)env * S.P_max * 4;
+  const double *el = S.est_lm + (size_t)env * S.L_max * 2;
+  double *ta = act + (size_t)ti * cap * 3;
+
+  // ---- initialize: the root, max_nodes_ ----
+  int budget = 0x7fffffff;  // accepted nodes the stop rule allows
+  if (mode == 0) {
+    const double *prob = S.vm_prob + (size_t)env * S.V;
+    int known = 0;
+    for (int v = tid; v < S.V; v += kT) known += prob[v] < cfg.occupancy_threshold ? 1 : 0;
+    double kd = (double)known;
+    for (int m = 1; m < 64; m <<= 1) kd += __shfl_xor(kd, m, 64);
+    if (kWaves > 1) {
+      __syncthreads();
+      if (lane == 0) red_d[tid >> 6] = kd;
+      __syncthreads();
+      kd = 0.0;
+      for (int w = 0; w < kWaves; ++w) kd += red_d[w];
+      __syncthreads();
+    }
+    const double mn = floor(kd * max_nodes);
+    budget = mn < 0.0 ? 0 : (mn > 2147483647.0 ? 0x7fffffff : (int)mn);
+  }
+  P2 goal{0.0, 0.0};
+  if (mode == 1) {
+    // the goal: graph node goal_key (landmarks in key order, then poses - the order of the exported graph) or the frontier point
+    const int gk = goal_key[ti];
+    goal = P2{goal_xy[2 * ti], goal_xy[2 * ti + 1]};
+    if (gk >= 0 && gk < L) {
+      const int *lk = S.lm_key + (size_t)env * S.L_max;
+      int slot = 0x7fffffff;  // the slot whose key has rank gk
+      for (int j = lane; j < L; j += 64) {
+        int rank = 0;
+        for (int q = 0; q < L; ++q) rank += lk[q] < lk[j] ? 1 : 0;
+        if (rank == gk) slot = min(slot, j);
+      }
+      for (int m = 1; m < 64; m <<= 1) slot = min(slot, __shfl_xor(slot, m, 64));
+      if (slot < L) goal = P2{el[2 * slot], el[2 * slot + 1]};
+    } else if (gk >= L && gk < L + P) {
+      goal = P2{ep[4 * (gk - L)], ep[4 * (gk - L) + 1]};
+    }
+  }
+  if (tid == 0) {
+    nd[0] = ep[4 * (P - 1)]; nd[1] = ep[4 * (P - 1) + 1]; nd[2] = ep[4 * (P - 1) + 2]; nd[3] = ep[4 * (P - 1) + 3];
+    nd[4] = 0.0;
+    ni[0] = -1; ni[1] = 0; ni[2] = 0;
+    ta[0] = ta[1] = ta[2] = 0.0;
+  }
+  __syncthreads();
+
+  // ---- growth: one accepted node per turn ----
+  const double span_x = cfg.map_max_x - cfg.map_min_x, span_y = cfg.map_max_y - cfg.map_min_y;
+  int n = 1, count = halton_start[ti], max_depth = 0, goal_node = -1;
+  bool full = false;  // the table filled before the stop rule was met
+  for (int turn = 0; turn < cap; ++turn) {
+    if (mode == 0 && n - 1 >= budget) break;
+    if (n >= cap) {
+      full = true;
+      break;
+    }
+    // sampleNode.  (The sample's own heading, theta = 2 pi h2 with h2 the radical inverse in base 5, enters nothing at
+    // safe_distance = 0 - nearestNode and connectNode read the sample's position only, the child's heading is the parent's plus the
+    // bearing - so the third coordinate of the point is not evaluated; the point is consumed all the same.)
+    const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
+    ++count;
+    const P2 sp{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+    // nearestNode
+    double best = __builtin_huge_val();
+    int bi = 0x7fffffff;
+    for (int j = tid; j < n; j += kT) {
+      const Pose pj{nd[kNd * j], nd[kNd * j + 1], nd[kNd * j + 2], nd[kNd * j + 3]};
+      double b;
+      const double dj = sq_distance(pj, sp, cfg.angle_weight, b);
+      if (dj < best) {
+        best = dj;
+        bi = j;
+      }
+    }
+    argmin_all(best, bi, red_d, red_i);
+    if (bi < 0 || bi >= n) bi = 0;  // (only a NaN distance to every node could leave no winner)
+    // connectNode, every thread alike
+    const Pose par{nd[kNd * bi], nd[kNd * bi + 1], nd[kNd * bi + 2], nd[kNd * bi + 3]};
+    const double pdist = nd[kNd * bi + 4];
+    const int pdepth = ni[kNi * bi + 1];
+    const double d = range_of<false>(par, sp, nullptr, nullptr);
+    const double angle = bearing_of<false>(par, sp, nullptr, nullptr);
+    const double len = d > cfg.max_edge_length ? cfg.max_edge_length : d;
+    const double ax = len * cos(angle), ay = len * sin(angle);
+    const Pose child = compose(par, make_pose(ax, ay, angle));
+    double bb;
+    const double dist = pdist + sqrt(sq_distance(child, P2{par.x, par.y}, cfg.angle_weight, bb));
+    __syncthreads();  // (every thread has read the table)
+    if (tid == 0) {
+      nd[kNd * n] = child.x; nd[kNd * n + 1] = child.y; nd[kNd * n + 2] = child.c; nd[kNd * n + 3] = child.s;
+      nd[kNd * n + 4] = dist;
+      ni[kNi * n] = bi; ni[kNi * n + 1] = pdepth + 1; ni[kNi * n + 2] = 0;
+      ni[kNi * bi + 2] += 1;
+      ta[3 * n] = ax; ta[3 * n + 1] = ay; ta[3 * n + 2] = angle;
+    }
+    __syncthreads();
+    max_depth = max(max_depth, pdepth + 1);
+    ++n;
+    if (mode == 1) {
+      // isReached(goal, node), then connectNode(goal, node): the goal Pose2(gx, gy, pi) becomes a child of the node that reached it
+      const double gx = child.x - goal.x, gy = child.y - goal.y;
+      if (sqrt(gx * gx + gy * gy) <= cfg.max_edge_length) {
+        if (n >= cap) {
+          full = true;
+          break;
+        }
+        const double gd = range_of<false>(child, goal, nullptr, nullptr);
+        const double gang = bearing_of<false>(child, goal, nullptr, nullptr);
+        const double glen = gd > cfg.max_edge_length ? cfg.max_edge_length : gd;
+        const double gax = glen * cos(gang), gay = glen * sin(gang);
+        const Pose gp = compose(child, make_pose(gax, gay, gang));
+        const double gdist = dist + sqrt(sq_distance(gp, P2{child.x, child.y}, cfg.angle_weight, bb));
+        if (tid == 0) {
+          nd[kNd * n] = gp.x; nd[kNd * n + 1] = gp.y; nd[kNd * n + 2] = gp.c; nd[kNd * n + 3] = gp.s;
+          nd[kNd * n + 4] = gdist;
+          ni[kNi * n] = n - 1; ni[kNi * n + 1] = pdepth + 2; ni[kNi * n + 2] = 0;
+          ni[kNi * (n - 1) + 2] += 1;
+          ta[3 * n] = gax; ta[3 * n + 1] = gay; ta[3 * n + 2] = gang;
+        }
+        __syncthreads();
+        goal_node = n;
+        max_depth = pdepth + 2;  // (of the plan: the path to the goal)
+        ++n;
+        break;
+      }
+    }
+  }
+  if (mode == 1 && goal_node < 0) full = true;  // (the turns ran out: the table is full)
+
+  // ---- results: the tables to memory, the leaves in node order ----
+  int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
+  for (int j = tid; j < n; j += kT) {
+    tl[2 * j] = ni[kNi * j];
+    tl[2 * j + 1] = ni[kNi * j + 1];
+    if (nodes_out) {
+      double *o = nodes_out + ((size_t)ti * cap + j) * kNodeOut;
+      o[0] = nd[kNd * j]; o[1] = nd[kNd * j + 1];
+      o[2] = atan2(nd[kNd * j + 3], nd[kNd * j + 2]);
+      o[3] = (double)ni[kNi * j];
+      o[4] = nd[kNd * j + 4];
+      o[5] = ta[3 * j]; o[6] = ta[3 * j + 1]; o[7] = ta[3 * j + 2];
+    }
+  }
+  int n_leaves = 0;
+  if (mode == 0) {
+    if (tid < 64) {  // (one wave lists: node order)
+      for (int base = 0; base < n; base += 64) {
+        const int j = base + lane;
+        const bool is_leaf = j < n && ni[kNi * j + 2] == 0;
+        const unsigned long long b = __ballot(is_leaf);
+        if (is_leaf) lf[n_leaves + __popcll(b & ((1ull << lane) - 1ull))] = j;
+        n_leaves += __popcll(b);
+      }
+    }
+  } else if (goal_node >= 0) {
+    if (tid == 0) lf[0] = goal_node;
+    n_leaves = 1;
+  }
+  if (tid == 0) {
+    const int res = (mode == 1 && full) ? R_SAMPLING_FAILURE : R_SUCCESS;
+    mt[M_NODES] = n;
+    mt[M_LEAVES] = n_leaves;
+    mt[M_HALTON] = count;
+    mt[M_RESULT] = res;
+    if (n_nodes_out) n_nodes_out[ti] = n;
+    if (result_out) result_out[ti] = res;
+    if (halton_next_out) halton_next_out[ti] = count;
+    // what the whole call is refused for: optimize2's tree does not fit the table; a plan deeper than max_actions
+    if ((mode == 0 && full) || ((mode == 0 || goal_node >= 0) && max_depth > S.A_max)) atomicMin(flag, DRLGX_E_CAPACITY);
+  }
+}
+
+// The action lists root -> leaf of every listed leaf, in the [cand][max_actions][3] layout drlgx_em_cost reads (zero behind the
+// plan), with cand_env and n_actions.  Tree ti's first candidate is the sum of the leaf counts before it - or, per_tree_row, row ti
+// (rrt: one plan per tree, none for a tree that failed).
+__global__ __launch_bounds__(64) void k_em_leaves(int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
+                                                  const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions,
+                                                  int32_t *n_actions) {
+  const int ti = blockIdx.x, lane = threadIdx.x;
+  if (ti >= n_sel) return;
+  int off = ti;
+  if (!per_tree_row) {
+    off = 0;
+    for (int q = lane; q < ti; q += 64) off += meta[(size_t)q * M_STRIDE + M_LEAVES];
+    for (int m = 1; m < 64; m <<= 1) off += __shfl_xor(off, m, 64);
+  }
+  const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
+  const double *ta = act + (size_t)ti * cap * 3;
+  const int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
+  if (per_tree_row && nl == 0) {
+    for (int q = lane; q < 3 * A_max; q += 64) actions[(size_t)off * A_max * 3 + q] = 0.0;
+    if (lane == 0) n_actions[off] = 0;
+    return;
+  }
+  for (int k = lane; k < nl; k += 64) {
+    const int node = lf[k], depth = tl[2 * node + 1];
+    const size_t c = (size_t)off + k;
+    double *row = actions + c * A_max * 3;
+    if (cand_env) cand_env[c] = env_sel[ti];
+    n_actions[c] = depth;
+    int j = node;
+    for (int s = depth - 1; s >= 0 && j > 0; --s) {  // (at most depth <= cap - 1 parents)
+      if (s < A_max) {
+        row[3 * s] = ta[3 * j]; row[3 * s + 1] = ta[3 * j + 1]; row[3 * s + 2] = ta[3 * j + 2];
+      }
+      j = tl[2 * j];
+    }
+    for (int s = depth; s < A_max; ++s) row[3 * s] = row[3 * s + 1] = row[3 * s + 2] = 0.0;
+  }
+}
+
+// optimize2's choice (Planner2D.cpp:1095-1111): per tree the first leaf in node order with the strictly smallest cost - the first
+// leaf is always taken, a NaN cost never replaces a held one.  One wave per tree.
+__global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int *meta, const double *cost, const double *actions,
+                                                const int32_t *n_actions, double *plan_out, int32_t *n_actions_out, double *cost_out,
+                                                int32_t *n_leaves_out) {
+  const int ti = blockIdx.x, lane = threadIdx.x;
+  if (ti >= n_sel) return;
+  int off = 0;
+  for (int q = lane; q < ti; q += 64) off += meta[(size_t)q * M_STRIDE + M_LEAVES];
+  for (int m = 1; m < 64; m <<= 1) off += __shfl_xor(off, m, 64);
+  const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
+  double best = __builtin_huge_val();
+  int bi = 0x7fffffff;
+  for (int k = lane; k < nl; k += 64) {
+    const double c = cost[off + k];
+    if (c < best || (c == best && k < bi)) {  // (a NaN compares false: never taken here)
+      best = c;
+      bi = k;
+    }
+  }
+  for (int m = 1; m < 64; m <<= 1) {
+    const double od = __shfl_xor(best, m, 64);
+    const int oi = __shfl_xor(bi, m, 64);
+    if (od < best || (od == best && oi < bi)) {
+      best = od;
+      bi = oi;
+    }
+  }
+  // the first leaf is held whatever its cost: a NaN there is never replaced, an infinite one only by a smaller cost
+  const double c0 = nl > 0 ? cost[off] : 0.0;
+  if (nl > 0 && (c0 != c0 || bi >= nl || !(best < c0))) bi = 0;
+  if (nl <= 0) {
+    if (lane == 0) {
+      n_actions_out[ti] = 0;
+      if (cost_out) cost_out[ti] = 0.0;
+      if (n_leaves_out) n_leaves_out[ti] = 0;
+    }
+    return;
+  }
+  const size_t c = (size_t)off + bi;
+  for (int q = lane; q < 3 * A_max; q += 64) plan_out[(size_t)ti * A_max * 3 + q] = actions[c * A_max * 3 + q];
+  if (lane == 0) {
+    n_actions_out[ti] = n_actions[c];
+    if (cost_out) cost_out[ti] = cost[c];
+    if (n_leaves_out) n_leaves_out[ti] = nl;
+  }
+}
+
+}  // namespace kemt
+
+size_t drlgx_em_tree_lds_bytes(int cap) { return kemt::lds_bytes(cap); }
+
+void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
+                          int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy, double *act, int *link, int *leaf,
+                          int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out) {
+  static bool attr_set[32] = {false};
+  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree)};
+  drlgx_ensure_lds_attr(attr_set, fns, 1, 160 * 1024);
+  hipLaunchKernelGGL(kemt::k_em_tree, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap, mode,
+                     max_nodes, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out, halton_next_out);
+}
+void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
+                            const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions) {
+  hipLaunchKernelGGL(kemt::k_em_leaves, dim3(n_sel), dim3(64), 0, st, n_sel, env_sel, cap, A_max, act, link, leaf, meta, per_tree_row,
+                     cand_env, actions, n_actions);
+}
+void drlgx_launch_em_pick(hipStream_t st, int n_sel, int A_max, const int *meta, const double *cost, const double *actions,
+                          const int32_t *n_actions, double *plan_out, int32_t *n_actions_out, double *cost_out, int32_t *n_leaves_out) {
+  hipLaunchKernelGGL(kemt::k_em_pick, dim3(n_sel), dim3(64), 0, st, n_sel, A_max, meta, cost, actions, n_actions, plan_out, n_actions_out,
+                     cost_out, n_leaves_out);
+}

@@ -257,6 +257,51 @@ class Engine(object):
         self._chk(self.L.drlgx_em_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), int(algorithm), _p(unc), _p(cost), _p(info)))
         return (unc, cost, info) if want_info else (unc, cost)
 
+    def set_sampler_parameter(self, max_nodes, safe_distance=0.0, dubins_control_model_enabled=False):
+        """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
+        control model is stored and then refused by em_plan / rrt_plan."""
+        self._chk(self.L.drlgx_set_sampler_parameter(self.h, float(max_nodes), float(safe_distance), int(bool(dubins_control_model_enabled))))
+
+    def _tree_outputs(self, n, max_tree_nodes, want_nodes):
+        dev, A = self.device, self.cfg.max_actions
+        out = dict(plan=torch.empty(n, A, 3, dtype=torch.float64, device=dev),
+                   n_actions=torch.empty(n, dtype=torch.int32, device=dev),
+                   result=torch.empty(n, dtype=torch.int32, device=dev),
+                   halton_next=torch.empty(n, dtype=torch.int32, device=dev),
+                   n_nodes=torch.empty(n, dtype=torch.int32, device=dev),
+                   nodes=torch.zeros(n, int(max_tree_nodes), 8, dtype=torch.float64, device=dev) if want_nodes else None)
+        return out
+
+    def em_plan(self, env_sel, halton_start, max_tree_nodes=1024, algorithm=0, want_nodes=False):
+        """EMPlanner2D::optimize2 for the listed environments (drlgx_em_plan): one tree per environment grown on the device from
+        Halton point `halton_start[i]` on, its leaves scored by the body of em_cost, the first leaf with the strictly smallest cost
+        taken.  env_sel, halton_start [n] i32 on the device.  Returns a dict of device tensors: plan [n, max_actions, 3] f64 (edge
+        odometry root -> leaf), n_actions, result (OptimizationResult), n_leaves, halton_next, n_nodes [n] i32, cost [n] f64 and,
+        with `want_nodes`, nodes [n, max_tree_nodes, 8] f64 (x y theta parent distance | edge odometry x y theta).  Raises
+        DrlgxError on a refusal (capacity: a tree beyond max_tree_nodes or deeper than cfg.max_actions)."""
+        self.use_torch_stream()
+        n = env_sel.numel()
+        o = self._tree_outputs(n, max_tree_nodes, want_nodes)
+        o["cost"] = torch.empty(n, dtype=torch.float64, device=self.device)
+        o["n_leaves"] = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._chk(self.L.drlgx_em_plan(self.h, n, _p(env_sel), _p(halton_start), int(max_tree_nodes), int(algorithm), _p(o["plan"]),
+                                       _p(o["n_actions"]), _p(o["cost"]), _p(o["result"]), _p(o["n_leaves"]), _p(o["halton_next"]),
+                                       _p(o["nodes"]), _p(o["n_nodes"])))
+        return o
+
+    def rrt_plan(self, env_sel, goal_key, goal_xy, halton_start, max_tree_nodes=1024, want_nodes=False):
+        """EMPlanner2D::rrt_planner for the listed environments (drlgx_rrt_plan): the tree grown until a node lies within
+        max_edge_length of the goal - graph node goal_key[i] if it is one (landmarks in key order, then poses), else the point
+        goal_xy[i] -, the plan the path root -> goal.  A tree that fills max_tree_nodes first has result SAMPLING_FAILURE and
+        no actions.  Returns the dict of em_plan without cost / n_leaves."""
+        self.use_torch_stream()
+        n = env_sel.numel()
+        o = self._tree_outputs(n, max_tree_nodes, want_nodes)
+        self._chk(self.L.drlgx_rrt_plan(self.h, n, _p(env_sel), _p(goal_key), _p(goal_xy), _p(halton_start), int(max_tree_nodes),
+                                        _p(o["plan"]), _p(o["n_actions"]), _p(o["result"]), _p(o["halton_next"]), _p(o["nodes"]),
+                                        _p(o["n_nodes"])))
+        return o
+
     def utility(self, dist=None):
         self.use_torch_stream()
         out = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)

@@ -1,8 +1,38 @@
 """`planner2d` — the module surface of the reference's second pybind module (src/Planner2D.cpp:9-106) that the DRL
 scripts use: the parameter classes and enums, and `EMPlanner2D(parameter, sensor_model, control_model)` with
 `calculate_utility` / `line_planner` / `simulations_reward` over the engine of the simulation the models belong to
-(`ss2d.Simulator2D`).  The RRT / EM / Dubins planners are outside the accelerated path (SURVEY.md §8 "out of scope")."""
+(`ss2d.Simulator2D`), and the tree sampler of the non-Dubins planners: `optimize2`, `rrt_planner`, `iter_solution`
+(`drlgx_em_plan` / `drlgx_rrt_plan`).  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (SURVEY.md §8
+"out of scope")."""
 import enum
+import math
+
+
+def _mt19937_canonical(seed):
+    """The first `std::generate_canonical<double, 53>` of `std::mt19937(seed)`: the single-integer seeding, one twist, two tempered
+    32-bit outputs (the first is the low part) over 2^64."""
+    mt = [0] * 624
+    mt[0] = seed & 0xFFFFFFFF
+    for i in range(1, 624):
+        mt[i] = (1812433253 * (mt[i - 1] ^ (mt[i - 1] >> 30)) + i) & 0xFFFFFFFF
+    for i in range(624):
+        y = (mt[i] & 0x80000000) | (mt[(i + 1) % 624] & 0x7FFFFFFF)
+        mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ (0x9908B0DF if y & 1 else 0)
+
+    def temper(y):
+        y ^= y >> 11
+        y ^= (y << 7) & 0x9D2C5680
+        y ^= (y << 15) & 0xEFC60000
+        return (y ^ (y >> 18)) & 0xFFFFFFFF
+
+    u = (float(temper(mt[0])) + float(temper(mt[1])) * 4294967296.0) / 18446744073709551616.0
+    return u if u < 1.0 else math.nextafter(1.0, 0.0)
+
+
+def halton_start_index(seed):
+    """The Halton index the planner's constructor starts from: `qrng_.setCount(rng_.uniformInt(0, 100000))` with `rng_(seed)`
+    (Planner2D.cpp:36-45, RNG.h:64-77): floor(100001 u), clamped to [0, 100000]."""
+    return min(max(int(math.floor(100001.0 * _mt19937_canonical(int(seed)))), 0), 100000)
 
 
 class OptimizationAlgorithm(enum.IntEnum):
@@ -59,8 +89,11 @@ class EMPlanner2D(object):
     """`EMPlanner2D(parameter, sensor_model, control_model)` (src/Planner2D.cpp:73-91) over the engine that the models'
     simulation owns: the calls the DRL scripts make - `calculate_utility` (static), `line_planner`, `simulations_reward` -
     run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`; `leaf_cost` is the leaf evaluation of `optimize2`
-    (`drlgx_em_cost`) for an action list the caller supplies.  The sampling planners (`optimize`, `optimize2`,
-    `rrt_planner`, the Dubins library) are outside the accelerated path (out of scope)."""
+    (`drlgx_em_cost`) for an action list the caller supplies; `optimize2` and `rrt_planner` grow the sampler's tree on the device
+    (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0) and `iter_solution` walks the best path as the
+    reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
+    call.  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (out of scope)."""
+    MAX_TREE_NODES = 2048  # the node capacity of one tree (the engine's maximum)
     OptimizationAlgorithm = OptimizationAlgorithm
     OptimizationResult = OptimizationResult
 
@@ -69,6 +102,8 @@ class EMPlanner2D(object):
         if self._ses is None or control_model._session is not self._ses:
             raise ValueError("the sensor and control models must come from one Simulator2D")
         self.set_parameter(parameter)
+        self.halton_next = halton_start_index(parameter.seed)
+        self._solution = []
 
     def get_parameter(self):
         return self._parameter
@@ -79,6 +114,7 @@ class EMPlanner2D(object):
         if self._ses.engine is not None:  # (constructed after SLAM2D.add_prior, as pyplanner2d.EMExplorer does)
             self._ses.engine.set_planner_parameter(parameter.angle_weight, parameter.distance_weight0, parameter.distance_weight1,
                                                    parameter.occupancy_threshold, parameter.max_edge_length, int(parameter.algorithm))
+            self._ses.engine.set_sampler_parameter(parameter.max_nodes, parameter.safe_distance, parameter.dubins_control_model_enabled)
 
     @staticmethod
     def calculate_utility(virtual_map, distance, parameter):
@@ -143,7 +179,105 @@ class EMPlanner2D(object):
         e.check_status()
         return (float(cost[0]), float(unc[0])) if return_uncertainty else float(cost[0])
 
-    def _out_of_scope(self, *a, **k):
-        raise NotImplementedError("sampling planners (EM / RRT / Dubins) are outside the accelerated path")
+    def _tree_call(self, run):
+        """One sampler call for the wrapped simulation: the parameter object as it is now, the Halton index carried on, the best
+        path kept for iter_solution."""
+        import torch
+        _require_sampler_scope(self._parameter)
+        e = self._ses.require_engine()
+        self.set_parameter(self._parameter)
+        sel = torch.zeros(1, dtype=torch.int32, device=e.device)
+        start = torch.tensor([self.halton_next], dtype=torch.int32, device=e.device)
+        o = run(e, sel, start)
+        e.check_status()
+        plan, n_act, result, nxt, nodes, n_nodes = e.fetch(o["plan"], o["n_actions"], o["result"], o["halton_next"], o["nodes"], o["n_nodes"])
+        self.halton_next = int(nxt[0])
+        self._solution = _solution_edges(e, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        return OptimizationResult(int(result[0]))
 
-    optimize = optimize2 = rrt_planner = iter_solution = iter_rrt = get_dubins_path = _out_of_scope
+    def optimize2(self, slam, virtual_map):
+        """EMPlanner2D::optimize2 (Planner2D.cpp:1043-1128) for the wrapped simulation (`drlgx_em_plan`)."""
+        alg = int(self._parameter.algorithm)
+        return self._tree_call(lambda e, sel, start: e.em_plan(sel, start, self.MAX_TREE_NODES, alg, want_nodes=True))
+
+    def rrt_planner(self, slam, virtual_map, n_key, fron_0, fron_1):
+        """EMPlanner2D::rrt_planner (Planner2D.cpp:838-935): goal = node `n_key` of the pose graph if it is one, else the frontier
+        point (fron_0, fron_1) (`drlgx_rrt_plan`)."""
+        import torch
+
+        def run(e, sel, start):
+            key = torch.tensor([int(n_key)], dtype=torch.int32, device=e.device)
+            xy = torch.tensor([[float(fron_0), float(fron_1)]], dtype=torch.float64, device=e.device)
+            return e.rrt_plan(sel, key, xy, start, self.MAX_TREE_NODES, want_nodes=True)
+        return self._tree_call(run)
+
+    def iter_solution(self):
+        """The edges of the best path from the best node back to the root (EMPlanner2D::BackwardIterator, Planner2D.h:200-257), each
+        with `first` (the parent node), `second` (the node) and `get_odoms()`; callers insert at the front to get the plan."""
+        return iter(self._solution)
+
+    def _out_of_scope(self, *a, **k):
+        raise NotImplementedError("optimize (RRT*), the Dubins library and iter_rrt are outside the accelerated path")
+
+    optimize = iter_rrt = get_dubins_path = _out_of_scope
+
+
+def _require_sampler_scope(parameter):
+    """The sampler serves the non-Dubins control model at safe_distance = 0 (the engine refuses anything else with
+    DRLGX_E_INVALID); the facades say so the way they say it for everything outside the accelerated path."""
+    if parameter.dubins_control_model_enabled or parameter.safe_distance != 0:
+        raise NotImplementedError("the tree sampler runs for the non-Dubins control model at safe_distance = 0 only "
+                                  "(obstacle logic and Dubins paths are outside the accelerated path)")
+
+
+class Node(object):
+    """EMPlanner2D::Node as the binding shows it (src/Planner2D.cpp:51-60): key, state, poses, distance."""
+
+    def __init__(self, key, pose, distance):
+        from . import ss2d
+        self.key, self.distance = int(key), float(distance)
+        self.state = ss2d.VehicleBeliefState(pose)
+        self.poses = [pose] if key >= 0 else []
+
+
+class Edge(object):
+    """EMPlanner2D::Edge (Planner2D.h:128-152): `get_odoms()` = the odometry from `first` to each pose of `second` - one pose, the
+    edge's action, for the non-Dubins control model."""
+
+    def __init__(self, first, second, odom):
+        self.first, self.second, self._odom = first, second, odom
+
+    def get_odoms(self):
+        return [self._odom]
+
+
+def _solution_edges(engine, plan, nodes):
+    """The best path's edges, leaf first: the path is found by walking the parents of the node whose edges are `plan`."""
+    from . import ss2d
+    if len(plan) == 0:
+        return []
+    root_key = engine.counts(0)["poses"] - 1
+    # the best node: the one whose ancestors' edges are the plan (bit-equal columns 5..7), searched from the back
+    depth = {0: 0}
+    for j in range(1, len(nodes)):
+        depth[j] = depth[int(nodes[j, 3])] + 1
+    best = -1
+    for j in range(len(nodes) - 1, 0, -1):
+        if depth[j] != len(plan):
+            continue
+        k, q = j, len(plan) - 1
+        while k > 0 and (nodes[k, 5:8] == plan[q]).all():
+            k, q = int(nodes[k, 3]), q - 1
+        if k == 0:
+            best = j
+            break
+    if best < 0:
+        raise RuntimeError("the plan is not a path of the returned tree")
+    edges = []
+    j = best
+    while j > 0:
+        par = int(nodes[j, 3])
+        mk = lambda n: Node(root_key + depth[n] if n > 0 else root_key, ss2d.Pose2(nodes[n, 0], nodes[n, 1], nodes[n, 2]), nodes[n, 4])
+        edges.append(Edge(mk(par), mk(j), ss2d.Pose2(nodes[j, 5], nodes[j, 6], nodes[j, 7])))
+        j = par
+    return edges

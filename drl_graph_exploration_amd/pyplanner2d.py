@@ -6,6 +6,7 @@ run on the HIP path one environment at a time; throughput work should use `VecEx
 reference's `ExplorationEnv` touches are provided:
 
     sim.simulate(odom)  sim.calculate_utility(d)  sim.line_plan(goal_key, fro)  sim.simulations_reward(actions)
+    sim.plan()  sim.rrt_plan(goal_key, fro)  sim._planner.iter_solution()
     sim.step  sim.vehicle_position  sim.environment.get_landmark(key)
     sim._slam.key_size() / adjacency_degree_get() / adjacency_out() / features_out() / get_key_points(i)
     sim._slam.map.get_landmark_size() / iter_landmarks() / iter_trajectory() / get_current_vehicle()
@@ -63,6 +64,8 @@ def config_from_ini(cp, max_poses=256, max_actions=None, max_snapshots=1):
         pp.seed = cp.getint("Planner", "seed")
         pp.reg_out = cp.getboolean("Planner", "reg_out")
         pp.algorithm = planner2d.OptimizationAlgorithm[cp.get("Planner", "algorithm")]
+        if cp.has_option("Planner", "dubins_control_model_enabled"):
+            pp.dubins_control_model_enabled = cp.getboolean("Planner", "dubins_control_model_enabled")
     c = DrlgxConfig()
     c.bearing_noise, c.range_noise = sp.bearing_noise, sp.range_noise
     c.min_bearing, c.max_bearing, c.min_range, c.max_range = sp.min_bearing, sp.max_bearing, sp.min_range, sp.max_range
@@ -256,8 +259,61 @@ class SS2D(object):
         return self._slam.map.distance
 
 
+class _Planner(object):
+    """`EMExplorer._planner`: what ExplorationEnv.plan / rrt_plan read after a successful call - `iter_solution()` - and the Halton
+    index that carries on from call to call (started as the reference's constructor starts it)."""
+
+    def __init__(self, owner):
+        self._o = owner
+        self.halton_next = planner2d.halton_start_index(owner._planner_params.seed)
+        self._solution = []
+
+    def _call(self, run):
+        o, pp = self._o, self._o._planner_params
+        planner2d._require_sampler_scope(pp)
+        e = o.engine
+        e.set_sampler_parameter(pp.max_nodes, pp.safe_distance, pp.dubins_control_model_enabled)
+        sel = torch.zeros(1, dtype=torch.int32, device=e.device)
+        start = torch.tensor([self.halton_next], dtype=torch.int32, device=e.device)
+        out = run(e, sel, start)
+        plan, n_act, result, nxt, nodes, n_nodes = e.fetch(out["plan"], out["n_actions"], out["result"], out["halton_next"], out["nodes"],
+                                                           out["n_nodes"])
+        self.halton_next = int(nxt[0])
+        self._solution = planner2d._solution_edges(e, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        self.last = out
+        return planner2d.OptimizationResult(int(result[0]))
+
+    def optimize2(self):
+        cap = planner2d.EMPlanner2D.MAX_TREE_NODES
+        return self._call(lambda e, sel, start: e.em_plan(sel, start, cap, int(self._o._planner_params.algorithm), want_nodes=True))
+
+    def rrt_planner(self, n_key, fron_0, fron_1):
+        cap = planner2d.EMPlanner2D.MAX_TREE_NODES
+
+        def run(e, sel, start):
+            key = torch.tensor([int(n_key)], dtype=torch.int32, device=e.device)
+            xy = torch.tensor([[float(fron_0), float(fron_1)]], dtype=torch.float64, device=e.device)
+            return e.rrt_plan(sel, key, xy, start, cap, want_nodes=True)
+        return self._call(run)
+
+    def iter_solution(self):
+        return iter(self._solution)
+
+
 class EMExplorer(SS2D):
     """scripts/envs/pyplanner2d.py:57-84."""
+
+    def __init__(self, *args, **kwargs):
+        super(EMExplorer, self).__init__(*args, **kwargs)
+        self._planner = _Planner(self)
+
+    def plan(self):
+        """pyplanner2d.py:70-71: EMPlanner2D::optimize2 on the device; the path is then `self._planner.iter_solution()`."""
+        return self._planner.optimize2() == planner2d.OptimizationResult.SUCCESS
+
+    def rrt_plan(self, goal_key, fron):
+        """pyplanner2d.py:73-74: EMPlanner2D::rrt_planner to graph node `goal_key` if it is one, else to the point `fron`."""
+        return self._planner.rrt_planner(goal_key, fron[0], fron[1]) == planner2d.OptimizationResult.SUCCESS
 
     def calculate_utility(self, distance):
         d = torch.tensor([float(distance)], dtype=torch.float64, device=self.engine.device)

@@ -98,6 +98,9 @@ class VecExplorationEnv(object):
         n = self.n_envs
         todo = np.arange(n, dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64).reshape(-1)
         self.dist[torch.as_tensor(todo, device=self.device)] = 0.0
+        if getattr(self, "_halton_next", None) is not None:  # (a re-created env gets a new planner: its Halton index starts over)
+            self._halton_next = self._halton_next.clone()
+            self._halton_next[torch.as_tensor(todo, device=self.device)] = self._halton_start
         while len(todo):
             if self.test:
                 seeds = self.env_index[todo].astype(np.uint32)
@@ -175,6 +178,35 @@ class VecExplorationEnv(object):
         # the plans' lengths on the host: the look-ahead and the step launch the action indices some plan reaches
         (self._n_act_h,) = self.engine.fetch(self._n_act)
         return self._actions, self._n_act
+
+    # ------------------------------------------------------------------ the EM-exploration baseline (exploration_env.py:107-128)
+    def _halton(self, seed):
+        from .planner2d import halton_start_index
+        if getattr(self, "_halton_next", None) is None:  # every env's planner starts where the reference's constructor starts it
+            self._halton_start = halton_start_index(seed)
+            self._halton_next = torch.full((self.n_envs,), self._halton_start, dtype=torch.int32, device=self.device)
+        return self._halton_next
+
+    def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0):
+        """ExplorationEnv.plan for all envs in one call (EMPlanner2D::optimize2, Engine.em_plan): per env the tree, the leaves' expected
+        costs with the configured algorithm, the best leaf's action list.  Returns (actions [n_envs, max_actions, 3] f64 edge
+        odometry, n_actions [n_envs] i32, result [n_envs] i32) on the device; every env's Halton index carries on from call to
+        call."""
+        self.engine.set_sampler_parameter(max_nodes)
+        sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
+        o = self.engine.em_plan(sel, self._halton(planner_seed), max_tree_nodes, int(self.cfg.algorithm))
+        self._halton_next = o["halton_next"]
+        return o["plan"], o["n_actions"], o["result"]
+
+    def rrt_plan(self, goal_key, frontier, max_tree_nodes=2048, planner_seed=0):
+        """ExplorationEnv.rrt_plan for all envs in one call (EMPlanner2D::rrt_planner, Engine.rrt_plan): goal_key [n_envs] i32 (a graph
+        node if it is one), frontier [n_envs, 2] f64 (the goal otherwise), on the device.  Returns like em_plan; an env whose tree
+        fills max_tree_nodes before it reaches the goal has result SAMPLING_FAILURE and no actions."""
+        sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
+        o = self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(), frontier.to(torch.float64).contiguous(), self._halton(planner_seed),
+                                 max_tree_nodes)
+        self._halton_next = o["halton_next"]
+        return o["plan"], o["n_actions"], o["result"]
 
     def rewards_all_goals(self, all_actions=None, return_raw=False, lookahead="sim"):
         """Look-ahead reward per candidate, normalised per env like exploration_env.py:151-161:

@@ -178,7 +178,7 @@ int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebui
 int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                      double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev);
 /* The leaf evaluation of EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1095-1104) for n_cand candidates (environment,
- * action list) the caller supplies - the sampler that builds the tree is not part of this library:
+ * action list) the caller supplies (drlgx_em_plan below grows optimize2's tree and feeds its leaves to this entry's body):
  *   updateTrajectory_EM (:472-551): the covariances of drlgx_fm2_update; every pose becomes a core pose of the leaf's map with
  *     information = cov^-1 (:521-523), the old ones at the current estimate (:1288), one per action at the noise-free predicted pose;
  *   VirtualMap::updateInformation on a copy of the root's virtual map (:1100-1101; VirtualMap.cpp:256-316, :213-229, :364-378):
@@ -199,6 +199,53 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
  * alone. */
 int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                   int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev);
+
+/* The planner parameters only the tree sampler reads (EMPlanner2D::Parameter, scripts/envs/pyplanner2d.py:29, :35, :50): max_nodes
+ * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
+ * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
+ * drlgx_em_plan / drlgx_rrt_plan.  After drlgx_create: max_nodes 0.5, safe_distance 0, Dubins off. */
+int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_distance, int dubins_control_model_enabled);
+/* EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1043-1128) for the n_sel environments env_sel_dev names: per environment
+ * one tree grown on the device from its live belief (k_em_tree.hip) -
+ *   initialize (:1281-1357): root = the current pose estimate; max_nodes_ = floor(#{p_v < occupancy_threshold} * max_nodes);
+ *   sampleNode (:101-125): Halton point number count++ (radical inverse in bases 2, 3, 5), x and y over the map box
+ *     (map_min_x .. map_max_x, map_min_y .. map_max_y), count starting at halton_start[i];
+ *   nearestNode (:267-276; Distance.cpp:5-9, :24-35): arg-min of range^2 + (angle_weight * bearing)^2 from the tree node's frame,
+ *     strict <: the lowest node index wins a tie;
+ *   connectNode, non-Dubins (:188-216, :250-258): angle = the sample's relative bearing in the parent's frame, len = min(d,
+ *     max_edge_length), child = parent * Pose2(angle, (len cos angle, len sin angle)), edge odometry (len cos angle, len sin angle,
+ *     angle), distance = parent.distance + sqrt(sqDistanceBetweenPoses(child, parent, angle_weight));
+ *   until max_nodes_ nodes are accepted (:1058-1092) -
+ * then every leaf (a node without children, in node order; the root itself when max_nodes_ = 0) is scored by the body of
+ * drlgx_em_cost with `algorithm`, and the first leaf with the strictly smallest cost is the plan (:1095-1111; the first leaf is
+ * always taken, a NaN cost never replaces a held one).  Live environments are only read.
+ * Every array is DEVICE memory: env_sel_dev int32[n_sel]; halton_start_dev int32[n_sel] (>= 0); plan_out_dev
+ * double[n_sel*max_actions*3] (the best leaf's edge odometry root -> leaf, zero behind the plan); n_actions_out_dev int32[n_sel];
+ * cost_out_dev double[n_sel] or NULL; result_out_dev int32[n_sel] or NULL (EMPlanner2D::OptimizationResult: 0 SAMPLING_FAILURE,
+ * 1 NO_SOLUTION, 2 TERMINATION, 3 SUCCESS - optimize2 at safe_distance 0 always succeeds); n_leaves_out_dev int32[n_sel] or NULL;
+ * halton_next_out_dev int32[n_sel] or NULL: the Halton index after the call (the reference's sequence keeps counting from call to
+ * call); nodes_out_dev double[n_sel*max_tree_nodes*8] or NULL: per node x, y, theta, parent index (-1: the root), distance, and the
+ * edge odometry from the parent (x, y, theta; zero for the root) - a leaf's plan is its ancestors' edges, root first;
+ * n_nodes_out_dev int32[n_sel] or NULL.  max_tree_nodes: the node capacity of one tree (root included), 1 .. 2048; every device
+ * loop is bounded by it.
+ * DRLGX_E_INVALID: a bad argument or algorithm, an environment that does not exist, a non-zero safe_distance or the Dubins control
+ * model (drlgx_set_sampler_parameter).  DRLGX_E_CAPACITY: a tree needs more than max_tree_nodes nodes, a tree is deeper than
+ * max_actions, or a leaf is refused by drlgx_em_cost (more than 256 predicted measurements); the outputs are then unspecified,
+ * live state and the status word are untouched, and the remedy is a larger max_tree_nodes or an engine created with a larger
+ * max_actions.  The call synchronises twice: once to read the leaf counts and the capacity flag, once in drlgx_em_cost's check. */
+int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                  int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
+                  int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev);
+/* EMPlanner2D::rrt_planner (Planner2D.cpp:838-935): the same tree, grown until a new node lies within max_edge_length of the goal
+ * (isReached, :88-99: Euclidean distance), to which the goal Pose2(gx, gy, pi) is then connected by connectNode; the plan is the
+ * path root -> goal.  The goal of environment i is the position of graph node goal_key[i] if 0 <= goal_key[i] < key_size
+ * (landmarks in key order, then poses: the node order of drlgx_graph), else the frontier point goal_xy[i].
+ * goal_key_dev int32[n_sel]; goal_xy_dev double[n_sel*2]; the other arrays as above.  A tree that fills max_tree_nodes without
+ * reaching its goal reports SAMPLING_FAILURE in result_out_dev with n_actions_out = 0 (the call itself returns DRLGX_OK);
+ * DRLGX_E_CAPACITY: a path to a goal longer than max_actions.  One synchronisation (the capacity flag). */
+int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *goal_key_dev, const double *goal_xy_dev,
+                   const int32_t *halton_start_dev, int max_tree_nodes, double *plan_out_dev, int32_t *n_actions_out_dev,
+                   int32_t *result_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev);
 
 /* Simulator2D::addLandmarks(landmarks, num_random, params) with a non-empty list (Simulator2D.cpp:445-464; the ini file's
  * optional [Landmarks] section, scripts/envs/pyss2d.py:107-115): the n_fixed listed points take the ground-truth keys
