@@ -738,6 +738,13 @@ size_t drlgx_em_lds_bytes(const DrlgxState &S);
 void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
                           const int32_t *n_actions, const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
                           double *info_out);
+// Expected map entropy of candidate plans (k_og.hip): nc candidates in drlgx_em_cost's layout, one workgroup each, in one launch; the
+// outputs (any of them null): entropy / cost [nc], prob [nc][V].  The check: flag[0] (zeroed by the caller) = DRLGX_E_INVALID if a
+// candidate names no environment or has more than max_actions actions
+size_t drlgx_og_lds_bytes(const DrlgxState &S);
+void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const int32_t *n_actions, int *flag);
+void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
+                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out);
 // The EM planner's tree sampler (k_em_tree.hip): one tree per selected environment, grown from its live belief, which is only read.
 // mode 0: optimize2's stop rule (max_nodes: the planner parameter), 1: rrt_planner's (goal_key / goal_xy).  Per-tree scratch, cap
 // nodes each: act [cap][3] edge odometry, link [cap][2] parent and depth, leaf [cap] the leaves in node order; meta [4] = nodes,

@@ -87,6 +87,7 @@ struct drlgx_engine {
   double *em_cov = nullptr;
   int32_t *em_nout = nullptr;
   int *em_flag = nullptr;
+  int *og_flag = nullptr;  // drlgx_og_cost's argument check (allocated on first use)
   // drlgx_em_plan / drlgx_rrt_plan (grown on demand): the trees' tables (edge odometry, parent and depth, leaf list, per-tree
   // results), the leaves as candidates of drlgx_em_cost with their costs; the sampler's own planner parameters
   double *tree_act = nullptr, *tree_cand_act = nullptr, *tree_cost = nullptr;
@@ -1024,6 +1025,31 @@ int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
     return DRLGX_E_INVALID;
   if (n_cand == 0) return DRLGX_OK;
   return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, algorithm, uncertainty_out_dev, cost_out_dev, info_out_dev);
+}
+
+// calculateUncertainty_OG_SHANNON + costFunction for candidate action lists (k_og.hip).  The candidates are checked first, as in
+// em_cost_run: one small launch and one read of its flag, so that a refused call leaves the status word alone.  No covariance, no
+// scratch per candidate: all candidates go in one launch.
+int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  double *entropy_out_dev, double *cost_out_dev, double *prob_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0) return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;  // (no array is read: empty ones may be null)
+  if (!cand_env_dev || !actions_dev || !n_actions_dev || (!entropy_out_dev && !cost_out_dev)) return DRLGX_E_INVALID;
+  const DrlgxState &S = e->S;
+  if (drlgx_og_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
+  if (!e->og_flag) {
+    int r;
+    if ((r = dev_alloc(e, &e->og_flag, (size_t)1))) return r;
+  }
+  int flag = 0;
+  HIPCHK(e, hipMemsetAsync(e->og_flag, 0, sizeof(int), e->stream));
+  drlgx_launch_og_check(S, e->stream, n_cand, cand_env_dev, n_actions_dev, e->og_flag);
+  HIPCHK(e, hipMemcpyAsync(&flag, e->og_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (flag) return flag;
+  drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, entropy_out_dev, cost_out_dev, prob_out_dev);
+  return check_launch(e);
 }
 
 // ---- the EM planner's tree sampler (k_em_tree.hip) ----

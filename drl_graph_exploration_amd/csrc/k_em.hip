@@ -28,6 +28,26 @@ __host__ __device__ inline size_t lds_bytes(int cap) {
   return ((size_t)cap * (kSp + kSl) + 3 * kWaves + 1) * sizeof(double) + (size_t)cap * sizeof(int);
 }
 
+// Pose i of a leaf's trajectory: the P old poses at the current estimate (ep), the new ones the noise-free chain from the last
+// estimate, as k_fm2_update chains them
+__device__ __forceinline__ Pose leaf_pose(const double *ep, int P, const double *act, int i) {
+  Pose ps{ep[4 * min(i, P - 1)], ep[4 * min(i, P - 1) + 1], ep[4 * min(i, P - 1) + 2], ep[4 * min(i, P - 1) + 3]};
+  for (int b = 0; b <= i - P; ++b) ps = compose(ps, make_pose(act[3 * b], act[3 * b + 1], act[3 * b + 2]));
+  return ps;
+}
+
+// distance of a plan, accumulated as the look-ahead accumulates it (Planner2D.cpp:1440, ksim: dist += sqrt(x^2 + y^2 +
+// angle_weight * theta^2), theta = Pose2::theta())
+__device__ __forceinline__ double plan_distance(const drlgx_config &cfg, const double *act, int K) {
+  double dist = 0.0;
+  for (int b = 0; b < K; ++b) {
+    const double ox = act[3 * b], oy = act[3 * b + 1];
+    const double th = theta_of(make_pose(ox, oy, act[3 * b + 2]));
+    dist = dist + sqrt(ox * ox + oy * oy + cfg.angle_weight * (th * th));
+  }
+  return dist;
+}
+
 // cov: [gridDim.x][cov_stride][9], the covariances k_fm2_update left for the same candidates; cand_env / actions / n_actions and the
 // outputs (any of them null) start at this launch's first candidate.
 __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *cand_env, const double *actions, const int32_t *n_actions,
@@ -52,9 +72,7 @@ __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *c
 
   // ---- pose staging: one lane per pose ----
   for (int i = tid; i < np; i += kT) {
-    Pose ps{ep[4 * min(i, P - 1)], ep[4 * min(i, P - 1) + 1], ep[4 * min(i, P - 1) + 2], ep[4 * min(i, P - 1) + 3]};
-    // new poses: the noise-free chain from the last estimate, as k_fm2_update chains them
-    for (int b = 0; b <= i - P; ++b) ps = compose(ps, make_pose(act[3 * b], act[3 * b + 1], act[3 * b + 2]));
+    const Pose ps = leaf_pose(ep, P, act, i);
     sp[4 * i] = ps.x; sp[4 * i + 1] = ps.y; sp[4 * i + 2] = ps.c; sp[4 * i + 3] = ps.s;
     // information = cov.inverse() (Planner2D.cpp:521-523): cofactors of the symmetric 3 x 3
     const double *c = cv + (size_t)i * 9;
@@ -84,17 +102,7 @@ __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *c
     o[6] = r00; o[7] = r11; o[8] = r22;
     pskip[i] = skip;
   }
-  if (tid == kT - 1) {
-    // distance of the plan, accumulated as the look-ahead accumulates it (Planner2D.cpp:1440, ksim: dist += sqrt(x^2 + y^2 +
-    // angle_weight * theta^2), theta = Pose2::theta())
-    double dist = 0.0;
-    for (int b = 0; b < K; ++b) {
-      const double ox = act[3 * b], oy = act[3 * b + 1];
-      const double th = theta_of(make_pose(ox, oy, act[3 * b + 2]));
-      dist = dist + sqrt(ox * ox + oy * oy + cfg.angle_weight * (th * th));
-    }
-    *sdist = dist;
-  }
+  if (tid == kT - 1) *sdist = plan_distance(cfg, act, K);
   __syncthreads();
 
   // ---- cell pass: one 8 x 8 tile of cells per wave and round (lane = 8 (row mod 8) + (col mod 8), as kmap::cell_pass) ----

@@ -301,6 +301,23 @@ __device__ __forceinline__ void clear_masks(const DrlgxState &S, const MapCtx &c
   if (tid == 0) *c.pcount = 0;
 }
 
+// where the bbox of a pose at (x, y) starts: its own cell, clamped into the grid (OccupancyMap.cpp:70-77); bbox_sweep widens it
+__device__ __forceinline__ void bbox_origin(const DrlgxState &S, int *bbox, double x, double y) {
+  const drlgx_config &cfg = S.cfg;
+  int orow = (int)floor((y - cfg.map_min_y) / cfg.resolution);
+  int ocol = (int)floor((x - cfg.map_min_x) / cfg.resolution);
+  orow = min(max(0, orow), S.rows - 1);
+  ocol = min(max(0, ocol), S.cols - 1);
+  bbox[0] = orow; bbox[1] = orow; bbox[2] = ocol; bbox[3] = ocol;
+}
+// the cell an estimated landmark lies in, -1 outside the grid (OccupancyMap.cpp:56-57, :127-131)
+__device__ __forceinline__ int landmark_cell(const DrlgxState &S, double x, double y) {
+  const drlgx_config &cfg = S.cfg;
+  const int r = (int)floor((y - cfg.map_min_y) / cfg.resolution);
+  const int cc = (int)floor((x - cfg.map_min_x) / cfg.resolution);
+  return (r >= S.rows || r < 0 || cc >= S.cols || cc < 0) ? -1 : r * S.cols + cc;
+}
+
 // ---- pose set-up: the pose tables, cleared masks and the ladder tables into LDS; landmark counts per cell; per pose its
 // window, the start of its bbox and the LLT factor of its information ----
 template <bool kCompact>
@@ -322,17 +339,12 @@ __device__ __forceinline__ void pose_setup(const DrlgxState &S, const MapCtx &c,
   // landmarks on the last threads, poses on the first ones: both in the same barrier interval
   for (int j = kThreads - 1 - tid; j < c.L; j += kThreads) {
     // OccupancyMap::update(map): landmark cell (OccupancyMap.cpp:127-131); every landmark in a cell is one occupied update
-    int r = (int)floor((el[2 * j + 1] - cfg.map_min_y) / cfg.resolution);
-    int cc = (int)floor((el[2 * j] - cfg.map_min_x) / cfg.resolution);
-    if (!(r >= rows || r < 0 || cc >= cols || cc < 0)) atomicAdd(&c.lmc[r * cols + cc], 1);
+    const int v = landmark_cell(S, el[2 * j], el[2 * j + 1]);
+    if (v >= 0) atomicAdd(&c.lmc[v], 1);
   }
   for (int p = tid; p < P; p += kThreads) {
     const double x = c.sp[4 * p], y = c.sp[4 * p + 1];
-    int orow = (int)floor((y - cfg.map_min_y) / cfg.resolution);
-    int ocol = (int)floor((x - cfg.map_min_x) / cfg.resolution);
-    orow = min(max(0, orow), rows - 1);
-    ocol = min(max(0, ocol), cols - 1);
-    c.bbox[4 * p + 0] = orow; c.bbox[4 * p + 1] = orow; c.bbox[4 * p + 2] = ocol; c.bbox[4 * p + 3] = ocol;
+    bbox_origin(S, c.bbox + 4 * p, x, y);
     // window of candidate cells for the information update: one cell wider than the tightest
     // (open) interval so that no cell the reference's radius query accepts can fall outside
     c.worg[2 * p + 0] = (int)floor((y - cfg.max_range - cfg.map_min_y) / cfg.resolution - 0.5);
@@ -470,6 +482,13 @@ __device__ __forceinline__ void push_through(const DrlgxState &S, const MapCtx &
 struct LadderFsm {
   unsigned long long t_occ, t_free;
   unsigned int t_flag;
+  // an estimated landmark in the cell: one occupied update (OccupancyMap.cpp:127-131)
+  __device__ __forceinline__ int landmark(int st) const { return (int)((t_occ >> (4 * st)) & 15); }
+  // a pose that sees the cell (OccupancyMap.cpp:103-117): frozen at the minimum, occupied above the threshold, else free
+  __device__ __forceinline__ int seen(int st) const {
+    const int f = (t_flag >> (2 * st)) & 3;
+    return (f & 1) ? st : (int)((((f & 2) ? t_occ : t_free) >> (4 * st)) & 15);
+  }
 };
 
 // ---- phase C (cell-centric) visits exactly the poses that update a cell, in trajectory order (ascending bits), for the
@@ -611,7 +630,7 @@ __device__ __forceinline__ void cell_pass(const DrlgxState &S, const MapCtx &c, 
       // in prob[]
       int st = 0;  // LOGODDS_UNKNOWN
       if (c0 == 0) {
-        for (int n = lmc_cell; n > 0; --n) st = (int)((fsm_t.t_occ >> (4 * st)) & 15);
+        for (int n = lmc_cell; n > 0; --n) st = fsm_t.landmark(st);
       } else {
         st = (int)c.prob[v];
       }
@@ -620,8 +639,7 @@ __device__ __forceinline__ void cell_pass(const DrlgxState &S, const MapCtx &c, 
       // cannot change it (cells at the clamped minimum / maximum, i.e. every cell seen more than a few times)
       while (m) {
         m &= m - 1;
-        const int f = (fsm_t.t_flag >> (2 * st)) & 3;
-        const int nst = (f & 1) ? st : (int)((((f & 2) ? fsm_t.t_occ : fsm_t.t_free) >> (4 * st)) & 15);
+        const int nst = fsm_t.seen(st);
         if (nst == st) break;
         st = nst;
       }

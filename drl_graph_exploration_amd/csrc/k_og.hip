@@ -1,0 +1,157 @@
+// Expected map entropy of candidate plans: calculateUncertainty_OG_SHANNON (src/em_exploration/Planner2D.cpp:368-392) for action
+// lists the caller supplies -
+//   node->virtual_map->updateProbability(slam, sensor_model)   (VirtualMap.cpp:61-84: OccupancyMap::update(map), OccupancyMap.cpp:122-138)
+//   uncertainty = sum_v -p_v ln p_v - (1 - p_v) ln(1 - p_v)     (:383-389)
+//   node->cost = uncertainty + distance * distance_weight_      (:418-420, :1322-1332)
+// without simulating, without noise, without re-solving and without any covariance: the leaf's map holds the P old poses at the
+// current estimate and one pose per action at the noise-free predicted pose chained from the last estimate (kem::leaf_pose), and
+// the landmarks at their current estimates.  The occupancy grid is rebuilt from the untouched map: the landmarks' cells, then
+// every pose in trajectory order.  Nothing of the live environment is written.
+//
+// One workgroup per candidate.  The P + K poses (x y c s) and their bounding boxes are staged in LDS once, the landmarks as the
+// count per cell.  The cell pass is cell-centric: a wave takes an 8 x 8 tile of cells, a lane walks the poses in trajectory order
+// for its cell and steps the ladder's state machine (kmap::LadderFsm, the packed tables of DrlgxState::lo_tocc ...) at every pose
+// that sees it - the order matters once the ladder clamps, so there is no mask and no pose-centric pass; a cell whose state maps
+// to itself stops early, as in kmap::cell_pass.  The two sums are reduced within a wave, then across the waves through LDS in
+// wave order: repeated calls give the same bits.  Part of the k_step.hip unity build: kmap's and kem's device functions as they
+// are, and -ffp-contract=off for the gates.
+#include "drlgx_dev.h"
+
+namespace kog {
+
+constexpr int kT = kmap::kThreads;  // (kmap::bbox_sweep deals its (pose, sample) pairs to a workgroup of this size)
+constexpr int kWaves = kT / 64;
+
+// doubles: poses [cap][4] | sums of the waves [2][kWaves] | the plan's distance | ladder values [DRLGX_LO_TAB];
+// ints: bbox [cap][4] | landmarks per cell [V]
+__host__ __device__ inline size_t lds_bytes(int cap, int V) {
+  return ((size_t)cap * 4 + 2 * kWaves + 1 + DRLGX_LO_TAB) * sizeof(double) + ((size_t)cap * 4 + (size_t)V) * sizeof(int);
+}
+
+// What k_og_cost could only report through the status word, found out before it is launched: a candidate that names no environment
+// or has more actions than max_actions.  flag[0] = DRLGX_E_INVALID then (the caller zeroes it).
+__global__ void k_og_check(DRLGX_KS_PARAM, int n_cand, const int32_t *cand_env, const int32_t *n_actions, int *flag) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ci >= n_cand) return;
+  const int env = cand_env[ci], K = n_actions[ci];
+  if (env < 0 || env >= S.n_envs || K < 0 || K > S.A_max) atomicMin(flag, DRLGX_E_INVALID);
+}
+
+// cand_env / actions / n_actions: [gridDim.x] candidates in drlgx_em_cost's layout; ent_out / cost_out [gridDim.x], prob_out
+// [gridDim.x][V], any of them null
+__global__ __launch_bounds__(kT) void k_og_cost(DRLGX_KS_PARAM, const int32_t *cand_env, const double *actions, const int32_t *n_actions,
+                                                double *ent_out, double *cost_out, double *prob_out) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  extern __shared__ __attribute__((aligned(16))) double og_smem[];
+  const drlgx_config &cfg = S.cfg;
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6, ci = blockIdx.x;
+  const int env = cand_env[ci];
+  const int K = n_actions[ci];
+  const bool env_ok = env >= 0 && env < S.n_envs;
+  const int P = env_ok ? S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_P] : 0, L = env_ok ? S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_L] : 0;
+  const int cap = S.P_max + S.A_max, np = P + K, V = S.V;
+  if (!env_ok || K < 0 || K > S.A_max || P < 1 || P > S.P_max || L < 0 || L > S.L_max) {  // (the host checked: flag it, touch nothing)
+    if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+    return;
+  }
+  kmap::MapCtx c;  // (what kmap::bbox_sweep reads: the pose table, the boxes, the pose count)
+  c.sp = og_smem;
+  double *red = c.sp + (size_t)cap * 4, *sdist = red + 2 * kWaves, *lpv = sdist + 1;
+  c.bbox = reinterpret_cast<int *>(lpv + DRLGX_LO_TAB);
+  c.P = np;
+  int *lmc = c.bbox + (size_t)cap * 4;
+  const double *ep = S.est_pose + (size_t)env * S.P_max * 4;
+  const double *el = S.est_lm + (size_t)env * S.L_max * 2;
+  const double *act = actions + (size_t)ci * S.A_max * 3;
+
+  // ---- staging: one lane per pose (the first lanes), the plan's distance on the last one; the cells' landmark counts cleared ----
+  for (int i = tid; i < np; i += kT) {
+    const Pose ps = kem::leaf_pose(ep, P, act, i);
+    c.sp[4 * i] = ps.x; c.sp[4 * i + 1] = ps.y; c.sp[4 * i + 2] = ps.c; c.sp[4 * i + 3] = ps.s;
+    kmap::bbox_origin(S, c.bbox + 4 * i, ps.x, ps.y);
+  }
+  if (tid == kT - 1) *sdist = kem::plan_distance(cfg, act, K);
+  if (tid < S.lo_ntab) lpv[tid] = S.lo_pv[tid];  // (lo_ntab <= DRLGX_LO_TAB < kT)
+  for (int v = tid; v < V; v += kT) lmc[v] = 0;
+  __syncthreads();
+  // every estimated landmark inside the grid is one occupied update of its cell (OccupancyMap.cpp:127-131)
+  for (int j = tid; j < L; j += kT) {
+    const int v = kmap::landmark_cell(S, el[2 * j], el[2 * j + 1]);
+    if (v >= 0) atomicAdd(&lmc[v], 1);
+  }
+  const bool use_bbox = !S.bbox_noop;  // (else the box provably holds every in-range cell: k_map.hip)
+  if (use_bbox) kmap::bbox_sweep(S, c);
+  __syncthreads();
+
+  // ---- cell pass: one 8 x 8 tile of cells per wave and round (lane = 8 (row mod 8) + (col mod 8), as kmap::cell_pass) ----
+  const int cols = S.cols, rows = S.rows;
+  const int tiles_c = (cols + 7) >> 3, ntiles = ((rows + 7) >> 3) * tiles_c;
+  const kmap::LadderFsm fsm{S.lo_tocc, S.lo_tfree, S.lo_tflag};
+  const double *live = S.vm_prob + (size_t)env * V;
+  double *pout = prob_out ? prob_out + (size_t)ci * V : nullptr;
+  double s_h = 0.0, s_known = 0.0;
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int trow = t / tiles_c, tcol = t - trow * tiles_c;
+    const int row = 8 * trow + (lane >> 3), col = 8 * tcol + (lane & 7);
+    if (!(row < rows && col < cols)) continue;
+    const int v = row * cols + col;
+    const P2 pt = kmap::cell_centre(cfg, row, col);
+    int st = 0;  // LOGODDS_UNKNOWN
+    for (int n = lmc[v]; n > 0; --n) st = fsm.landmark(st);
+    for (int i = 0; i < np; ++i) {
+      // OccupancyMap::update(state) (OccupancyMap.cpp:98-118): the cell lies in the pose's box and passes checkWithoutMinRange
+      if (use_bbox && (row < c.bbox[4 * i] || row > c.bbox[4 * i + 1] || col < c.bbox[4 * i + 2] || col > c.bbox[4 * i + 3])) continue;
+      const Pose ps{c.sp[4 * i], c.sp[4 * i + 1], c.sp[4 * i + 2], c.sp[4 * i + 3]};
+      const double gx = ps.x - pt.x, gy = ps.y - pt.y;
+      if (!(gx * gx + gy * gy < S.r2_max_lt)) continue;  // sqrt(d2) < max_range, exactly
+      if (!kmap::in_fov(S, ps, pt)) continue;
+      const int nst = fsm.seen(st);
+      if (nst == st) break;  // absorbing: the transition depends on the state only
+      st = nst;
+    }
+    const double pv = lpv[st];  // VirtualMap::updateProbability: the host's value table
+    if (pout) pout[v] = pv;
+    s_h += -pv * log(pv) - (1.0 - pv) * log(1.0 - pv);
+    if (live[v] < cfg.occupancy_threshold) s_known += 1.0;  // the LIVE map (Planner2D.cpp:1322-1325)
+  }
+
+  // ---- reductions: within a wave, then across the waves in wave order ----
+  s_h = kmap::wave_sum63(s_h);
+  s_known = kmap::wave_sum63(s_known);
+  if (lane == 63) {
+    red[wave] = s_h;
+    red[kWaves + wave] = s_known;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double h = 0.0, known = 0.0;
+    for (int w = 0; w < kWaves; ++w) {
+      h += red[w];
+      known += red[kWaves + w];
+    }
+    if (ent_out) ent_out[ci] = h;
+    if (cost_out) {
+      const double pk = known / (double)V;
+      const double dw = cfg.distance_weight0 - (cfg.distance_weight0 - cfg.distance_weight1) * pk;
+      cost_out[ci] = h + *sdist * dw;
+    }
+  }
+}
+
+}  // namespace kog
+
+size_t drlgx_og_lds_bytes(const DrlgxState &S) { return kog::lds_bytes(S.P_max + S.A_max, S.V); }
+
+void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const int32_t *n_actions, int *flag) {
+  hipLaunchKernelGGL(kog::k_og_check, dim3((n_cand + 63) / 64), dim3(64), 0, st, DRLGX_KS_ARG(S), n_cand, cand_env, n_actions, flag);
+}
+
+void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
+                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out) {
+  static bool attr_set[32] = {false};
+  const void *fns[] = {reinterpret_cast<const void *>(&kog::k_og_cost)};
+  drlgx_ensure_lds_attr(attr_set, fns, 1, (int)kmap::kLdsBudget);
+  hipLaunchKernelGGL(kog::k_og_cost, dim3(nc), dim3(kog::kT), drlgx_og_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions, n_actions,
+                     ent_out, cost_out, prob_out);
+}

@@ -26,6 +26,7 @@
 #include "k_slam_host.hip"    // LDS / workspace sizing, drlgx_launch_slam
 #include "k_map.hip"
 #include "k_em.hip"          // leaf evaluation of candidate plans (kmap's device functions, this unit's -ffp-contract=off)
+#include "k_og.hip"          // expected map entropy of candidate plans (kmap's ladder, bbox and gates, kem's pose chain)
 
 namespace kstep {
 

@@ -257,6 +257,19 @@ class Engine(object):
         self._chk(self.L.drlgx_em_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), int(algorithm), _p(unc), _p(cost), _p(info)))
         return (unc, cost, info) if want_info else (unc, cost)
 
+    def og_cost(self, cand_env, actions, n_actions, want_prob=False):
+        """Expected map entropy of candidate plans (drlgx_og_cost: calculateUncertainty_OG_SHANNON and costFunction, without
+        simulating, re-solving or any covariance): returns (entropy [C], cost [C]) float64 and, with `want_prob`, the leaf
+        occupancy map's probabilities [C, rows, cols].  Candidates as in `em_cost`: cand_env [C] i32, actions
+        [C, max_actions, 3] f64, n_actions [C] i32 on the device."""
+        self.use_torch_stream()
+        n = cand_env.numel()
+        ent = torch.empty(n, dtype=torch.float64, device=self.device)
+        cost = torch.empty(n, dtype=torch.float64, device=self.device)
+        prob = torch.empty(n, self.rows, self.cols, dtype=torch.float64, device=self.device) if want_prob else None
+        self._chk(self.L.drlgx_og_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(ent), _p(cost), _p(prob)))
+        return (ent, cost, prob) if want_prob else (ent, cost)
+
     def set_sampler_parameter(self, max_nodes, safe_distance=0.0, dubins_control_model_enabled=False):
         """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
         control model is stored and then refused by em_plan / rrt_plan."""

@@ -89,7 +89,7 @@ class EMPlanner2D(object):
     """`EMPlanner2D(parameter, sensor_model, control_model)` (src/Planner2D.cpp:73-91) over the engine that the models'
     simulation owns: the calls the DRL scripts make - `calculate_utility` (static), `line_planner`, `simulations_reward` -
     run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`; `leaf_cost` is the leaf evaluation of `optimize2`
-    (`drlgx_em_cost`) for an action list the caller supplies; `optimize2` and `rrt_planner` grow the sampler's tree on the device
+    (`drlgx_em_cost`) for an action list the caller supplies, `leaf_entropy` the OG-Shannon cost of one (`drlgx_og_cost`); `optimize2` and `rrt_planner` grow the sampler's tree on the device
     (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0) and `iter_solution` walks the best path as the
     reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
     call.  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (out of scope)."""
@@ -165,6 +165,24 @@ class EMPlanner2D(object):
         copy of the root's virtual map, node->uncertainty = calculateUncertainty_EM, node->cost = costFunction - the expected cost
         of the plan with the parameter's algorithm, without simulating it and without noise (`drlgx_em_cost`).  The live
         objects are not modified.  The sampler that builds optimize2's tree stays out of scope: `optimize2` itself raises."""
+        e, ce, acts, n = self._one_candidate(actions)
+        unc, cost = e.em_cost(ce, acts, n, int(self._parameter.algorithm))
+        e.check_status()
+        return (float(cost[0]), float(unc[0])) if return_uncertainty else float(cost[0])
+
+    def leaf_entropy(self, slam, virtual_map, actions, return_cost=False):
+        """calculateUncertainty_OG_SHANNON (Planner2D.cpp:368-392) for ONE action list of the wrapped simulation: the Shannon
+        entropy of the occupancy map after the estimated landmarks, the trajectory and the plan's noise-free predicted poses have
+        swept it (`drlgx_og_cost`); with `return_cost` also costFunction = entropy + distance * distance_weight.  No covariance,
+        no simulation; the live objects are not modified.  The tree planners under the OG algorithms stay out of scope (the
+        reference leaves their nodes' map a null pointer)."""
+        e, ce, acts, n = self._one_candidate(actions)
+        ent, cost = e.og_cost(ce, acts, n)
+        e.check_status()
+        return (float(ent[0]), float(cost[0])) if return_cost else float(ent[0])
+
+    def _one_candidate(self, actions):
+        """(engine, cand_env, actions, n_actions) of one action list (Pose2 or (x, y, theta) entries) in the candidate layout."""
         import torch
         e = self._ses.require_engine()
         A = e.cfg.max_actions
@@ -175,9 +193,7 @@ class EMPlanner2D(object):
             acts[0, k] = torch.tensor([a.x, a.y, a.theta] if hasattr(a, "x") else list(a), dtype=torch.float64)
         n = torch.tensor([len(actions)], dtype=torch.int32, device=e.device)
         ce = torch.zeros(1, dtype=torch.int32, device=e.device)
-        unc, cost = e.em_cost(ce, acts.to(e.device), n, int(self._parameter.algorithm))
-        e.check_status()
-        return (float(cost[0]), float(unc[0])) if return_uncertainty else float(cost[0])
+        return e, ce, acts.to(e.device), n
 
     def _tree_call(self, run):
         """One sampler call for the wrapped simulation: the parameter object as it is now, the Halton index carried on, the best

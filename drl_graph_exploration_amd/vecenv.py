@@ -213,10 +213,21 @@ class VecExplorationEnv(object):
         nearest frontier is the arg-max -> interp to [-1, 0], loop_clo False; else [-1, 1], loop_clo True.
         lookahead="sim": the stochastic look-ahead (EMPlanner2D::simulations_reward, drlgx_lookahead).  "em": the deterministic
         expected cost instead - raw = the root's uncertainty (Engine.uncertainty_em) minus the leaf's cost (Engine.em_cost, the
-        leaf evaluation of optimize2) with the planner parameter's algorithm: the sign convention of U_before - U_after."""
-        if lookahead not in ("sim", "em"):
-            raise ValueError("lookahead must be 'sim' or 'em', not %r" % (lookahead,))
+        leaf evaluation of optimize2) with the planner parameter's algorithm: the sign convention of U_before - U_after.  "og":
+        the expected map entropy (Engine.og_cost, calculateUncertainty_OG_SHANNON) in the same convention - raw = the entropy of
+        the candidate's environment with no action (one extra candidate per env in the same call) minus the candidate's cost."""
+        if lookahead not in ("sim", "em", "og"):
+            raise ValueError("lookahead must be 'sim', 'em' or 'og', not %r" % (lookahead,))
         actions, n_act = all_actions if all_actions is not None else (self._actions, self._n_act)
+        if lookahead == "og":
+            nc = self._cand_env.numel()
+            roots = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
+            ent, cost = self.engine.og_cost(torch.cat([self._cand_env, roots]),
+                                            torch.cat([actions, actions.new_zeros((self.n_envs,) + tuple(actions.shape[1:]))]),
+                                            torch.cat([n_act, torch.zeros_like(roots)]))
+            raw = ent[nc:][self._cand_env.long()] - cost[:nc]
+            r, self.loop_clo = normalise_rewards(raw, self._cand_env.long(), self._cand_first, self.n_envs, self._graph["n_frontier"])
+            return (r, raw) if return_raw else r
         if lookahead == "em":
             alg = int(self.cfg.algorithm)
             _, cost = self.engine.em_cost(self._cand_env, actions, n_act, alg)

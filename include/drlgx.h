@@ -200,6 +200,26 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
 int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                   int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev);
 
+/* calculateUncertainty_OG_SHANNON (src/em_exploration/Planner2D.cpp:368-392) and costFunction (:418-420) for n_cand candidates
+ * (environment, action list) the caller supplies - the Shannon entropy of the occupancy map after the plan's poses have swept it:
+ *   OccupancyMap::update(map) (OccupancyMap.cpp:122-138): every cell at LOGODDS_UNKNOWN; one occupied update of its cell per estimated
+ *     landmark inside the grid; then every pose in trajectory order - the P old poses at the current estimate, one per action at the
+ *     noise-free predicted pose chained from the last estimate (as drlgx_em_cost chains them) - updates the cells of its sector-sweep
+ *     bounding box that pass checkWithoutMinRange and are not at MIN_LOGODDS: occupied above OCCUPIED_THRESH + 1e-8, else free;
+ *   p_v = the cell's probability (VirtualMap::updateProbability, VirtualMap.cpp:61-84); entropy = sum_v -p_v ln p_v - (1 - p_v) ln(1 - p_v);
+ *   cost = entropy + distance * distance_weight, both exactly drlgx_em_cost's (the distance weight from the LIVE map's probabilities).
+ * No covariance is needed, nothing is simulated or re-solved, live environments are not modified.  (The reference's tree planners
+ * cannot run under OG_SHANNON as shipped - Node::map stays a null pointer, Planner2D.h:92, Planner2D.cpp:256, :785 - so this is the
+ * cost's arithmetic for caller-supplied plans; drlgx_em_plan and drlgx_em_cost's algorithms are unchanged, SLAM_OG_SHANNON is out.)
+ * Candidate layout as drlgx_em_cost: cand_env_dev int32[n_cand] (several candidates may name one environment); actions_dev
+ * double[n_cand*max_actions*3]; n_actions_dev int32[n_cand], 0 <= n <= max_actions.  entropy_out_dev / cost_out_dev: DEVICE
+ * double[n_cand], either may be NULL but not both; prob_out_dev: DEVICE double[n_cand*V] (row-major grid: the leaf map's
+ * probabilities) or NULL.  Any n_cand >= 0 (0 returns at once and reads no array), all candidates in one launch.  DRLGX_E_INVALID: both scalar outputs NULL, a candidate
+ * that names no environment or has more than max_actions actions.  The candidates are checked before anything else is launched (one
+ * read of a device flag: this call synchronises once); a refused call leaves the status word and the live state alone. */
+int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  double *entropy_out_dev, double *cost_out_dev, double *prob_out_dev);
+
 /* The planner parameters only the tree sampler reads (EMPlanner2D::Parameter, scripts/envs/pyplanner2d.py:29, :35, :50): max_nodes
  * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
  * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
