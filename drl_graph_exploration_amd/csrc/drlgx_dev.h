@@ -749,10 +749,13 @@ void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int
 // mode 0: optimize2's stop rule (max_nodes: the planner parameter), 1: rrt_planner's (goal_key / goal_xy).  Per-tree scratch, cap
 // nodes each: act [cap][3] edge odometry, link [cap][2] parent and depth, leaf [cap] the leaves in node order; meta [4] = nodes,
 // leaves, next Halton index, OptimizationResult.  flag[0] (zeroed by the caller): DRLGX_E_INVALID / DRLGX_E_CAPACITY.
+// obstacles: the kSafe = true instantiation with the planner parameter safe_distance (isSafe, the retry loop of sampleNode, the two
+// counters of 1000, the shrink at the start of the call); a tree it ends with SAMPLING_FAILURE has no leaf and touches no flag.
 size_t drlgx_em_tree_lds_bytes(int cap);
 void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                          int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy, double *act, int *link, int *leaf,
-                          int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out);
+                          int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
+                          double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
+                          int32_t *result_out, int32_t *halton_next_out);
 // the action lists root -> leaf in drlgx_em_cost's candidate layout; per_tree_row: row ti of the outputs instead of the running count
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions);

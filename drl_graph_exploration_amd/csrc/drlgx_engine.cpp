@@ -96,6 +96,7 @@ struct drlgx_engine {
   size_t tree_nodes_cap = 0, tree_sel_cap = 0, tree_cand_cap = 0;
   double sampler_max_nodes = 0.5, sampler_safe_distance = 0.0;
   int sampler_dubins = 0;
+  int sampler_obstacles = 0;  // drlgx_set_sampler_obstacles: the sampler's obstacle logic (safe_distance > 0), off unless asked for
   // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
   // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
   // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
@@ -1064,6 +1065,13 @@ int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_d
   return DRLGX_OK;
 }
 
+int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled) {
+  DRLGX_ENTER(e);
+  if (!e) return DRLGX_E_INVALID;
+  e->sampler_obstacles = enabled ? 1 : 0;
+  return DRLGX_OK;
+}
+
 // a scratch array of at least `count` elements: kept while it is large enough, replaced (behind the stream's work) when it is not
 extern "C++" {
 template <typename T>
@@ -1098,9 +1106,11 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
   }
   int *flag_dev = e->tree_meta + (size_t)n_sel * kTreeMeta;
   HIPCHK(e, hipMemsetAsync(flag_dev, 0, sizeof(int), e->stream));
-  drlgx_launch_em_tree(e->S, e->stream, n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, goal_key_dev, goal_xy_dev,
-                       e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev, nodes_out_dev, n_nodes_out_dev, result_out_dev,
-                       halton_next_out_dev);
+  // (the obstacle logic only where there is a distance to keep: at exactly 0 the plain growth loop is the same tree)
+  const bool obstacles = e->sampler_obstacles && e->sampler_safe_distance != 0.0;
+  drlgx_launch_em_tree(e->S, e->stream, n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, obstacles,
+                       e->sampler_safe_distance, goal_key_dev, goal_xy_dev, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev,
+                       nodes_out_dev, n_nodes_out_dev, result_out_dev, halton_next_out_dev);
   if ((r = check_launch(e))) return r;
   meta_h.resize((size_t)n_sel * kTreeMeta + 1);
   HIPCHK(e, hipMemcpyAsync(meta_h.data(), e->tree_meta, meta_h.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1111,7 +1121,7 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
 static bool tree_args_ok(const drlgx_engine *e, int n_sel, const void *env_sel, const void *halton_start, int cap, const void *plan_out,
                          const void *n_actions_out) {
   return e && n_sel >= 0 && env_sel && halton_start && plan_out && n_actions_out && cap >= 1 && cap <= kTreeMaxNodes &&
-         e->sampler_safe_distance == 0.0 && !e->sampler_dubins;
+         (e->sampler_obstacles ? e->sampler_safe_distance >= 0.0 : e->sampler_safe_distance == 0.0) && !e->sampler_dubins;
 }
 
 int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
@@ -1137,11 +1147,13 @@ int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const 
     if ((r = scratch_reserve(e, &e->tree_cost, n_cand))) return r;
     e->tree_cand_cap = n_cand;
   }
-  drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 0,
-                         e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
-  if ((r = check_launch(e))) return r;
-  if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, algorithm, nullptr, e->tree_cost, nullptr)))
-    return r;
+  if (n_cand > 0) {  // (every tree failed to sample: nothing to score, the pick below writes the empty plans)
+    drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
+                           0, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
+    if ((r = check_launch(e))) return r;
+    if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, algorithm, nullptr, e->tree_cost, nullptr)))
+      return r;
+  }
   drlgx_launch_em_pick(e->stream, n_sel, S.A_max, e->tree_meta, e->tree_cost, e->tree_cand_act, e->tree_cand_n, plan_out_dev,
                        n_actions_out_dev, cost_out_dev, n_leaves_out_dev);
   return check_launch(e);

@@ -19,7 +19,37 @@
 // nodes; DESIGN.md section 4 has the comparison).  Every loop is bounded by the node capacity `cap`: each turn of the growth loop
 // accepts exactly one node, so a tree that cannot finish ends with a capacity result instead of spinning.
 //
-// The live belief is only read.  Built with -ffp-contract=off: the nearest-node comparison is a gate.
+//
+// THE OBSTACLE LOGIC (kSafe = true; the engine launches it only behind drlgx_set_sampler_obstacles and a safe_distance > 0 - the
+// kSafe = false instantiation is the code above, unchanged) adds, restated from the same file:
+//   isSafe(node) (:48-56; Distance.cpp:78-97)   unsafe iff an estimated landmark of the environment lies strictly nearer than
+//                                safe_distance (a negative radius finds nothing).  Each lane keeps one landmark in registers (lanes
+//                                stride the rest), a ballot decides: only emptiness is asked, the landmarks' order does not matter
+//   sampleNode (:101-125)        Halton points until one is safe, every drawn point consumed; the 1001st unsafe point of one call
+//                                ends the tree with SAMPLING_FAILURE
+//   isSafe(node, parent) (:58-86), asked by connectNode after the child is scaled (:243-248): |safe_distance| < 1e-3 tests nothing;
+//                                else d = range(child, parent), unit = the child's position in the PARENT's frame / d, and for
+//                                l = sd/2; l < d; l += sd/2 (repeated addition, strict <) the point child.transform_from(l unit).
+//                                AS WRITTEN IN THE REFERENCE these points lie BEYOND the child, in the direction of the child's
+//                                heading turned by the edge's bearing once more - not between parent and child.  Reproduced as
+//                                written: this project follows the reference's behaviour.  Waypoints serially, landmarks in
+//                                parallel, out at the first unsafe one (the branch is wave-uniform); at most 2 max_edge_length /
+//                                1e-3 turns (d <= max_edge_length, the step is at least 5e-4)
+//   the connect counter (:1070-1079, :890-899)   a refused connect adds no node; the 1001st in a row ends the tree
+//   the shrink (:1046-1054, :841-849)   when the root is nearer than safe_distance to its nearest estimated landmark, the call's
+//                                safe_distance is that distance - 0.1 (optimize2: not below 0; rrt_planner: unclamped) - IF the
+//                                landmark's KEY is smaller than the NUMBER of landmarks: searchLandmarkNearest returns the key
+//                                (Simulator2D.cpp:394-403: landmarks in key order, strict <, so the lowest key wins a tie) and the
+//                                planner compares it with getLandmarkSize().  Kept as it is
+//   rrt_planner's goal edge (:910-922)   a goal whose edge is unsafe is not in the tree: SUCCESS, no leaf, an empty plan
+// ONE DEVIATION: in rrt_planner a shrunk safe_distance below -1e-3 (the root within 0.099 m of a landmark) makes the reference's
+// waypoint loop run for ever - a negative step, l < d always true.  Such a tree ends at once with SAMPLING_FAILURE, the root alone,
+// no point drawn.
+// A tree that ends with SAMPLING_FAILURE keeps the nodes accepted so far, has no leaf and no plan; the other trees of the launch are
+// not concerned, and the flag is not touched: a sampling failure is a result.  Loop bounds: cap accepted nodes, the two counters of
+// 1000, the waypoint bound.
+//
+// The live belief is only read.  Built with -ffp-contract=off: the nearest-node comparison and the safety tests are gates.
 #include "drlgx_dev.h"
 
 #ifndef DRLGX_EM_TREE_THREADS
@@ -34,6 +64,8 @@ constexpr int kNd = 5, kNi = 3;  // per node: x y c s distance | parent depth ch
 constexpr int kNodeOut = 8;      // doubles per node of nodes_out
 enum { M_NODES = 0, M_LEAVES = 1, M_HALTON = 2, M_RESULT = 3, M_STRIDE = 4 };
 enum { R_SAMPLING_FAILURE = 0, R_SUCCESS = 3 };  // EMPlanner2D::OptimizationResult
+constexpr int kMaxFailed = 1000;     // `failed > 1000` of sampleNode and of the growth loops
+constexpr double kEdgeEps = 1e-3;    // |safe_distance| below which isSafe(node, parent) tests nothing
 
 __host__ __device__ inline size_t lds_bytes(int cap) {
   return (size_t)cap * (kNd * sizeof(double) + kNi * sizeof(int)) + 2 * kWaves * sizeof(double) + 64;
@@ -87,12 +119,52 @@ __device__ __forceinline__ void argmin_all(double &d, int &idx, double *red_d, i
   }
 }
 
+// The estimated landmarks of one environment as the safety tests read them: landmark `lane` in registers (+inf where there is
+// none: its distance is never below a radius), the ones from 64 on in memory.  Every wave holds all of them.
+struct Obstacles {
+  double x, y;
+  const double *el;
+  int L;
+};
+
+// isSafe(node): no landmark strictly nearer than sd; the same answer in every thread
+__device__ __forceinline__ bool point_safe(const P2 &pt, const Obstacles &ob, double sd) {
+  if (sd < 0.0) return true;
+  const int lane = threadIdx.x & 63;
+  const double dx = ob.x - pt.x, dy = ob.y - pt.y;
+  bool hit = sqrt(dx * dx + dy * dy) < sd;
+  for (int j = lane + 64; j < ob.L; j += 64) {
+    const double ex = ob.el[2 * j] - pt.x, ey = ob.el[2 * j + 1] - pt.y;
+    hit = hit || sqrt(ex * ex + ey * ey) < sd;
+  }
+  return __ballot(hit) == 0ull;
+}
+
+// isSafe(node, parent), non-Dubins: the waypoints as the reference writes them (beyond the child - see the head of the file)
+__device__ __forceinline__ bool edge_safe(const Pose &child, const Pose &par, const Obstacles &ob, double sd, int wp_bound) {
+  if (fabs(sd) < kEdgeEps) return true;
+  const double d = range_of<false>(child, P2{par.x, par.y}, nullptr, nullptr);
+  const P2 loc = transform_to(par, P2{child.x, child.y});
+  const double half = sd / 2;
+  double l = half;
+  for (int w = 0; w < wp_bound && l < d; ++w) {  // (d == 0: no waypoint)
+    const double inv = 1.0 / d;
+    const P2 unit{inv * loc.x, inv * loc.y};
+    if (!point_safe(transform_from(child, P2{l * unit.x, l * unit.y}), ob, sd)) return false;
+    l += half;
+  }
+  return true;
+}
+
 // mode 0: optimize2's stop rule; 1: rrt_planner's.  goal_key / goal_xy: mode 1 only.  nodes_out (null: not wanted): per tree
 // [cap][8] = x y theta parent distance | the edge odometry from the parent (x y theta).  flag[0] (zeroed by the caller): the smallest DRLGX_E_* code any tree met.
+// kSafe: the obstacle logic with the planner parameter safe_distance (> 0); kSafe = false never reads it.
+template <bool kSafe>
 __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                                                int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy,
-                                                double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out,
-                                                int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out) {
+                                                int mode, double max_nodes, double safe_distance, const int32_t *goal_key,
+                                                const double *goal_xy, double *act, int *link, int *leaf, int *meta, int *flag,
+                                                double *nodes_out, int32_t *n_nodes_out, int32_t *result_out,
+                                                int32_t *halton_next_out) {
   extern __shared__ __attribute__((aligned(16))) double tree_smem[];
   const int tid = threadIdx.x, lane = tid & 63, ti = blockIdx.x;
   if (ti >= n_sel) return;
@@ -169,11 +241,51 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
   }
   __syncthreads();
 
-  // ---- growth: one accepted node per turn ----
+  // ---- the call's safe_distance: the shrink ----
+  Obstacles ob{__builtin_huge_val(), __builtin_huge_val(), el, L};
+  double sd = safe_distance;
+  bool sampling_failed = false, goal_refused = false;
+  int wp_bound = 0;
+  if (kSafe) {
+    if (lane < L) {
+      ob.x = el[2 * lane];
+      ob.y = el[2 * lane + 1];
+    }
+    // searchLandmarkNearest: the landmarks in key order, strict < - the arg-min of (distance, key); what comes back is the KEY
+    const int *lk = S.lm_key + (size_t)env * S.L_max;
+    const double rx = ep[4 * (P - 1)], ry = ep[4 * (P - 1) + 1];
+    double bd = __builtin_huge_val();
+    int bk = 0x7fffffff;
+    for (int j = lane; j < L; j += 64) {
+      const double dx = el[2 * j] - rx, dy = el[2 * j + 1] - ry;
+      const double dj = sqrt(dx * dx + dy * dy);
+      if (dj < bd || (dj == bd && lk[j] < bk)) {
+        bd = dj;
+        bk = lk[j];
+      }
+    }
+    for (int m = 1; m < 64; m <<= 1) {
+      const double od = __shfl_xor(bd, m, 64);
+      const int ok = __shfl_xor(bk, m, 64);
+      if (od < bd || (od == bd && ok < bk)) {
+        bd = od;
+        bk = ok;
+      }
+    }
+    // (no landmark: the reference's search answers 1, which is not below 0.)  The key against the NUMBER of landmarks, as written
+    if (L > 0 && bk >= 0 && bk < L && bd < sd) sd = mode == 0 ? (bd - 0.1 > 0.0 ? bd - 0.1 : 0.0) : bd - 0.1;
+    // the deviation: rrt_planner's waypoint loop would not end
+    if (mode == 1 && sd < -kEdgeEps) sampling_failed = true;
+    const double wb = 2.0 * cfg.max_edge_length / kEdgeEps + 2.0;
+    wp_bound = wb < 2147483647.0 ? (int)wb : 0x7fffffff;
+  }
+
+  // ---- growth: one accepted node per turn (kSafe: or one refused connect, at most kMaxFailed in a row) ----
   const double span_x = cfg.map_max_x - cfg.map_min_x, span_y = cfg.map_max_y - cfg.map_min_y;
-  int n = 1, count = halton_start[ti], max_depth = 0, goal_node = -1;
+  int n = 1, count = halton_start[ti], max_depth = 0, goal_node = -1, failed = 0;
   bool full = false;  // the table filled before the stop rule was met
-  for (int turn = 0; turn < cap; ++turn) {
+  const long long max_turns = kSafe ? (long long)cap * (kMaxFailed + 2) : (long long)cap;
+  for (long long turn = 0; turn < max_turns && !sampling_failed; ++turn) {
     if (mode == 0 && n - 1 >= budget) break;
     if (n >= cap) {
       full = true;
@@ -182,9 +294,25 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     // sampleNode.  (The sample's own heading, theta = 2 pi h2 with h2 the radical inverse in base 5, enters nothing at
     // safe_distance = 0 - nearestNode and connectNode read the sample's position only, the child's heading is the parent's plus the
     // bearing - so the third coordinate of the point is not evaluated; the point is consumed all the same.)
-    const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
-    ++count;
-    const P2 sp{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+    // kSafe: points are drawn until one is safe, each one consumed; the 1001st unsafe one ends the tree.
+    P2 sp{0.0, 0.0};
+    if (kSafe) {
+      bool found = false;
+      for (int u = 0; u <= kMaxFailed && !found; ++u) {
+        const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
+        ++count;
+        sp = P2{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+        found = point_safe(sp, ob, sd);
+      }
+      if (!found) {
+        sampling_failed = true;
+        break;
+      }
+    } else {
+      const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
+      ++count;
+      sp = P2{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+    }
     // nearestNode
     double best = __builtin_huge_val();
     int bi = 0x7fffffff;
@@ -208,6 +336,17 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     const double len = d > cfg.max_edge_length ? cfg.max_edge_length : d;
     const double ax = len * cos(angle), ay = len * sin(angle);
     const Pose child = compose(par, make_pose(ax, ay, angle));
+    if (kSafe) {
+      // isSafe(node, parent) on the scaled child: a refused connect adds no node
+      if (!edge_safe(child, par, ob, sd, wp_bound)) {
+        if (++failed > kMaxFailed) {
+          sampling_failed = true;
+          break;
+        }
+        continue;
+      }
+      failed = 0;
+    }
     double bb;
     const double dist = pdist + sqrt(sq_distance(child, P2{par.x, par.y}, cfg.angle_weight, bb));
     __syncthreads();  // (every thread has read the table)
@@ -234,6 +373,10 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
         const double glen = gd > cfg.max_edge_length ? cfg.max_edge_length : gd;
         const double gax = glen * cos(gang), gay = glen * sin(gang);
         const Pose gp = compose(child, make_pose(gax, gay, gang));
+        if (kSafe && !edge_safe(gp, child, ob, sd, wp_bound)) {
+          goal_refused = true;  // the loop ends all the same (:910-922): SUCCESS, the goal not in the tree, no plan
+          break;
+        }
         const double gdist = dist + sqrt(sq_distance(gp, P2{child.x, child.y}, cfg.angle_weight, bb));
         if (tid == 0) {
           nd[kNd * n] = gp.x; nd[kNd * n + 1] = gp.y; nd[kNd * n + 2] = gp.c; nd[kNd * n + 3] = gp.s;
@@ -250,7 +393,7 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
       }
     }
   }
-  if (mode == 1 && goal_node < 0) full = true;  // (the turns ran out: the table is full)
+  if (mode == 1 && goal_node < 0 && !sampling_failed && !goal_refused) full = true;  // (the turns ran out: the table is full)
 
   // ---- results: the tables to memory, the leaves in node order ----
   int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
@@ -267,7 +410,7 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     }
   }
   int n_leaves = 0;
-  if (mode == 0) {
+  if (mode == 0 && !sampling_failed) {
     if (tid < 64) {  // (one wave lists: node order)
       for (int base = 0; base < n; base += 64) {
         const int j = base + lane;
@@ -282,7 +425,7 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     n_leaves = 1;
   }
   if (tid == 0) {
-    const int res = (mode == 1 && full) ? R_SAMPLING_FAILURE : R_SUCCESS;
+    const int res = ((mode == 1 && full) || sampling_failed) ? R_SAMPLING_FAILURE : R_SUCCESS;
     mt[M_NODES] = n;
     mt[M_LEAVES] = n_leaves;
     mt[M_HALTON] = count;
@@ -291,7 +434,9 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     if (result_out) result_out[ti] = res;
     if (halton_next_out) halton_next_out[ti] = count;
     // what the whole call is refused for: optimize2's tree does not fit the table; a plan deeper than max_actions
-    if ((mode == 0 && full) || ((mode == 0 || goal_node >= 0) && max_depth > S.A_max)) atomicMin(flag, DRLGX_E_CAPACITY);
+    // (a tree that failed to sample offers no plan: nothing of it can be too deep)
+    if ((mode == 0 && full) || (((mode == 0 && !sampling_failed) || goal_node >= 0) && max_depth > S.A_max))
+      atomicMin(flag, DRLGX_E_CAPACITY);
   }
 }
 
@@ -365,7 +510,8 @@ __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int 
   // the first leaf is held whatever its cost: a NaN there is never replaced, an infinite one only by a smaller cost
   const double c0 = nl > 0 ? cost[off] : 0.0;
   if (nl > 0 && (c0 != c0 || bi >= nl || !(best < c0))) bi = 0;
-  if (nl <= 0) {
+  if (nl <= 0) {  // (a tree that failed to sample: no leaf, an empty plan)
+    for (int q = lane; q < 3 * A_max; q += 64) plan_out[(size_t)ti * A_max * 3 + q] = 0.0;
     if (lane == 0) {
       n_actions_out[ti] = 0;
       if (cost_out) cost_out[ti] = 0.0;
@@ -387,13 +533,20 @@ __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int 
 size_t drlgx_em_tree_lds_bytes(int cap) { return kemt::lds_bytes(cap); }
 
 void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                          int mode, double max_nodes, const int32_t *goal_key, const double *goal_xy, double *act, int *link, int *leaf,
-                          int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out, int32_t *result_out, int32_t *halton_next_out) {
+                          int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
+                          double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
+                          int32_t *result_out, int32_t *halton_next_out) {
   static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree)};
-  drlgx_ensure_lds_attr(attr_set, fns, 1, 160 * 1024);
-  hipLaunchKernelGGL(kemt::k_em_tree, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap, mode,
-                     max_nodes, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out, halton_next_out);
+  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree<false>), reinterpret_cast<const void *>(&kemt::k_em_tree<true>)};
+  drlgx_ensure_lds_attr(attr_set, fns, 2, 160 * 1024);
+  if (obstacles)
+    hipLaunchKernelGGL(kemt::k_em_tree<true>, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap,
+                       mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
+                       halton_next_out);
+  else
+    hipLaunchKernelGGL(kemt::k_em_tree<false>, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap,
+                       mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
+                       halton_next_out);
 }
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions) {

@@ -32,6 +32,7 @@ class Engine(object):
         self.n_rollouts = n_rollouts
         self.device = torch.device("cuda", device)
         self.h = C.c_void_p()
+        self.sampler_parameter, self.sampler_obstacles = (0.5, 0.0, False), False  # (the engine's values after drlgx_create)
         _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)), self.h)  # (NULL: the creation's error)
         r, c = C.c_int32(), C.c_int32()
         self.L.drlgx_vm_shape(self.h, C.byref(r), C.byref(c))
@@ -272,8 +273,18 @@ class Engine(object):
 
     def set_sampler_parameter(self, max_nodes, safe_distance=0.0, dubins_control_model_enabled=False):
         """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
-        control model is stored and then refused by em_plan / rrt_plan."""
+        control model is stored and then refused by em_plan / rrt_plan (a safe_distance >= 0 is served once
+        set_sampler_obstacles(True) has opted in).  The values last set are kept in `sampler_parameter`."""
         self._chk(self.L.drlgx_set_sampler_parameter(self.h, float(max_nodes), float(safe_distance), int(bool(dubins_control_model_enabled))))
+        self.sampler_parameter = (float(max_nodes), float(safe_distance), bool(dubins_control_model_enabled))
+
+    def set_sampler_obstacles(self, enabled):
+        """The sampler's obstacle logic (drlgx_set_sampler_obstacles), an opt-in that is off after construction: with it em_plan /
+        rrt_plan serve safe_distance >= 0 - isSafe on samples and edges, the retry loop of sampleNode, the two counters of 1000 and
+        the shrink at the start of a call, as the reference has them; a tree can then end with SAMPLING_FAILURE (a result, not an
+        error).  Off, a non-zero safe_distance is refused as before.  The setting is kept in `sampler_obstacles`."""
+        self._chk(self.L.drlgx_set_sampler_obstacles(self.h, int(bool(enabled))))
+        self.sampler_obstacles = bool(enabled)
 
     def _tree_outputs(self, n, max_tree_nodes, want_nodes):
         dev, A = self.device, self.cfg.max_actions

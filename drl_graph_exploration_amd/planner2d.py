@@ -90,14 +90,18 @@ class EMPlanner2D(object):
     simulation owns: the calls the DRL scripts make - `calculate_utility` (static), `line_planner`, `simulations_reward` -
     run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`; `leaf_cost` is the leaf evaluation of `optimize2`
     (`drlgx_em_cost`) for an action list the caller supplies, `leaf_entropy` the OG-Shannon cost of one (`drlgx_og_cost`); `optimize2` and `rrt_planner` grow the sampler's tree on the device
-    (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0) and `iter_solution` walks the best path as the
-    reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
+    (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0 - or, with the attribute `obstacle_logic` set,
+    any safe_distance >= 0 with the reference's isSafe / retry / shrink logic; it is an opt-in because the default refusal is what
+    existing callers and tests rely on) and `iter_solution` walks the best path as the reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
     call.  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (out of scope)."""
     MAX_TREE_NODES = 2048  # the node capacity of one tree (the engine's maximum)
     OptimizationAlgorithm = OptimizationAlgorithm
     OptimizationResult = OptimizationResult
+    obstacle_logic = False  # True: the sampler's obstacle logic (Engine.set_sampler_obstacles) - a non-zero safe_distance is served
 
-    def __init__(self, parameter, sensor_model, control_model):
+    def __init__(self, parameter, sensor_model, control_model, obstacle_logic=False):
+        if obstacle_logic:
+            self.obstacle_logic = True
         self._ses = sensor_model._session
         if self._ses is None or control_model._session is not self._ses:
             raise ValueError("the sensor and control models must come from one Simulator2D")
@@ -115,6 +119,7 @@ class EMPlanner2D(object):
             self._ses.engine.set_planner_parameter(parameter.angle_weight, parameter.distance_weight0, parameter.distance_weight1,
                                                    parameter.occupancy_threshold, parameter.max_edge_length, int(parameter.algorithm))
             self._ses.engine.set_sampler_parameter(parameter.max_nodes, parameter.safe_distance, parameter.dubins_control_model_enabled)
+            self._ses.engine.set_sampler_obstacles(self.obstacle_logic)
 
     @staticmethod
     def calculate_utility(virtual_map, distance, parameter):
@@ -199,7 +204,7 @@ class EMPlanner2D(object):
         """One sampler call for the wrapped simulation: the parameter object as it is now, the Halton index carried on, the best
         path kept for iter_solution."""
         import torch
-        _require_sampler_scope(self._parameter)
+        _require_sampler_scope(self._parameter, self.obstacle_logic)
         e = self._ses.require_engine()
         self.set_parameter(self._parameter)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
@@ -238,12 +243,19 @@ class EMPlanner2D(object):
     optimize = iter_rrt = get_dubins_path = _out_of_scope
 
 
-def _require_sampler_scope(parameter):
+def _require_sampler_scope(parameter, obstacle_logic=False):
     """The sampler serves the non-Dubins control model at safe_distance = 0 (the engine refuses anything else with
-    DRLGX_E_INVALID); the facades say so the way they say it for everything outside the accelerated path."""
-    if parameter.dubins_control_model_enabled or parameter.safe_distance != 0:
+    DRLGX_E_INVALID); the facades say so the way they say it for everything outside the accelerated path.  With `obstacle_logic`
+    (the opt-in) any safe_distance >= 0 passes; the Dubins control model still raises."""
+    if parameter.dubins_control_model_enabled:
+        raise NotImplementedError("the tree sampler runs for the non-Dubins control model only (Dubins paths are outside the "
+                                  "accelerated path)")
+    if obstacle_logic:
+        if parameter.safe_distance < 0:
+            raise ValueError("safe_distance must not be negative")
+    elif parameter.safe_distance != 0:
         raise NotImplementedError("the tree sampler runs for the non-Dubins control model at safe_distance = 0 only "
-                                  "(obstacle logic and Dubins paths are outside the accelerated path)")
+                                  "(obstacle logic is an opt-in: obstacle_logic=True; Dubins paths are outside the accelerated path)")
 
 
 class Node(object):

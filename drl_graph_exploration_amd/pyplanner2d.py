@@ -270,9 +270,10 @@ class _Planner(object):
 
     def _call(self, run):
         o, pp = self._o, self._o._planner_params
-        planner2d._require_sampler_scope(pp)
+        planner2d._require_sampler_scope(pp, o.obstacle_logic)
         e = o.engine
         e.set_sampler_parameter(pp.max_nodes, pp.safe_distance, pp.dubins_control_model_enabled)
+        e.set_sampler_obstacles(o.obstacle_logic)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
         start = torch.tensor([self.halton_next], dtype=torch.int32, device=e.device)
         out = run(e, sel, start)
@@ -301,9 +302,12 @@ class _Planner(object):
 
 
 class EMExplorer(SS2D):
-    """scripts/envs/pyplanner2d.py:57-84."""
+    """scripts/envs/pyplanner2d.py:57-84.  `obstacle_logic` (an opt-in, off by default): plan() / rrt_plan() run the planner's
+    safe_distance as the ini file gives it, with the sampler's obstacle logic (Engine.set_sampler_obstacles); off, a non-zero
+    planner safe_distance raises NotImplementedError as before."""
 
     def __init__(self, *args, **kwargs):
+        self.obstacle_logic = bool(kwargs.pop("obstacle_logic", False))
         super(EMExplorer, self).__init__(*args, **kwargs)
         self._planner = _Planner(self)
 

@@ -187,24 +187,46 @@ class VecExplorationEnv(object):
             self._halton_next = torch.full((self.n_envs,), self._halton_start, dtype=torch.int32, device=self.device)
         return self._halton_next
 
-    def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0):
+    def _with_safe_distance(self, max_nodes, safe_distance, run):
+        """One sampler call under `safe_distance` (None: the engine's settings as they are, only max_nodes replaced if given): a
+        value opts in to the sampler's obstacle logic for this call, and the engine's previous sampler settings come back after it."""
+        e = self.engine
+        old_par, old_obs = e.sampler_parameter, e.sampler_obstacles
+        if safe_distance is None:
+            if max_nodes is not None:
+                e.set_sampler_parameter(max_nodes)
+            return run()
+        e.set_sampler_parameter(old_par[0] if max_nodes is None else max_nodes, safe_distance)
+        e.set_sampler_obstacles(True)
+        try:
+            return run()
+        finally:
+            e.set_sampler_parameter(*old_par)
+            e.set_sampler_obstacles(old_obs)
+
+    def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0, safe_distance=None):
         """ExplorationEnv.plan for all envs in one call (EMPlanner2D::optimize2, Engine.em_plan): per env the tree, the leaves' expected
         costs with the configured algorithm, the best leaf's action list.  Returns (actions [n_envs, max_actions, 3] f64 edge
         odometry, n_actions [n_envs] i32, result [n_envs] i32) on the device; every env's Halton index carries on from call to
-        call."""
-        self.engine.set_sampler_parameter(max_nodes)
+        call.  `safe_distance` (None: 0, as before): a value runs this call with the sampler's obstacle logic at that planner
+        safe_distance (an env can then have result SAMPLING_FAILURE and no actions) and restores the engine's sampler settings."""
         sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
-        o = self.engine.em_plan(sel, self._halton(planner_seed), max_tree_nodes, int(self.cfg.algorithm))
+        start = self._halton(planner_seed)
+        o = self._with_safe_distance(max_nodes, safe_distance,
+                                     lambda: self.engine.em_plan(sel, start, max_tree_nodes, int(self.cfg.algorithm)))
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]
 
-    def rrt_plan(self, goal_key, frontier, max_tree_nodes=2048, planner_seed=0):
+    def rrt_plan(self, goal_key, frontier, max_tree_nodes=2048, planner_seed=0, safe_distance=None):
         """ExplorationEnv.rrt_plan for all envs in one call (EMPlanner2D::rrt_planner, Engine.rrt_plan): goal_key [n_envs] i32 (a graph
         node if it is one), frontier [n_envs, 2] f64 (the goal otherwise), on the device.  Returns like em_plan; an env whose tree
-        fills max_tree_nodes before it reaches the goal has result SAMPLING_FAILURE and no actions."""
+        fills max_tree_nodes before it reaches the goal has result SAMPLING_FAILURE and no actions.  `safe_distance`: as em_plan's
+        (a goal whose edge is unsafe gives SUCCESS with no actions, as the reference's empty solution)."""
         sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
-        o = self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(), frontier.to(torch.float64).contiguous(), self._halton(planner_seed),
-                                 max_tree_nodes)
+        start = self._halton(planner_seed)
+        o = self._with_safe_distance(None, safe_distance,
+                                     lambda: self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(),
+                                                                  frontier.to(torch.float64).contiguous(), start, max_tree_nodes))
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]
 

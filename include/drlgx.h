@@ -223,8 +223,37 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
 /* The planner parameters only the tree sampler reads (EMPlanner2D::Parameter, scripts/envs/pyplanner2d.py:29, :35, :50): max_nodes
  * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
  * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
- * drlgx_em_plan / drlgx_rrt_plan.  After drlgx_create: max_nodes 0.5, safe_distance 0, Dubins off. */
+ * drlgx_em_plan / drlgx_rrt_plan (a safe_distance > 0 is served once drlgx_set_sampler_obstacles, below, has opted in).  After
+ * drlgx_create: max_nodes 0.5, safe_distance 0, Dubins off. */
 int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_distance, int dubins_control_model_enabled);
+/* The sampler's obstacle logic, an OPT-IN (default 0: every call behaves as described above and below, a non-zero safe_distance is
+ * refused).  With enabled != 0, drlgx_em_plan / drlgx_rrt_plan accept safe_distance >= 0 (a negative value and the Dubins control
+ * model are still refused with DRLGX_E_INVALID before anything is touched; at exactly 0 the plain growth loop runs) and the tree
+ * kernel adds, for the non-Dubins control model (src/em_exploration/Planner2D.cpp):
+ *   isSafe(node) (:48-56; Distance.cpp:78-97): a point is unsafe iff an estimated landmark of the environment lies strictly nearer
+ *     than safe_distance; a negative radius finds nothing;
+ *   sampleNode (:101-125): Halton points are drawn until one is safe, every drawn point advances the index; more than 1000 unsafe
+ *     points in one sampleNode end the tree with SAMPLING_FAILURE;
+ *   isSafe(node, parent) in connectNode, on the scaled child (:58-86, :243-248): safe if |safe_distance| < 1e-3; else with
+ *     d = range(child, parent) and unit = the child's position in the parent's frame / d, the points child.transform_from(l unit)
+ *     for l = sd/2; l < d; l += sd/2 must all be safe.  As the reference writes it these points lie BEYOND the child along the
+ *     child's heading, not between parent and child; reproduced as written;
+ *   the connect counter (:1070-1079, :890-899): a refused connect adds no node; more than 1000 in a row end the tree with
+ *     SAMPLING_FAILURE;
+ *   the shrink at the start of a call (:1046-1054, :841-849): if the current pose estimate is nearer than safe_distance to its
+ *     nearest estimated landmark, the call runs with distance - 0.1 (drlgx_em_plan: max(0, .); drlgx_rrt_plan: unclamped) - but, as
+ *     in the reference, only if that landmark's KEY is smaller than the NUMBER of landmarks (searchLandmarkNearest returns the key,
+ *     Simulator2D.cpp:394-403, nearest in key order with strict <; the planner compares it with getLandmarkSize()).  The stored
+ *     parameter is not changed;
+ *   rrt_planner's goal edge (:910-922): a goal whose edge is unsafe is not in the tree - result SUCCESS, n_actions 0, the goal not
+ *     counted in n_nodes.
+ * One deviation: in rrt_planner a shrunk safe_distance below -1e-3 makes the reference's waypoint loop run for ever; the engine ends
+ * that tree at once with SAMPLING_FAILURE, an empty plan and its Halton index unchanged.
+ * A tree that ends with SAMPLING_FAILURE reports result 0, n_actions 0, no leaves, the nodes accepted so far in n_nodes / nodes_out,
+ * and in halton_next the index after the last drawn point; the other trees of the call are not concerned, it offers no candidate to
+ * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  Dubins paths, optimize (RRT*) and
+ * SLAM_OG_SHANNON stay out of scope. */
+int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled);
 /* EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1043-1128) for the n_sel environments env_sel_dev names: per environment
  * one tree grown on the device from its live belief (k_em_tree.hip) -
  *   initialize (:1281-1357): root = the current pose estimate; max_nodes_ = floor(#{p_v < occupancy_threshold} * max_nodes);
