@@ -751,11 +751,25 @@ void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int
 // leaves, next Halton index, OptimizationResult.  flag[0] (zeroed by the caller): DRLGX_E_INVALID / DRLGX_E_CAPACITY.
 // obstacles: the kSafe = true instantiation with the planner parameter safe_distance (isSafe, the retry loop of sampleNode, the two
 // counters of 1000, the shrink at the start of the call); a tree it ends with SAMPLING_FAILURE has no leaf and touches no flag.
+// dubins (null: the non-Dubins control model): the kDubins = true instantiation, mode 1 only - the Dubins path library
+// (drlgx_set_dubins_library_host) on the device, SoA in library order.  max_steps: the largest num_steps (the bound of the step
+// loops); reach: (the largest |end| + tol)(1 + 2^-30), beyond which no entry can match (+inf: never skip a scan); pose: per-tree
+// scratch [cap][4], the nodes' (x y cos sin) for the plan.  A node's act row is then (library index, num_steps, 0), its depth in
+// link counts steps, and drlgx_launch_em_leaves_dubins writes the plan: one row per step, row ti of the outputs.
+struct DrlgxDubins {
+  const double *end_x, *end_y, *v, *w;
+  const int *num_steps;
+  int n, max_steps;
+  double dt, tol, reach;
+  double *pose;
+};
 size_t drlgx_em_tree_lds_bytes(int cap);
 void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
                           int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
                           double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
-                          int32_t *result_out, int32_t *halton_next_out);
+                          int32_t *result_out, int32_t *halton_next_out, const DrlgxDubins *dubins);
+void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
+                                   const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions);
 // the action lists root -> leaf in drlgx_em_cost's candidate layout; per_tree_row: row ti of the outputs instead of the running count
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions);

@@ -97,6 +97,16 @@ struct drlgx_engine {
   double sampler_max_nodes = 0.5, sampler_safe_distance = 0.0;
   int sampler_dubins = 0;
   int sampler_obstacles = 0;  // drlgx_set_sampler_obstacles: the sampler's obstacle logic (safe_distance > 0), off unless asked for
+  // drlgx_set_dubins_library_host: the Dubins path library, the opt-in of the Dubins control model (dubins.n == 0: none loaded) - on
+  // the device for the kernel, on the host for drlgx_dubins_library; the nodes' poses for the plan (grown with the trees' tables)
+  DrlgxDubins dubins = {};
+  double *dub_end_x = nullptr, *dub_end_y = nullptr, *dub_v = nullptr, *dub_w = nullptr, *tree_pose = nullptr;
+  int *dub_steps = nullptr;
+  size_t dub_cap = 0, tree_pose_cap = 0;
+  double dub_reach = 0.0;
+  int dub_prefilter = 1;
+  std::vector<double> dub_end_h, dub_v_h, dub_w_h;  // end: x y theta per entry
+  std::vector<int> dub_steps_h;
   // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
   // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
   // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
@@ -1086,12 +1096,108 @@ static int scratch_reserve(drlgx_engine *e, T **p, size_t count) {
 }
 }
 
+// ---- the Dubins path library (EMPlanner2D::initializeDubinsPathLibrary, Planner2D.cpp:1359-1414) ----
+static const int kDubinsMaxEntries = 131072;  // (the [Dubins] section scripts/envs/pyplanner2d.ini ships gives 78 030)
+static const int kDubinsMaxSteps = 4096;      // steps of one path
+static const int kDubinsMaxPairs = 1 << 20;   // (v, w) pairs looked at, entries or not
+
+int drlgx_set_dubins_library_host(drlgx_engine *e, const double *params) {
+  DRLGX_ENTER(e);
+  if (!e) return DRLGX_E_INVALID;
+  if (!params) {
+    e->dubins = DrlgxDubins{};
+    e->dub_end_h.clear(); e->dub_v_h.clear(); e->dub_w_h.clear(); e->dub_steps_h.clear();
+    return DRLGX_OK;
+  }
+  const double max_w = params[0], dw = params[1], min_v = params[2], max_v = params[3], dv = params[4], dt = params[5];
+  const double min_duration = params[6], max_duration = params[7], tol = params[8];
+  if (!(max_w > 0.0) || !(dw > 0.0) || !(dv > 0.0) || !(dt > 0.0) || !(tol > 0.0) || !(max_v >= min_v) || !std::isfinite(max_w) ||
+      !std::isfinite(max_v) || !std::isfinite(min_v) || !std::isfinite(tol) || !std::isfinite(min_duration) || !std::isfinite(max_duration))
+    return DRLGX_E_INVALID;
+  // the loops as the reference writes them: the counts come from this floating-point arithmetic, not from a division
+  std::vector<double> end, vv, ww, ex, ey;
+  std::vector<int> steps;
+  int pairs = 0, max_steps = 0;
+  double reach = 0.0;
+  for (double v = max_v; v > min_v - 1e-10; v -= dv) {
+    for (double w = 0; w < max_w + 1e-10; w += dw) {
+      if (++pairs > kDubinsMaxPairs) return DRLGX_E_CAPACITY;
+      for (int s = -1; s <= 1; s += 2) {
+        double t = 0.0;
+        const double wws = w * s;
+        double x = 0.0, y = 0.0, c = 1.0, sn = 0.0;  // Pose2(0, 0, 0)
+        int num_steps = 0;
+        while (t < max_duration) {
+          if (++num_steps > kDubinsMaxSteps) return DRLGX_E_CAPACITY;
+          const double nx = x + v * dt * c, ny = y + v * dt * sn, th = std::atan2(sn, c) + wws * dt;
+          x = nx; y = ny; c = std::cos(th); sn = std::sin(th);  // Pose2(x, y, theta)
+          t += dt;
+          if (t > min_duration) {
+            if (steps.size() >= (size_t)kDubinsMaxEntries) return DRLGX_E_CAPACITY;
+            end.push_back(x); end.push_back(y); end.push_back(std::atan2(sn, c));
+            ex.push_back(x); ey.push_back(y);
+            vv.push_back(v); ww.push_back(wws); steps.push_back(num_steps);
+            max_steps = std::max(max_steps, num_steps);
+            reach = std::max(reach, std::sqrt(x * x + y * y));
+          }
+        }
+      }
+    }
+  }
+  if (steps.empty()) return DRLGX_E_INVALID;  // (no path lasts longer than min_duration: nothing could ever connect)
+  const size_t n = steps.size();
+  int r;
+  if (n > e->dub_cap) {
+    if ((r = scratch_reserve(e, &e->dub_end_x, n))) return r;
+    if ((r = scratch_reserve(e, &e->dub_end_y, n))) return r;
+    if ((r = scratch_reserve(e, &e->dub_v, n))) return r;
+    if ((r = scratch_reserve(e, &e->dub_w, n))) return r;
+    if ((r = scratch_reserve(e, &e->dub_steps, n))) return r;
+    e->dub_cap = n;
+  }
+  HIPCHK(e, hipMemcpyAsync(e->dub_end_x, ex.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dub_end_y, ey.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dub_v, vv.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dub_w, ww.data(), n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dub_steps, steps.data(), n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (the host buffers end with this call)
+  // the exact pre-filter's bound: |local| beyond it implies |local - end_i| > tol for every i (triangle inequality); the factor
+  // covers the roundings of the square roots and of this sum many times over
+  e->dub_reach = (reach + tol) * (1.0 + 9.313225746154785e-10);
+  e->dubins = DrlgxDubins{e->dub_end_x, e->dub_end_y, e->dub_v, e->dub_w, e->dub_steps, (int)n, max_steps, dt, tol,
+                          e->dub_prefilter ? e->dub_reach : HUGE_VAL, nullptr};
+  e->dub_end_h.swap(end); e->dub_v_h.swap(vv); e->dub_w_h.swap(ww); e->dub_steps_h.swap(steps);
+  return DRLGX_OK;
+}
+
+int drlgx_set_dubins_prefilter(drlgx_engine *e, int enabled) {
+  DRLGX_ENTER(e);
+  if (!e) return DRLGX_E_INVALID;
+  e->dub_prefilter = enabled ? 1 : 0;
+  if (e->dubins.n > 0) e->dubins.reach = e->dub_prefilter ? e->dub_reach : HUGE_VAL;
+  return DRLGX_OK;
+}
+
+int drlgx_dubins_library(drlgx_engine *e, int capacity, int32_t *n_out, double *end_xytheta, double *v, double *w, int32_t *num_steps) {
+  DRLGX_ENTER(e);
+  if (!e || !n_out || capacity < 0) return DRLGX_E_INVALID;
+  const int n = (int)e->dub_steps_h.size();
+  *n_out = n;
+  const int m = std::min(n, capacity);
+  if (end_xytheta) std::copy(e->dub_end_h.begin(), e->dub_end_h.begin() + (size_t)3 * m, end_xytheta);
+  if (v) std::copy(e->dub_v_h.begin(), e->dub_v_h.begin() + m, v);
+  if (w) std::copy(e->dub_w_h.begin(), e->dub_w_h.begin() + m, w);
+  if (num_steps) std::copy(e->dub_steps_h.begin(), e->dub_steps_h.begin() + m, num_steps);
+  return DRLGX_OK;
+}
+
 // Grows the trees and reads their results back: meta_h[n_sel][kTreeMeta] and the flag - the one synchronisation.  Returns the
 // flag's code when a tree was refused.
 static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int cap, int mode,
                      const int32_t *goal_key_dev, const double *goal_xy_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev,
                      int32_t *result_out_dev, int32_t *halton_next_out_dev, std::vector<int> &meta_h) {
   int r;
+  const bool dubins = e->sampler_dubins != 0;  // (tree_args_ok: mode 1 with a library loaded)
   if ((size_t)n_sel > e->tree_sel_cap) {
     if ((r = scratch_reserve(e, &e->tree_meta, (size_t)n_sel * kTreeMeta + 1))) return r;  // (+ the flag, behind the trees' rows)
     e->tree_sel_cap = (size_t)n_sel;
@@ -1104,13 +1210,18 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
     if ((r = scratch_reserve(e, &e->tree_leaf, nodes))) return r;
     e->tree_nodes_cap = nodes;
   }
+  if (dubins && nodes > e->tree_pose_cap) {
+    if ((r = scratch_reserve(e, &e->tree_pose, nodes * 4))) return r;
+    e->tree_pose_cap = nodes;
+  }
+  e->dubins.pose = e->tree_pose;
   int *flag_dev = e->tree_meta + (size_t)n_sel * kTreeMeta;
   HIPCHK(e, hipMemsetAsync(flag_dev, 0, sizeof(int), e->stream));
   // (the obstacle logic only where there is a distance to keep: at exactly 0 the plain growth loop is the same tree)
   const bool obstacles = e->sampler_obstacles && e->sampler_safe_distance != 0.0;
   drlgx_launch_em_tree(e->S, e->stream, n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, obstacles,
                        e->sampler_safe_distance, goal_key_dev, goal_xy_dev, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev,
-                       nodes_out_dev, n_nodes_out_dev, result_out_dev, halton_next_out_dev);
+                       nodes_out_dev, n_nodes_out_dev, result_out_dev, halton_next_out_dev, dubins ? &e->dubins : nullptr);
   if ((r = check_launch(e))) return r;
   meta_h.resize((size_t)n_sel * kTreeMeta + 1);
   HIPCHK(e, hipMemcpyAsync(meta_h.data(), e->tree_meta, meta_h.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1118,17 +1229,20 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
   return meta_h.back();
 }
 
+// The Dubins control model is served where a library is loaded (drlgx_set_dubins_library_host, the opt-in) and the planner is
+// rrt_planner; everywhere else the flag is refused.
 static bool tree_args_ok(const drlgx_engine *e, int n_sel, const void *env_sel, const void *halton_start, int cap, const void *plan_out,
-                         const void *n_actions_out) {
+                         const void *n_actions_out, bool rrt) {
   return e && n_sel >= 0 && env_sel && halton_start && plan_out && n_actions_out && cap >= 1 && cap <= kTreeMaxNodes &&
-         (e->sampler_obstacles ? e->sampler_safe_distance >= 0.0 : e->sampler_safe_distance == 0.0) && !e->sampler_dubins;
+         (e->sampler_obstacles ? e->sampler_safe_distance >= 0.0 : e->sampler_safe_distance == 0.0) &&
+         (!e->sampler_dubins || (rrt && e->dubins.n > 0));
 }
 
 int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
                   int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
                   int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
   DRLGX_ENTER(e);
-  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev) ||
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev, false) ||
       (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
     return DRLGX_E_INVALID;
   if (n_sel == 0) return DRLGX_OK;
@@ -1163,7 +1277,7 @@ int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const
                    const int32_t *halton_start_dev, int max_tree_nodes, double *plan_out_dev, int32_t *n_actions_out_dev,
                    int32_t *result_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
   DRLGX_ENTER(e);
-  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev) || !goal_key_dev ||
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev, true) || !goal_key_dev ||
       !goal_xy_dev)
     return DRLGX_E_INVALID;
   if (n_sel == 0) return DRLGX_OK;
@@ -1171,8 +1285,12 @@ int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const
   int r = tree_grow(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, 1, goal_key_dev, goal_xy_dev, nodes_out_dev, n_nodes_out_dev,
                     result_out_dev, halton_next_out_dev, meta);
   if (r) return r;
-  drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 1,
-                         nullptr, plan_out_dev, n_actions_out_dev);
+  if (e->sampler_dubins)  // one row per step, recomputed from the nodes' library entries
+    drlgx_launch_em_leaves_dubins(e->stream, n_sel, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
+                                  e->dubins, plan_out_dev, n_actions_out_dev);
+  else
+    drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 1,
+                           nullptr, plan_out_dev, n_actions_out_dev);
   return check_launch(e);
 }
 

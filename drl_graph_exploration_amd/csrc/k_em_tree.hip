@@ -49,6 +49,32 @@
 // not concerned, and the flag is not touched: a sampling failure is a result.  Loop bounds: cap accepted nodes, the two counters of
 // 1000, the waypoint bound.
 //
+//
+// THE DUBINS CONTROL MODEL (kDubins = true; rrt_planner only, launched when drlgx_set_dubins_library_host has loaded a library and the
+// sampler's Dubins flag is set - the kDubins = false instantiations are the code above, unchanged) replaces connectNode, restated
+// from the same file:
+//   the library (:1359-1414)     built by the engine on the host, SoA: the end point of every (v, w, duration) path from Pose2(0, 0, 0)
+//   sampleNode (:41-45, :110-115)   the generator has dimension 2: the same x, y in bases 2 and 3; the sample's theta is 0 and unread
+//   connectNodeDubinsPath (:157-176)   local = the sample in the parent's frame; the FIRST entry in library order with
+//                                |local - end_i| < tolerance_radius (strict) wins: lanes stride the library in index order, a ballot
+//                                per stride takes the lowest matching lane of the first stride that has one, and the scan ends
+//                                there.  A scan that cannot match is skipped: |local| > (max_i |end_i| + tolerance_radius)(1 +
+//                                2^-30) implies |local - end_i| > tolerance_radius for every i by the triangle inequality, the factor
+//                                covering the roundings of the three square roots many times over (an infinite bound switches the
+//                                skip off: drlgx_set_dubins_prefilter).  Every thread then integrates the entry's num_steps Euler
+//                                steps from the PARENT's pose - x += v dt cos, y += v dt sin, theta = atan2(sin, cos) + w dt, the
+//                                angle through (cos, sin) at every step as Pose2(x, y, theta) does; the node is the last pose
+//   isSafe(node, parent) (:59-70)   |safe_distance| < 1e-3 tests nothing; else poses 1 .. num_steps - 2 (the first and the last are
+//                                not tested) each pass isSafe(point): steps serially, landmarks in parallel, out at the first
+//                                unsafe one.  There is no waypoint loop, so a negative shrunk safe_distance is no deviation here
+//   connectNode (:179-265, :295-300)   no scaling to max_edge_length and no bearing test; no match or an unsafe pose refuses the
+//                                connect - the counter of 1000 runs at safe_distance = 0 too; key = parent.key + num_steps (the
+//                                node's depth counts STEPS), distance = parent.distance + v dt n + |w dt n| angle_weight
+//   the goal edge (:915)         connectNode(goal, node): the goal joins only if a library path from the node ends within
+//                                tolerance_radius of it and is safe - the goal NODE is that path's last pose; else SUCCESS, no plan
+// The node's edge record is (library index, num_steps, 0) instead of an odometry; k_em_leaves_dubins replays the steps for the plan.
+// Loop bounds: the library size, the largest num_steps, cap, the two counters of 1000.
+//
 // The live belief is only read.  Built with -ffp-contract=off: the nearest-node comparison and the safety tests are gates.
 #include "drlgx_dev.h"
 
@@ -156,15 +182,69 @@ __device__ __forceinline__ bool edge_safe(const Pose &child, const Pose &par, co
   return true;
 }
 
+// connectNodeDubinsPath's search: the lowest library index whose end point lies strictly within the tolerance radius of `local`, or
+// -1; the same answer in every thread.  At most ceil(n / kT) strides.
+__device__ __forceinline__ int dubins_match(const DrlgxDubins &lib, const P2 &local, int *red_i) {
+  if (sqrt(local.x * local.x + local.y * local.y) > lib.reach) return -1;  // (provably no match - see the head of the file)
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int base = 0; base < lib.n; base += kT) {
+    const int i = base + tid;
+    bool hit = false;
+    if (i < lib.n) {
+      const double dx = lib.end_x[i] - local.x, dy = lib.end_y[i] - local.y;
+      hit = sqrt(dx * dx + dy * dy) < lib.tol;
+    }
+    const unsigned long long b = __ballot(hit);
+    int first = b ? base + (tid - lane) + (int)__builtin_ctzll(b) : 0x7fffffff;
+    if (kWaves > 1) {
+      __syncthreads();  // (the previous round's readers are done)
+      if (lane == 0) red_i[tid >> 6] = first;
+      __syncthreads();
+      first = red_i[0];
+      for (int w = 1; w < kWaves; ++w) first = min(first, red_i[w]);
+    }
+    if (first != 0x7fffffff) return first;
+  }
+  return -1;
+}
+
+// One Euler step of the Dubins model, the angle through (cos, sin) as Pose2(x, y, theta) takes it
+__device__ __forceinline__ Pose dubins_step(const Pose &p, double vdt, double wdt) {
+  const double x = p.x + vdt * p.c, y = p.y + vdt * p.s, th = atan2(p.s, p.c) + wdt;
+  return Pose{x, y, cos(th), sin(th)};
+}
+
+// connectNode under the Dubins model from `par` towards `target`: false = refused (no library path, or an unsafe intermediate pose).
+// child: the path's last pose; m, ns: the library entry and its steps; edge: distanceBetweenNodes
+template <bool kSafe>
+__device__ __forceinline__ bool dubins_connect(const DrlgxDubins &lib, const Pose &par, const P2 &target, const Obstacles &ob, double sd,
+                                               double angle_weight, int *red_i, Pose &child, int &m, int &ns, double &edge) {
+  m = dubins_match(lib, transform_to(par, target), red_i);
+  if (m < 0) return false;
+  const double v = lib.v[m], w = lib.w[m];
+  ns = min(lib.num_steps[m], lib.max_steps);
+  const double vdt = v * lib.dt, wdt = w * lib.dt;
+  const bool test = kSafe && !(fabs(sd) < kEdgeEps);
+  child = par;
+  for (int step = 0; step < ns; ++step) {
+    child = dubins_step(child, vdt, wdt);
+    if (test && step >= 1 && step <= ns - 2 && !point_safe(P2{child.x, child.y}, ob, sd)) return false;
+  }
+  edge = vdt * (double)ns + fabs(wdt * (double)ns) * angle_weight;
+  return true;
+}
+
 // mode 0: optimize2's stop rule; 1: rrt_planner's.  goal_key / goal_xy: mode 1 only.  nodes_out (null: not wanted): per tree
 // [cap][8] = x y theta parent distance | the edge odometry from the parent (x y theta).  flag[0] (zeroed by the caller): the smallest DRLGX_E_* code any tree met.
 // kSafe: the obstacle logic with the planner parameter safe_distance (> 0); kSafe = false never reads it.
-template <bool kSafe>
+// kDubins: the Dubins control model with the library `lib` (mode 1 only; kDubins = false never reads it): a node's depth counts steps,
+// its act row is (library index, num_steps, 0), and lib.pose [tree][cap][4] receives the nodes' (x y cos sin) for k_em_leaves_dubins.
+template <bool kSafe, bool kDubins>
 __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
                                                 int mode, double max_nodes, double safe_distance, const int32_t *goal_key,
                                                 const double *goal_xy, double *act, int *link, int *leaf, int *meta, int *flag,
                                                 double *nodes_out, int32_t *n_nodes_out, int32_t *result_out,
-                                                int32_t *halton_next_out) {
+                                                int32_t *halton_next_out, DrlgxDubins lib) {
   extern __shared__ __attribute__((aligned(16))) double tree_smem[];
   const int tid = threadIdx.x, lane = tid & 63, ti = blockIdx.x;
   if (ti >= n_sel) return;
@@ -275,7 +355,7 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     // (no landmark: the reference's search answers 1, which is not below 0.)  The key against the NUMBER of landmarks, as written
     if (L > 0 && bk >= 0 && bk < L && bd < sd) sd = mode == 0 ? (bd - 0.1 > 0.0 ? bd - 0.1 : 0.0) : bd - 0.1;
     // the deviation: rrt_planner's waypoint loop would not end
-    if (mode == 1 && sd < -kEdgeEps) sampling_failed = true;
+    if (!kDubins && mode == 1 && sd < -kEdgeEps) sampling_failed = true;
     const double wb = 2.0 * cfg.max_edge_length / kEdgeEps + 2.0;
     wp_bound = wb < 2147483647.0 ? (int)wb : 0x7fffffff;
   }
@@ -284,7 +364,7 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
   const double span_x = cfg.map_max_x - cfg.map_min_x, span_y = cfg.map_max_y - cfg.map_min_y;
   int n = 1, count = halton_start[ti], max_depth = 0, goal_node = -1, failed = 0;
   bool full = false;  // the table filled before the stop rule was met
-  const long long max_turns = kSafe ? (long long)cap * (kMaxFailed + 2) : (long long)cap;
+  const long long max_turns = kSafe || kDubins ? (long long)cap * (kMaxFailed + 2) : (long long)cap;
   for (long long turn = 0; turn < max_turns && !sampling_failed; ++turn) {
     if (mode == 0 && n - 1 >= budget) break;
     if (n >= cap) {
@@ -327,6 +407,62 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
     }
     argmin_all(best, bi, red_d, red_i);
     if (bi < 0 || bi >= n) bi = 0;  // (only a NaN distance to every node could leave no winner)
+    if (kDubins) {
+      // connectNode under the Dubins model, every thread alike: the whole turn, the goal edge included
+      const Pose par{nd[kNd * bi], nd[kNd * bi + 1], nd[kNd * bi + 2], nd[kNd * bi + 3]};
+      const double pdist = nd[kNd * bi + 4];
+      const int pdepth = ni[kNi * bi + 1];
+      Pose child;
+      int m, ns;
+      double edge;
+      if (!dubins_connect<kSafe>(lib, par, sp, ob, sd, cfg.angle_weight, red_i, child, m, ns, edge)) {
+        if (++failed > kMaxFailed) {
+          sampling_failed = true;
+          break;
+        }
+        continue;
+      }
+      failed = 0;
+      const double dist = pdist + edge;
+      __syncthreads();  // (every thread has read the table)
+      if (tid == 0) {
+        nd[kNd * n] = child.x; nd[kNd * n + 1] = child.y; nd[kNd * n + 2] = child.c; nd[kNd * n + 3] = child.s;
+        nd[kNd * n + 4] = dist;
+        ni[kNi * n] = bi; ni[kNi * n + 1] = pdepth + ns; ni[kNi * n + 2] = 0;
+        ni[kNi * bi + 2] += 1;
+        ta[3 * n] = (double)m; ta[3 * n + 1] = (double)ns; ta[3 * n + 2] = 0.0;
+      }
+      __syncthreads();
+      max_depth = max(max_depth, pdepth + ns);
+      ++n;
+      const double gx = child.x - goal.x, gy = child.y - goal.y;
+      if (mode == 1 && sqrt(gx * gx + gy * gy) <= cfg.max_edge_length) {
+        if (n >= cap) {
+          full = true;
+          break;
+        }
+        Pose gp;
+        int gm, gns;
+        double gedge;
+        if (!dubins_connect<kSafe>(lib, child, goal, ob, sd, cfg.angle_weight, red_i, gp, gm, gns, gedge)) {
+          goal_refused = true;  // (:915: the loop ends all the same - SUCCESS, the goal not in the tree, no plan)
+          break;
+        }
+        if (tid == 0) {
+          nd[kNd * n] = gp.x; nd[kNd * n + 1] = gp.y; nd[kNd * n + 2] = gp.c; nd[kNd * n + 3] = gp.s;
+          nd[kNd * n + 4] = dist + gedge;
+          ni[kNi * n] = n - 1; ni[kNi * n + 1] = pdepth + ns + gns; ni[kNi * n + 2] = 0;
+          ni[kNi * (n - 1) + 2] += 1;
+          ta[3 * n] = (double)gm; ta[3 * n + 1] = (double)gns; ta[3 * n + 2] = 0.0;
+        }
+        __syncthreads();
+        goal_node = n;
+        max_depth = pdepth + ns + gns;  // (of the plan: the steps of the path to the goal)
+        ++n;
+        break;
+      }
+      continue;
+    }
     // connectNode, every thread alike
     const Pose par{nd[kNd * bi], nd[kNd * bi + 1], nd[kNd * bi + 2], nd[kNd * bi + 3]};
     const double pdist = nd[kNd * bi + 4];
@@ -400,6 +536,10 @@ __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const i
   for (int j = tid; j < n; j += kT) {
     tl[2 * j] = ni[kNi * j];
     tl[2 * j + 1] = ni[kNi * j + 1];
+    if (kDubins) {
+      double *o = lib.pose + ((size_t)ti * cap + j) * 4;
+      o[0] = nd[kNd * j]; o[1] = nd[kNd * j + 1]; o[2] = nd[kNd * j + 2]; o[3] = nd[kNd * j + 3];
+    }
     if (nodes_out) {
       double *o = nodes_out + ((size_t)ti * cap + j) * kNodeOut;
       o[0] = nd[kNd * j]; o[1] = nd[kNd * j + 1];
@@ -479,6 +619,44 @@ __global__ __launch_bounds__(64) void k_em_leaves(int n_sel, const int32_t *env_
   }
 }
 
+// rrt_planner's plan under the Dubins model: one row per STEP root -> goal, Edge::getOdoms (Planner2D.h:143-151) - between(previous
+// pose, this pose), the origin moving along -, the steps integrated again from the parent's stored pose and the node's library entry.
+// Row ti of the outputs; a tree without a goal node has no plan.  Lane q takes the q-th node of the path from the goal up (at most
+// cap - 1 parents); n_actions = the goal's depth in steps (<= A_max: a deeper path has refused the call).
+__global__ __launch_bounds__(64) void k_em_leaves_dubins(int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
+                                                         const int *meta, DrlgxDubins lib, double *actions, int32_t *n_actions) {
+  const int ti = blockIdx.x, lane = threadIdx.x;
+  if (ti >= n_sel) return;
+  const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
+  const double *ta = act + (size_t)ti * cap * 3, *tp = lib.pose + (size_t)ti * cap * 4;
+  const int *tl = link + (size_t)ti * cap * 2;
+  double *row = actions + (size_t)ti * A_max * 3;
+  const int total = nl > 0 ? tl[2 * leaf[(size_t)ti * cap] + 1] : 0;
+  for (int q = lane; q < 3 * A_max; q += 64)
+    if (q >= 3 * total) row[q] = 0.0;
+  if (lane == 0) n_actions[ti] = total;
+  if (nl == 0) return;
+  int j = leaf[(size_t)ti * cap];
+  for (int k = 0; k < lane && j > 0; ++k) j = tl[2 * j];
+  for (int turn = 0; turn < cap && j > 0; turn += 64) {
+    const int par = tl[2 * j], m = (int)ta[3 * j];
+    const int ns = min((int)ta[3 * j + 1], lib.max_steps), first = tl[2 * j + 1] - ns;
+    if (m >= 0 && m < lib.n && par >= 0 && par < cap) {
+      const double vdt = lib.v[m] * lib.dt, wdt = lib.w[m] * lib.dt;
+      Pose p{tp[4 * par], tp[4 * par + 1], tp[4 * par + 2], tp[4 * par + 3]};
+      for (int s = 0; s < ns; ++s) {
+        const Pose nx = dubins_step(p, vdt, wdt);
+        const Pose od = between(p, nx, nullptr);
+        if (first + s >= 0 && first + s < A_max) {
+          row[3 * (first + s)] = od.x; row[3 * (first + s) + 1] = od.y; row[3 * (first + s) + 2] = theta_of(od);
+        }
+        p = nx;
+      }
+    }
+    for (int k = 0; k < 64 && j > 0; ++k) j = tl[2 * j];
+  }
+}
+
 // optimize2's choice (Planner2D.cpp:1095-1111): per tree the first leaf in node order with the strictly smallest cost - the first
 // leaf is always taken, a NaN cost never replaces a held one.  One wave per tree.
 __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int *meta, const double *cost, const double *actions,
@@ -535,18 +713,33 @@ size_t drlgx_em_tree_lds_bytes(int cap) { return kemt::lds_bytes(cap); }
 void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
                           int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
                           double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
-                          int32_t *result_out, int32_t *halton_next_out) {
+                          int32_t *result_out, int32_t *halton_next_out, const DrlgxDubins *dubins) {
   static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree<false>), reinterpret_cast<const void *>(&kemt::k_em_tree<true>)};
-  drlgx_ensure_lds_attr(attr_set, fns, 2, 160 * 1024);
-  if (obstacles)
-    hipLaunchKernelGGL(kemt::k_em_tree<true>, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap,
-                       mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
-                       halton_next_out);
+  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree<false, false>), reinterpret_cast<const void *>(&kemt::k_em_tree<true, false>),
+                       reinterpret_cast<const void *>(&kemt::k_em_tree<false, true>), reinterpret_cast<const void *>(&kemt::k_em_tree<true, true>)};
+  drlgx_ensure_lds_attr(attr_set, fns, 4, 160 * 1024);
+  const DrlgxDubins lib = dubins ? *dubins : DrlgxDubins{};
+  if (dubins && obstacles)
+    hipLaunchKernelGGL((kemt::k_em_tree<true, true>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
+                       cap, mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out,
+                       result_out, halton_next_out, lib);
+  else if (dubins)
+    hipLaunchKernelGGL((kemt::k_em_tree<false, true>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
+                       cap, mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
+                       halton_next_out, lib);
+  else if (obstacles)
+    hipLaunchKernelGGL((kemt::k_em_tree<true, false>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
+                       cap, mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out,
+                       result_out, halton_next_out, lib);
   else
-    hipLaunchKernelGGL(kemt::k_em_tree<false>, dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start, cap,
-                       mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
-                       halton_next_out);
+    hipLaunchKernelGGL((kemt::k_em_tree<false, false>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
+                       cap, mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
+                       halton_next_out, lib);
+}
+void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
+                                   const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions) {
+  hipLaunchKernelGGL(kemt::k_em_leaves_dubins, dim3(n_sel), dim3(64), 0, st, n_sel, cap, A_max, act, link, leaf, meta, lib, actions,
+                     n_actions);
 }
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions) {

@@ -33,6 +33,7 @@ class Engine(object):
         self.device = torch.device("cuda", device)
         self.h = C.c_void_p()
         self.sampler_parameter, self.sampler_obstacles = (0.5, 0.0, False), False  # (the engine's values after drlgx_create)
+        self.dubins_parameter = None
         _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)), self.h)  # (NULL: the creation's error)
         r, c = C.c_int32(), C.c_int32()
         self.L.drlgx_vm_shape(self.h, C.byref(r), C.byref(c))
@@ -274,7 +275,8 @@ class Engine(object):
     def set_sampler_parameter(self, max_nodes, safe_distance=0.0, dubins_control_model_enabled=False):
         """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
         control model is stored and then refused by em_plan / rrt_plan (a safe_distance >= 0 is served once
-        set_sampler_obstacles(True) has opted in).  The values last set are kept in `sampler_parameter`."""
+        set_sampler_obstacles(True) has opted in; the Dubins control model is served by rrt_plan once set_dubins_library has loaded
+        a library).  The values last set are kept in `sampler_parameter`."""
         self._chk(self.L.drlgx_set_sampler_parameter(self.h, float(max_nodes), float(safe_distance), int(bool(dubins_control_model_enabled))))
         self.sampler_parameter = (float(max_nodes), float(safe_distance), bool(dubins_control_model_enabled))
 
@@ -285,6 +287,48 @@ class Engine(object):
         error).  Off, a non-zero safe_distance is refused as before.  The setting is kept in `sampler_obstacles`."""
         self._chk(self.L.drlgx_set_sampler_obstacles(self.h, int(bool(enabled))))
         self.sampler_obstacles = bool(enabled)
+
+    DUBINS_FIELDS = ("max_w", "dw", "min_v", "max_v", "dv", "dt", "min_duration", "max_duration", "tolerance_radius")
+
+    def set_dubins_library(self, parameter):
+        """The Dubins path library (drlgx_set_dubins_library_host), and with it the opt-in of the Dubins control model: `parameter`
+        is a planner2d.DubinsParameter (or any object / sequence with its nine fields in DUBINS_FIELDS order); None clears the
+        library.  The engine builds the library with the reference's loops; with one loaded and the Dubins flag of
+        set_sampler_parameter set, rrt_plan is served (one plan row per step, nodes columns 5-7 = library index, num_steps, 0);
+        em_plan stays refused.  Raises DrlgxError for parameters the engine refuses.  Returns the library's size."""
+        self.dubins_parameter = None  # (the nine values of the library loaded last, for callers that would load it again)
+        if parameter is None:
+            self._chk(self.L.drlgx_set_dubins_library_host(self.h, None))
+            return 0
+        vals = [float(getattr(parameter, f)) for f in self.DUBINS_FIELDS] if hasattr(parameter, "max_w") else [float(x) for x in parameter]
+        if len(vals) != 9:
+            raise ValueError("nine Dubins parameters expected: %s" % ", ".join(self.DUBINS_FIELDS))
+        arr = (C.c_double * 9)(*vals)
+        self._chk(self.L.drlgx_set_dubins_library_host(self.h, arr))
+        self.dubins_parameter = tuple(vals)
+        return self.dubins_library_size()
+
+    def dubins_library_size(self):
+        n = C.c_int32(0)
+        self._chk(self.L.drlgx_dubins_library(self.h, 0, C.byref(n), None, None, None, None))
+        return int(n.value)
+
+    def dubins_library(self):
+        """The library as the engine built it (drlgx_dubins_library), in library order: a dict of numpy arrays end [n, 3] (x, y,
+        theta), v, w [n] f64, num_steps [n] i32; n = 0 with no library loaded."""
+        n = self.dubins_library_size()
+        end, v, w = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+        steps = np.zeros(n, dtype=np.int32)
+        got = C.c_int32(0)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._chk(self.L.drlgx_dubins_library(self.h, n, C.byref(got), end.ctypes.data_as(dp), v.ctypes.data_as(dp), w.ctypes.data_as(dp),
+                                              steps.ctypes.data_as(ip)))
+        return dict(end=end, v=v, w=w, num_steps=steps)
+
+    def set_dubins_prefilter(self, enabled):
+        """The library scan's exact pre-filter (drlgx_set_dubins_prefilter; on after construction): off, every sample scans the
+        library; the results are the same."""
+        self._chk(self.L.drlgx_set_dubins_prefilter(self.h, int(bool(enabled))))
 
     def _tree_outputs(self, n, max_tree_nodes, want_nodes):
         dev, A = self.device, self.cfg.max_actions
@@ -317,7 +361,8 @@ class Engine(object):
         """EMPlanner2D::rrt_planner for the listed environments (drlgx_rrt_plan): the tree grown until a node lies within
         max_edge_length of the goal - graph node goal_key[i] if it is one (landmarks in key order, then poses), else the point
         goal_xy[i] -, the plan the path root -> goal.  A tree that fills max_tree_nodes first has result SAMPLING_FAILURE and
-        no actions.  Returns the dict of em_plan without cost / n_leaves."""
+        no actions.  Returns the dict of em_plan without cost / n_leaves.  Under the Dubins control model (set_dubins_library and the
+        sampler's Dubins flag) the plan has one row per step and nodes columns 5-7 are (library index, num_steps, 0)."""
         self.use_torch_stream()
         n = env_sel.numel()
         o = self._tree_outputs(n, max_tree_nodes, want_nodes)

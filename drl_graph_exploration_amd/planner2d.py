@@ -1,9 +1,10 @@
 """`planner2d` — the module surface of the reference's second pybind module (src/Planner2D.cpp:9-106) that the DRL
 scripts use: the parameter classes and enums, and `EMPlanner2D(parameter, sensor_model, control_model)` with
 `calculate_utility` / `line_planner` / `simulations_reward` over the engine of the simulation the models belong to
-(`ss2d.Simulator2D`), and the tree sampler of the non-Dubins planners: `optimize2`, `rrt_planner`, `iter_solution`
-(`drlgx_em_plan` / `drlgx_rrt_plan`).  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (SURVEY.md §8
-"out of scope")."""
+(`ss2d.Simulator2D`), and the tree sampler of the planners: `optimize2`, `rrt_planner`, `iter_solution`
+(`drlgx_em_plan` / `drlgx_rrt_plan`) for the non-Dubins control model and, behind the opt-in `dubins_paths`, `rrt_planner` with
+the Dubins control model (`get_dubins_path`, `iter_dubins_library`).  `optimize` and `iter_rrt` are outside the accelerated path
+(SURVEY.md §8 "out of scope")."""
 import enum
 import math
 
@@ -77,12 +78,18 @@ class EMPlannerParameter(object):
 
 
 class DubinsParameter(object):
-    """EMPlanner2D::DubinsParameter (src/Planner2D.cpp:12-22): carried for the ini reader; the Dubins path library is
-    outside the accelerated path."""
+    """EMPlanner2D::DubinsParameter (src/Planner2D.cpp:12-22): what Engine.set_dubins_library builds the path library from."""
 
     def __init__(self):
         self.max_w = self.dw = self.min_v = self.max_v = self.dv = self.dt = 0.0
         self.min_duration = self.max_duration = self.tolerance_radius = 0.0
+
+
+class Dubins(object):
+    """EMPlanner2D::Dubins as the binding shows it (src/Planner2D.cpp:24-29): one library path - v, w, end (Pose2), num_steps."""
+
+    def __init__(self, v, w, end, num_steps):
+        self.v, self.w, self.end, self.num_steps = float(v), float(w), end, int(num_steps)
 
 
 class EMPlanner2D(object):
@@ -93,15 +100,21 @@ class EMPlanner2D(object):
     (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0 - or, with the attribute `obstacle_logic` set,
     any safe_distance >= 0 with the reference's isSafe / retry / shrink logic; it is an opt-in because the default refusal is what
     existing callers and tests rely on) and `iter_solution` walks the best path as the reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
-    call.  `optimize`, the Dubins library and `iter_rrt` are outside the accelerated path (out of scope)."""
+    call.  With the attribute `dubins_paths` set (an opt-in for the same reason) and `dubins_control_model_enabled`, `set_parameter`
+    loads `parameter.dubins_parameter` as the engine's Dubins library and `rrt_planner` runs the Dubins control model: an edge's
+    `get_odoms()` is then one odometry per step, a node's `poses` the step poses; `get_dubins_path(i)` / `iter_dubins_library()`
+    read the library; `optimize2` raises.  `optimize` and `iter_rrt` are outside the accelerated path."""
     MAX_TREE_NODES = 2048  # the node capacity of one tree (the engine's maximum)
     OptimizationAlgorithm = OptimizationAlgorithm
     OptimizationResult = OptimizationResult
     obstacle_logic = False  # True: the sampler's obstacle logic (Engine.set_sampler_obstacles) - a non-zero safe_distance is served
+    dubins_paths = False    # True: the Dubins control model (Engine.set_dubins_library) - rrt_planner serves dubins_control_model_enabled
 
-    def __init__(self, parameter, sensor_model, control_model, obstacle_logic=False):
+    def __init__(self, parameter, sensor_model, control_model, obstacle_logic=False, dubins_paths=False):
         if obstacle_logic:
             self.obstacle_logic = True
+        if dubins_paths:
+            self.dubins_paths = True
         self._ses = sensor_model._session
         if self._ses is None or control_model._session is not self._ses:
             raise ValueError("the sensor and control models must come from one Simulator2D")
@@ -120,6 +133,8 @@ class EMPlanner2D(object):
                                                    parameter.occupancy_threshold, parameter.max_edge_length, int(parameter.algorithm))
             self._ses.engine.set_sampler_parameter(parameter.max_nodes, parameter.safe_distance, parameter.dubins_control_model_enabled)
             self._ses.engine.set_sampler_obstacles(self.obstacle_logic)
+            if self.dubins_paths and parameter.dubins_control_model_enabled:
+                load_dubins_library(self._ses.engine, parameter.dubins_parameter)
 
     @staticmethod
     def calculate_utility(virtual_map, distance, parameter):
@@ -200,11 +215,11 @@ class EMPlanner2D(object):
         ce = torch.zeros(1, dtype=torch.int32, device=e.device)
         return e, ce, acts.to(e.device), n
 
-    def _tree_call(self, run):
+    def _tree_call(self, run, rrt=False):
         """One sampler call for the wrapped simulation: the parameter object as it is now, the Halton index carried on, the best
         path kept for iter_solution."""
         import torch
-        _require_sampler_scope(self._parameter, self.obstacle_logic)
+        _require_sampler_scope(self._parameter, self.obstacle_logic, self.dubins_paths and rrt)
         e = self._ses.require_engine()
         self.set_parameter(self._parameter)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
@@ -213,7 +228,7 @@ class EMPlanner2D(object):
         e.check_status()
         plan, n_act, result, nxt, nodes, n_nodes = e.fetch(o["plan"], o["n_actions"], o["result"], o["halton_next"], o["nodes"], o["n_nodes"])
         self.halton_next = int(nxt[0])
-        self._solution = _solution_edges(e, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        self._solution = solution_edges(e, self._parameter, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
         return OptimizationResult(int(result[0]))
 
     def optimize2(self, slam, virtual_map):
@@ -230,7 +245,7 @@ class EMPlanner2D(object):
             key = torch.tensor([int(n_key)], dtype=torch.int32, device=e.device)
             xy = torch.tensor([[float(fron_0), float(fron_1)]], dtype=torch.float64, device=e.device)
             return e.rrt_plan(sel, key, xy, start, self.MAX_TREE_NODES, want_nodes=True)
-        return self._tree_call(run)
+        return self._tree_call(run, rrt=True)
 
     def iter_solution(self):
         """The edges of the best path from the best node back to the root (EMPlanner2D::BackwardIterator, Planner2D.h:200-257), each
@@ -238,18 +253,48 @@ class EMPlanner2D(object):
         return iter(self._solution)
 
     def _out_of_scope(self, *a, **k):
-        raise NotImplementedError("optimize (RRT*), the Dubins library and iter_rrt are outside the accelerated path")
+        raise NotImplementedError("optimize (RRT*), the Dubins library (without the opt-in dubins_paths) and iter_rrt are outside "
+                                  "the accelerated path")
 
-    optimize = iter_rrt = get_dubins_path = _out_of_scope
+    optimize = iter_rrt = _out_of_scope
+
+    def iter_dubins_library(self):
+        """The Dubins library in library order (src/Planner2D.cpp:101-103), as the engine built it."""
+        if not self.dubins_paths:
+            self._out_of_scope()
+        return iter(dubins_library(self._ses.require_engine()))
+
+    def get_dubins_path(self, *index):
+        """EMPlanner2D::getDubinsPath(i): entry `i` of the library."""
+        if not self.dubins_paths:
+            self._out_of_scope()
+        return dubins_library(self._ses.require_engine())[int(index[0])]
 
 
-def _require_sampler_scope(parameter, obstacle_logic=False):
+def load_dubins_library(engine, dubins_parameter):
+    """Engine.set_dubins_library unless the engine already holds the library of these nine values."""
+    if dubins_parameter is None:
+        raise ValueError("dubins_control_model_enabled needs parameter.dubins_parameter (the [Dubins] section)")
+    vals = tuple(float(getattr(dubins_parameter, f)) for f in engine.DUBINS_FIELDS)
+    if engine.dubins_parameter != vals:
+        engine.set_dubins_library(vals)
+
+
+def dubins_library(engine):
+    """The engine's library as a list of Dubins."""
+    from . import ss2d
+    lib = engine.dubins_library()
+    return [Dubins(lib["v"][i], lib["w"][i], ss2d.Pose2(*lib["end"][i]), lib["num_steps"][i]) for i in range(len(lib["v"]))]
+
+
+def _require_sampler_scope(parameter, obstacle_logic=False, dubins_rrt=False):
     """The sampler serves the non-Dubins control model at safe_distance = 0 (the engine refuses anything else with
     DRLGX_E_INVALID); the facades say so the way they say it for everything outside the accelerated path.  With `obstacle_logic`
-    (the opt-in) any safe_distance >= 0 passes; the Dubins control model still raises."""
-    if parameter.dubins_control_model_enabled:
-        raise NotImplementedError("the tree sampler runs for the non-Dubins control model only (Dubins paths are outside the "
-                                  "accelerated path)")
+    (the opt-in) any safe_distance >= 0 passes; the Dubins control model raises unless `dubins_rrt`: the caller is rrt_planner and
+    has opted in to Dubins paths."""
+    if parameter.dubins_control_model_enabled and not dubins_rrt:
+        raise NotImplementedError("the tree sampler runs the Dubins control model for rrt_planner only, behind the opt-in "
+                                  "dubins_paths=True (optimize2 under Dubins paths is outside the accelerated path)")
     if obstacle_logic:
         if parameter.safe_distance < 0:
             raise ValueError("safe_distance must not be negative")
@@ -261,22 +306,61 @@ def _require_sampler_scope(parameter, obstacle_logic=False):
 class Node(object):
     """EMPlanner2D::Node as the binding shows it (src/Planner2D.cpp:51-60): key, state, poses, distance."""
 
-    def __init__(self, key, pose, distance):
+    def __init__(self, key, pose, distance, poses=None):
         from . import ss2d
         self.key, self.distance = int(key), float(distance)
         self.state = ss2d.VehicleBeliefState(pose)
-        self.poses = [pose] if key >= 0 else []
+        self.poses = poses if poses is not None else ([pose] if key >= 0 else [])
 
 
 class Edge(object):
     """EMPlanner2D::Edge (Planner2D.h:128-152): `get_odoms()` = the odometry from `first` to each pose of `second` - one pose, the
-    edge's action, for the non-Dubins control model."""
+    edge's action, for the non-Dubins control model; one odometry per step, the origin moving along, for the Dubins model."""
 
     def __init__(self, first, second, odom):
-        self.first, self.second, self._odom = first, second, odom
+        self.first, self.second, self._odoms = first, second, odom if isinstance(odom, list) else [odom]
 
     def get_odoms(self):
-        return [self._odom]
+        return list(self._odoms)
+
+
+def solution_edges(engine, parameter, plan, nodes):
+    """The best path's edges, leaf first, for the control model of `parameter`."""
+    if parameter.dubins_control_model_enabled:
+        return _dubins_solution_edges(engine, parameter, plan, nodes)
+    return _solution_edges(engine, plan, nodes)
+
+
+def _dubins_solution_edges(engine, parameter, plan, nodes):
+    """rrt_planner under the Dubins model: the goal node is the last node of the tree when there is a plan; a node's columns 5-7
+    are (library index, num_steps, 0) and the plan holds one row per step, root -> goal.  A node's poses are its steps from the
+    parent's pose (connectNodeDubinsPath, Planner2D.cpp:157-176)."""
+    from . import ss2d
+    if len(plan) == 0:
+        return []
+    lib = engine.dubins_library()
+    dt = float(parameter.dubins_parameter.dt)
+    root_key = engine.counts(0)["poses"] - 1
+    path = [len(nodes) - 1]
+    while path[-1] > 0:
+        path.append(int(nodes[path[-1], 3]))
+    path.reverse()  # root .. goal
+    if sum(int(nodes[j, 6]) for j in path[1:]) != len(plan):
+        raise RuntimeError("the plan is not the path to the tree's last node")
+    made = {0: Node(root_key, ss2d.Pose2(nodes[0, 0], nodes[0, 1], nodes[0, 2]), nodes[0, 4])}
+    edges, row = [], 0
+    for par, j in zip(path[:-1], path[1:]):
+        m, ns = int(nodes[j, 5]), int(nodes[j, 6])
+        v, w = float(lib["v"][m]), float(lib["w"][m])
+        x, y, th = float(nodes[par, 0]), float(nodes[par, 1]), float(nodes[par, 2])
+        poses = []
+        for _ in range(ns):
+            x, y, th = x + v * dt * math.cos(th), y + v * dt * math.sin(th), math.atan2(math.sin(th), math.cos(th)) + w * dt
+            poses.append(ss2d.Pose2(x, y, math.atan2(math.sin(th), math.cos(th))))
+        made[j] = Node(made[par].key + ns, ss2d.Pose2(nodes[j, 0], nodes[j, 1], nodes[j, 2]), nodes[j, 4], poses)
+        edges.insert(0, Edge(made[par], made[j], [ss2d.Pose2(*plan[row + s]) for s in range(ns)]))
+        row += ns
+    return edges
 
 
 def _solution_edges(engine, plan, nodes):

@@ -66,6 +66,10 @@ def config_from_ini(cp, max_poses=256, max_actions=None, max_snapshots=1):
         pp.algorithm = planner2d.OptimizationAlgorithm[cp.get("Planner", "algorithm")]
         if cp.has_option("Planner", "dubins_control_model_enabled"):
             pp.dubins_control_model_enabled = cp.getboolean("Planner", "dubins_control_model_enabled")
+        if pp.dubins_control_model_enabled and cp.has_section("Dubins"):  # read_dubins_params (scripts/envs/pyplanner2d.py:9-20)
+            pp.dubins_parameter = planner2d.DubinsParameter()
+            for k in ("max_w", "dw", "min_v", "max_v", "dv", "dt", "min_duration", "max_duration", "tolerance_radius"):
+                setattr(pp.dubins_parameter, k, cp.getfloat("Dubins", k))
     c = DrlgxConfig()
     c.bearing_noise, c.range_noise = sp.bearing_noise, sp.range_noise
     c.min_bearing, c.max_bearing, c.min_range, c.max_range = sp.min_bearing, sp.max_bearing, sp.min_range, sp.max_range
@@ -268,19 +272,21 @@ class _Planner(object):
         self.halton_next = planner2d.halton_start_index(owner._planner_params.seed)
         self._solution = []
 
-    def _call(self, run):
+    def _call(self, run, rrt=False):
         o, pp = self._o, self._o._planner_params
-        planner2d._require_sampler_scope(pp, o.obstacle_logic)
+        planner2d._require_sampler_scope(pp, o.obstacle_logic, o.dubins_paths and rrt)
         e = o.engine
         e.set_sampler_parameter(pp.max_nodes, pp.safe_distance, pp.dubins_control_model_enabled)
         e.set_sampler_obstacles(o.obstacle_logic)
+        if o.dubins_paths and pp.dubins_control_model_enabled:
+            planner2d.load_dubins_library(e, pp.dubins_parameter)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
         start = torch.tensor([self.halton_next], dtype=torch.int32, device=e.device)
         out = run(e, sel, start)
         plan, n_act, result, nxt, nodes, n_nodes = e.fetch(out["plan"], out["n_actions"], out["result"], out["halton_next"], out["nodes"],
                                                            out["n_nodes"])
         self.halton_next = int(nxt[0])
-        self._solution = planner2d._solution_edges(e, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        self._solution = planner2d.solution_edges(e, pp, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
         self.last = out
         return planner2d.OptimizationResult(int(result[0]))
 
@@ -295,19 +301,32 @@ class _Planner(object):
             key = torch.tensor([int(n_key)], dtype=torch.int32, device=e.device)
             xy = torch.tensor([[float(fron_0), float(fron_1)]], dtype=torch.float64, device=e.device)
             return e.rrt_plan(sel, key, xy, start, cap, want_nodes=True)
-        return self._call(run)
+        return self._call(run, rrt=True)
 
     def iter_solution(self):
         return iter(self._solution)
+
+    def iter_dubins_library(self):
+        if not self._o.dubins_paths:
+            raise NotImplementedError("the Dubins library is an opt-in: dubins_paths=True")
+        planner2d.load_dubins_library(self._o.engine, self._o._planner_params.dubins_parameter)
+        return iter(planner2d.dubins_library(self._o.engine))
+
+    def get_dubins_path(self, index):
+        return list(self.iter_dubins_library())[int(index)]
 
 
 class EMExplorer(SS2D):
     """scripts/envs/pyplanner2d.py:57-84.  `obstacle_logic` (an opt-in, off by default): plan() / rrt_plan() run the planner's
     safe_distance as the ini file gives it, with the sampler's obstacle logic (Engine.set_sampler_obstacles); off, a non-zero
-    planner safe_distance raises NotImplementedError as before."""
+    planner safe_distance raises NotImplementedError as before.  `dubins_paths` (an opt-in too): with `[Planner]
+    dubins_control_model_enabled = true` rrt_plan() runs the Dubins control model with the ini file's [Dubins] library
+    (Engine.set_dubins_library), an edge's get_odoms() then holds one odometry per step; plan() raises; off, the flag raises
+    NotImplementedError as before.  Executing the intermediate steps (simulate(core=False)) stays outside the accelerated path."""
 
     def __init__(self, *args, **kwargs):
         self.obstacle_logic = bool(kwargs.pop("obstacle_logic", False))
+        self.dubins_paths = bool(kwargs.pop("dubins_paths", False))
         super(EMExplorer, self).__init__(*args, **kwargs)
         self._planner = _Planner(self)
 

@@ -217,16 +217,32 @@ class VecExplorationEnv(object):
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]
 
-    def rrt_plan(self, goal_key, frontier, max_tree_nodes=2048, planner_seed=0, safe_distance=None):
+    def rrt_plan(self, goal_key, frontier, max_tree_nodes=2048, planner_seed=0, safe_distance=None, dubins=None):
         """ExplorationEnv.rrt_plan for all envs in one call (EMPlanner2D::rrt_planner, Engine.rrt_plan): goal_key [n_envs] i32 (a graph
         node if it is one), frontier [n_envs, 2] f64 (the goal otherwise), on the device.  Returns like em_plan; an env whose tree
         fills max_tree_nodes before it reaches the goal has result SAMPLING_FAILURE and no actions.  `safe_distance`: as em_plan's
-        (a goal whose edge is unsafe gives SUCCESS with no actions, as the reference's empty solution)."""
+        (a goal whose edge is unsafe gives SUCCESS with no actions, as the reference's empty solution).  `dubins` (a
+        planner2d.DubinsParameter; None: the non-Dubins control model as before): this call runs the Dubins control model with that
+        library (Engine.set_dubins_library, kept loaded for the next such call) - the actions are then one odometry per step - and
+        the engine's Dubins flag comes back after it."""
         sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
         start = self._halton(planner_seed)
-        o = self._with_safe_distance(None, safe_distance,
-                                     lambda: self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(),
-                                                                  frontier.to(torch.float64).contiguous(), start, max_tree_nodes))
+        run = lambda: self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(), frontier.to(torch.float64).contiguous(), start,
+                                           max_tree_nodes)
+        if dubins is not None:
+            from .planner2d import load_dubins_library
+            plain = run
+
+            def run():
+                e = self.engine
+                load_dubins_library(e, dubins)
+                now = e.sampler_parameter
+                e.set_sampler_parameter(now[0], now[1], True)
+                try:
+                    return plain()
+                finally:
+                    e.set_sampler_parameter(*now)
+        o = self._with_safe_distance(None, safe_distance, run)
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]
 

@@ -223,7 +223,8 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
 /* The planner parameters only the tree sampler reads (EMPlanner2D::Parameter, scripts/envs/pyplanner2d.py:29, :35, :50): max_nodes
  * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
  * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
- * drlgx_em_plan / drlgx_rrt_plan (a safe_distance > 0 is served once drlgx_set_sampler_obstacles, below, has opted in).  After
+ * drlgx_em_plan / drlgx_rrt_plan (a safe_distance > 0 is served once drlgx_set_sampler_obstacles, below, has opted in; the Dubins
+ * control model is served by drlgx_rrt_plan once drlgx_set_dubins_library_host, below, has loaded a library).  After
  * drlgx_create: max_nodes 0.5, safe_distance 0, Dubins off. */
 int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_distance, int dubins_control_model_enabled);
 /* The sampler's obstacle logic, an OPT-IN (default 0: every call behaves as described above and below, a non-zero safe_distance is
@@ -251,9 +252,49 @@ int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_d
  * that tree at once with SAMPLING_FAILURE, an empty plan and its Halton index unchanged.
  * A tree that ends with SAMPLING_FAILURE reports result 0, n_actions 0, no leaves, the nodes accepted so far in n_nodes / nodes_out,
  * and in halton_next the index after the last drawn point; the other trees of the call are not concerned, it offers no candidate to
- * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  Dubins paths, optimize (RRT*) and
- * SLAM_OG_SHANNON stay out of scope. */
+ * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  optimize (RRT*) and
+ * SLAM_OG_SHANNON stay out of scope; Dubins paths are served for drlgx_rrt_plan only (below). */
 int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled);
+/* The Dubins control model's path library (EMPlanner2D::initializeDubinsPathLibrary, Planner2D.cpp:1359-1414), and with it the
+ * OPT-IN of that control model: with no library loaded the Dubins flag of drlgx_set_sampler_parameter is refused as before.
+ * params: HOST double[9] = max_w, dw, min_v, max_v, dv, dt, min_duration, max_duration, tolerance_radius (the [Dubins] section of the
+ * planner's ini file, EMPlanner2D::DubinsParameter); NULL clears the library.  The engine builds the library in doubles with the
+ * reference's loops, in the reference's order - v from max_v while v > min_v - 1e-10 by v -= dv; w from 0 while w < max_w + 1e-10
+ * by w += dw; sign -1 then +1 (w = 0 is listed twice, as -0 and +0); from Pose2(0, 0, 0) and t = 0, while t < max_duration:
+ * num_steps++, x += v dt cos(theta), y += v dt sin(theta), theta = atan2(sin, cos) + sign w dt (the angle goes through (cos, sin)
+ * at every step, as Pose2(x, y, theta) takes it), t += dt, and an entry {v, sign w, num_steps, end = the pose} whenever
+ * t > min_duration (strict).  The counts come from that repeated addition, not from a division.
+ * DRLGX_E_INVALID: a non-positive or non-finite max_w, dw, dv, dt or tolerance_radius, max_v < min_v, or parameters that give no
+ * entry.  DRLGX_E_CAPACITY: more than 131 072 entries (the shipped [Dubins] section gives 78 030), a path of more than 4 096
+ * steps, or more than 2^20 (v, w) pairs; the library loaded before is then kept.
+ * With a library loaded and the Dubins flag set, drlgx_rrt_plan is served at safe_distance = 0, or >= 0 under
+ * drlgx_set_sampler_obstacles; drlgx_em_plan still returns DRLGX_E_INVALID (its leaf scoring treats every action as a core pose
+ * with measurements, the reference's Dubins edges have non-core steps).  What changes in the tree (Planner2D.cpp):
+ *   sampleNode (:41-45, :110-115): the same x, y (Halton bases 2 and 3); the sample's theta is 0 and is not read;
+ *   connectNodeDubinsPath (:157-176): local = the sample in the parent's frame; the FIRST entry in library order with
+ *     |local - end_i| < tolerance_radius (strict) wins; the node's poses are num_steps Euler steps of that (v, w) from the parent's
+ *     pose, the node is the last of them; no entry: the connect is refused;
+ *   connectNode (:179-265): no scaling to max_edge_length, no bearing test; isSafe(node, parent) (:59-70): safe at once if
+ *     |safe_distance| < 1e-3, else poses 1 .. num_steps - 2 must each pass isSafe(point) - the first and the last are not tested;
+ *     distance = parent.distance + v dt n + |w dt n| angle_weight (:295-300); key = parent.key + n: a node's depth counts steps;
+ *   a refused connect counts towards the 1001 in a row that end the tree with SAMPLING_FAILURE, at safe_distance = 0 too;
+ *   the goal edge (:915): the goal joins the tree only if a library path from the node that reached it ends within
+ *     tolerance_radius of the goal and is safe - the goal node is then that path's last pose; otherwise the result is SUCCESS with
+ *     n_actions 0, as for a refused goal edge;
+ *   the shrink of drlgx_rrt_plan is unclamped as before; there is no waypoint loop, so a negative shrunk safe_distance is served
+ *     (a negative radius finds no landmark).
+ * The plan (Edge::getOdoms, Planner2D.h:143-151) has one row per STEP, root -> goal: between(previous pose, this pose); n_actions
+ * is the total number of steps, and a path of more steps than max_actions refuses the call with DRLGX_E_CAPACITY (live state and
+ * the status word untouched).  nodes_out keeps 8 columns: x, y, theta, parent, distance as before, columns 5-7 are (library index,
+ * num_steps, 0) instead of an edge odometry. */
+int drlgx_set_dubins_library_host(drlgx_engine *e, const double *params);
+/* The library as loaded: *n_out = its size (0: none); up to `capacity` entries of end_xytheta [.][3], v, w, num_steps (HOST arrays,
+ * each may be NULL). */
+int drlgx_dubins_library(drlgx_engine *e, int capacity, int32_t *n_out, double *end_xytheta, double *v, double *w, int32_t *num_steps);
+/* The library scan's exact pre-filter (default on): a sample whose position in the parent's frame lies farther from the origin than
+ * (the largest |end_i| + tolerance_radius)(1 + 2^-30) cannot match any entry (triangle inequality), so the scan is skipped.
+ * enabled = 0 scans every time; the results are identical (tests compare them). */
+int drlgx_set_dubins_prefilter(drlgx_engine *e, int enabled);
 /* EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1043-1128) for the n_sel environments env_sel_dev names: per environment
  * one tree grown on the device from its live belief (k_em_tree.hip) -
  *   initialize (:1281-1357): root = the current pose estimate; max_nodes_ = floor(#{p_v < occupancy_threshold} * max_nodes);
@@ -291,7 +332,8 @@ int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const 
  * (landmarks in key order, then poses: the node order of drlgx_graph), else the frontier point goal_xy[i].
  * goal_key_dev int32[n_sel]; goal_xy_dev double[n_sel*2]; the other arrays as above.  A tree that fills max_tree_nodes without
  * reaching its goal reports SAMPLING_FAILURE in result_out_dev with n_actions_out = 0 (the call itself returns DRLGX_OK);
- * DRLGX_E_CAPACITY: a path to a goal longer than max_actions.  One synchronisation (the capacity flag). */
+ * DRLGX_E_CAPACITY: a path to a goal longer than max_actions.  One synchronisation (the capacity flag).  Under the Dubins control
+ * model (drlgx_set_dubins_library_host) the plan has one row per step and nodes_out columns 5-7 are (library index, num_steps, 0). */
 int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *goal_key_dev, const double *goal_xy_dev,
                    const int32_t *halton_start_dev, int max_tree_nodes, double *plan_out_dev, int32_t *n_actions_out_dev,
                    int32_t *result_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev);
