@@ -389,9 +389,10 @@ __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const i
         for (int r = 0; r < 3; ++r)
           for (int q = 0; q < 3; ++q) base[r * 3 + q] = Sig[(size_t)(3 * i + r) * n + 3 * i + q];
       double *o = out + (size_t)i * 9;
+      // (the upper triangle, mirrored: the Gauss-Jordan prior and the chain's products are symmetric only up to round-off)
       o[0] = base[0] - acc[0]; o[1] = base[1] - acc[1]; o[2] = base[2] - acc[2];
-      o[3] = base[3] - acc[1]; o[4] = base[4] - acc[3]; o[5] = base[5] - acc[4];
-      o[6] = base[6] - acc[2]; o[7] = base[7] - acc[4]; o[8] = base[8] - acc[5];
+      o[3] = o[1];             o[4] = base[4] - acc[3]; o[5] = base[5] - acc[4];
+      o[6] = o[2];             o[7] = o[5];             o[8] = base[8] - acc[5];
     }
     __builtin_amdgcn_wave_barrier();
   }
