@@ -29,6 +29,7 @@ struct DrlgxState {
   int n_envs, n_inst, n_roll;  // instances: [0,n_envs) live, [n_envs, 2 n_envs) look-ahead bases, then rollouts
   int P_max, L_max, M_max, LG, V, Vu, rows, cols, A_max;  // Vu = V rounded up to 4 (byte plane stride)
   int win;  // (win x win) candidate window of cells around a pose = ceil(2*max_range/res)+1
+  int disc_cells;  // host's upper bound on the cell centres within max_range of a pose, wherever it stands (disc_cells_bound)
   int count_explored;
   double lo_free, lo_occ, lo_min, lo_max, occ_thresh;  // log-odds constants computed on the HOST (bit-exact ladder)
   int bbox_noop;   // 1: the sector-sweep bounding box provably contains every in-range cell (full-circle FOV)
@@ -708,6 +709,7 @@ void drlgx_launch_step_arrow_loop(const DrlgxState &S, hipStream_t st, LaunchSel
 // rebuild 0: the reductions only, over the map as it stands (after a reset: the untouched map)
 void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel, int rebuild);
 bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound);
+bool drlgx_map_compact_ok(const DrlgxState &S, int p_bound);
 void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t st, int n, const int32_t *src,
                        const int32_t *dst, int src_off, int dst_off, int skip_mask,  // skip fields with cls & mask
                        const int *cnt = nullptr,  // S.cnt: copy the live part of per-pose / -landmark / -factor fields only

@@ -256,6 +256,28 @@ static void read_env_switches(drlgx_engine *e) {
 static double p2l(double p) { return std::log(p / (1.0 - p)); }
 static double l2p(double l) { return std::exp(l) / (1.0 + std::exp(l)); }
 
+// Upper bound on the lattice points an open disc of radius r (in cells) holds, wherever its centre lies.  By the lattice's
+// symmetries the centre may be taken in [0, 1/2]^2; that square is covered by 32 x 32 sub-squares of side h = 1 / 64, every centre lies
+// within h / sqrt(2) of the middle of one, so the disc around it lies inside the disc of radius r + h / sqrt(2) around that middle:
+// the largest count over the 1024 middles bounds every centre's.  (3.0 cells, the default sensor at resolution 2: 32, the true
+// maximum; 3.5 cells: 41 - reached 0.2 to 0.35 cell off a lattice point along one axis.)
+static int disc_cells_bound(double r) {
+  const int n = 32;
+  const double h = 0.5 / n, rr = r + h * 0.70710678118654752440 + 1e-9;
+  const int k = (int)std::ceil(rr) + 1;
+  int best = 0;
+  for (int a = 0; a < n; ++a)
+    for (int b = 0; b < n; ++b) {
+      const double u = (a + 0.5) * h, v = (b + 0.5) * h;
+      int cnt = 0;
+      for (int i = -k; i <= k; ++i)
+        for (int j = -k; j <= k; ++j)
+          if ((i - u) * (i - u) + (j - v) * (j - v) <= rr * rr) ++cnt;
+      best = std::max(best, cnt);
+    }
+  return best;
+}
+
 // capacities, map geometry and the log-odds / noise constants
 static int set_map_constants(drlgx_engine *e) {
   DrlgxState &S = e->S;
@@ -285,6 +307,8 @@ static int set_map_constants(drlgx_engine *e) {
     e->last_error = "max_range / resolution too large for the 64-lane cell window";
     return DRLGX_E_INVALID;
   }
+  // in-range cells per pose (the map kernel's compact form has room for kmap::kPairsPerPose of them: map_lds_bytes_compact)
+  S.disc_cells = disc_cells_bound(cfg->max_range / cfg->resolution);
   // log-odds constants (OccupancyMap.h:10-19) evaluated with the HOST libm: exact ladder values
   S.lo_free = p2l(0.3);
   S.lo_occ = p2l(0.7);
@@ -1581,6 +1605,16 @@ int drlgx_get_cov_traces_host(drlgx_engine *e, int inst, double *lm_trace, doubl
   if (pose_trace)
     for (int i = 0; i < P; ++i) pose_trace[i] = pt[i];
   return DRLGX_OK;
+}
+
+int drlgx_debug_disc_cells_bound(double radius_cells) {
+  if (!(radius_cells >= 0.0 && radius_cells <= 64.0)) return DRLGX_E_INVALID;
+  return disc_cells_bound(radius_cells);
+}
+
+int drlgx_debug_map_compact_ok(const drlgx_engine *e, int p_bound) {
+  if (!e) return DRLGX_E_INVALID;
+  return drlgx_map_compact_ok(e->S, p_bound) ? 1 : 0;
 }
 
 int drlgx_vm_shape(const drlgx_engine *e, int *rows, int *cols) {

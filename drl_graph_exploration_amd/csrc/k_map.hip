@@ -750,7 +750,7 @@ __device__ __forceinline__ void map_body(const DrlgxState &S, const LaunchSel &s
       pair_list(S, c, c0, nc);
       if (c0 == 0) DRLGX_PROF(S, 43);
       const int npairs = *c.pcount;
-      if (kCompact && npairs > nc * kPairsPerPose) {  // (cannot happen for a disc-shaped footprint: flag it, leave the map alone)
+      if (kCompact && npairs > nc * kPairsPerPose) {  // (the host launches this form only when no disc can hold more: flag it, leave the map alone)
         if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
         return;
       }
@@ -793,9 +793,11 @@ size_t drlgx_map_lds_bytes(const DrlgxState &S, int *chunk_out, int pcap) {
   return map_lds_bytes(S, chunk, pc);
 }
 
-// the compact carve for the launch's pose bound, if it lets two workgroups share a CU (<= 80 KB each): bytes, else 0
+// the compact carve for the launch's pose bound, if it lets two workgroups share a CU (<= 80 KB each): bytes, else 0.  Its stage
+// holds kPairsPerPose in-range cells per pose: a sensor whose disc can hold more (S.disc_cells, the host's bound: 41 at a radius of
+// 3.5 cells, the 8-cell window) is served by the resident form, whose stage has a slot per window cell
 static size_t map_lds_bytes_compact(const DrlgxState &S, int pcap, int *chunk_out) {
-  if (!S.bbox_noop) return 0;
+  if (!S.bbox_noop || S.disc_cells > kmap::kPairsPerPose) return 0;
   const int pc = pcap > 0 && pcap < S.P_max ? pcap : S.P_max;
   const int chunk = pc < 64 ? pc : 64;
   const size_t b = map_lds_bytes(S, chunk, pc, true);
@@ -822,9 +824,11 @@ extern "C" int drlgx_debug_map_form(int form) {
 
 // true when a rebuild launch of more instances than CUs would run the two-workgroups-per-CU form (the engine then keeps the map
 // stage out of the fused step kernel and launches it separately)
-bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound) {
+bool drlgx_map_two_per_cu(const DrlgxState &S, int p_bound) { return map_form() != 0 && drlgx_map_compact_ok(S, p_bound); }
+// true when the compact form serves this engine's sensor and map at the pose bound (drlgx_debug_map_compact_ok)
+bool drlgx_map_compact_ok(const DrlgxState &S, int p_bound) {
   int cchunk = 0;
-  return map_form() != 0 && map_lds_bytes_compact(S, p_bound, &cchunk) != 0;
+  return map_lds_bytes_compact(S, p_bound, &cchunk) != 0;
 }
 
 void drlgx_launch_map(const DrlgxState &S, hipStream_t st, LaunchSel sel, int rebuild) {

@@ -15,7 +15,8 @@ constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = 64;         // candidate cells per pose: an 8 x 8 slot grid whatever the window width W <= 8
 constexpr int kPairsPerPose = 40;  // in-range cells per pose the compact stage has room for (the disc of radius max_range
-                                   // holds ~28 cell centres of the 7 x 7 window, never more than 32)
+                                   // holds ~28 cell centres of the 7 x 7 window, never more than 32; the 8 x 8 window's disc
+                                   // up to 41: the host keeps such a sensor on the resident form, DrlgxState::disc_cells)
 constexpr size_t kLdsBudget = 160 * 1024;  // LDS of a CU: what one workgroup of the map kernel may take
 
 // pc: poses the per-pose tables hold (the launch's pose bound); chunk: poses per A / C pass; V: cells;

@@ -479,6 +479,16 @@ int drlgx_debug_gemm_tile_rows(int m, int n, int k_slices, int transpose_a);
  * parity test switches between them with this call. */
 int drlgx_debug_map_form(int form);
 
+/* Development aid: 1 when the two-workgroups-per-CU form can serve this engine at a launch bound of p_bound poses, 0 when every
+ * map launch runs the resident form whatever drlgx_debug_map_form asks for: a sensor whose bounding box prunes, a carve beyond
+ * half the LDS, or a sensor disc that can hold more cell centres than the compact stage has room for per pose (40; the host
+ * bounds the lattice count - 41 at a radius of 3.5 cells, the 8-cell window). */
+int drlgx_debug_map_compact_ok(const drlgx_engine *e, int p_bound);
+
+/* Development aid, stateless and host-only: the bound drlgx_create puts on the cell centres within max_range of a pose
+ * (radius_cells = max_range / resolution, 0 .. 64), so that a CPU test can hold it against a brute-force lattice count. */
+int drlgx_debug_disc_cells_bound(double radius_cells);
+
 /* The incremental belief update (csrc/k_inc.hip): between relinearisations of the iSAM2 policy (SLAM2D.cpp:10-12: every
  * 10th update, |delta| >= 0.1) SLAM2D::optimize (SLAM2D.cpp:374-430) only gains the new pose's odometry factor and the
  * step's bearing-range factors, so the engine applies the covariance-form update of FastMarginals2::propagate / update

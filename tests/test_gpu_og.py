@@ -25,24 +25,26 @@ A = og_cases.MAX_ACTIONS
 
 class Ctx(object):
     """The 3 environments of one map of og_cases stepped through its script beside their oracles (P = 7), and the reference of
-    every (environment, plan) computed once."""
+    every (environment, plan) computed once.  `cases`: another module or object with og_cases' names (tests/rect_cases.py: OgView)."""
 
-    def __init__(self, name):
+    def __init__(self, name, cases=og_cases):
         from drl_graph_exploration_amd.engine import Engine
-        n = og_cases.N_ENVS
+        assert cases.MAX_ACTIONS == A
+        self.K = cases
+        n = cases.N_ENVS
         self.name = name
-        self.cfg = og_cases.engine_config(name)
+        self.cfg = cases.engine_config(name)
         self.eng = Engine(self.cfg, n)
-        self.sims = og_cases.make_sims(name)
-        self.eng.reset(np.arange(n), np.arange(n), starts=og_cases.STARTS)
-        for act in og_cases.SCRIPT:
+        self.sims = cases.make_sims(name)
+        self.eng.reset(np.arange(n), np.arange(n), starts=cases.STARTS)
+        for act in cases.SCRIPT:
             self.eng.step(torch.tensor([act] * n, dtype=torch.float64, device=self.eng.device))
         assert self.eng.status() == 0
         for e, s in enumerate(self.sims):  # the belief is the oracle's (what the restatement starts from)
             assert self.eng.counts(e)["poses"] == s.num_poses() and self.eng.counts(e)["landmarks"] == s.num_landmarks()
             np.testing.assert_allclose(self.eng.poses(e)[0], s.poses()[0], atol=1e-9)
             np.testing.assert_allclose(self.eng.landmarks(e)[1], s.landmarks()[1], atol=1e-9)
-        self.plans = [og_cases.plans_for(s) for s in self.sims]
+        self.plans = [cases.plans_for(s) for s in self.sims]
         self.cases = [(e, k) for e in range(n) for k in range(len(self.plans[e]))]
         self._ref = {}
 
@@ -61,7 +63,7 @@ class Ctx(object):
 
     def live_state(self):
         out = []
-        for e in range(og_cases.N_ENVS):
+        for e in range(self.K.N_ENVS):
             out += list(self.eng.poses(e)) + list(self.eng.landmarks(e)) + list(self.eng.virtual_map(e))
         return out
 
