@@ -748,16 +748,9 @@ void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, cons
 void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
                           const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out);
 // The EM planner's tree sampler (k_em_tree.hip): one tree per selected environment, grown from its live belief, which is only read.
-// mode 0: optimize2's stop rule (max_nodes: the planner parameter), 1: rrt_planner's (goal_key / goal_xy).  Per-tree scratch, cap
-// nodes each: act [cap][3] edge odometry, link [cap][2] parent and depth, leaf [cap] the leaves in node order; meta [4] = nodes,
-// leaves, next Halton index, OptimizationResult.  flag[0] (zeroed by the caller): DRLGX_E_INVALID / DRLGX_E_CAPACITY.
-// obstacles: the kSafe = true instantiation with the planner parameter safe_distance (isSafe, the retry loop of sampleNode, the two
-// counters of 1000, the shrink at the start of the call); a tree it ends with SAMPLING_FAILURE has no leaf and touches no flag.
-// dubins (null: the non-Dubins control model): the kDubins = true instantiation, mode 1 only - the Dubins path library
-// (drlgx_set_dubins_library_host) on the device, SoA in library order.  max_steps: the largest num_steps (the bound of the step
-// loops); reach: (the largest |end| + tol)(1 + 2^-30), beyond which no entry can match (+inf: never skip a scan); pose: per-tree
-// scratch [cap][4], the nodes' (x y cos sin) for the plan.  A node's act row is then (library index, num_steps, 0), its depth in
-// link counts steps, and drlgx_launch_em_leaves_dubins writes the plan: one row per step, row ti of the outputs.
+// The Dubins path library (drlgx_set_dubins_library_host) on the device, SoA in library order.  max_steps: the largest num_steps
+// (the bound of the step loops); reach: (the largest |end| + tol)(1 + 2^-30), beyond which no entry can match (+inf: never skip a
+// scan); pose: per-tree scratch [cap][4], the nodes' (x y cos sin) for the plan.
 struct DrlgxDubins {
   const double *end_x, *end_y, *v, *w;
   const int *num_steps;
@@ -765,11 +758,32 @@ struct DrlgxDubins {
   double dt, tol, reach;
   double *pose;
 };
+struct DrlgxTreeArgs {
+  int n_sel;                    // trees: one workgroup each
+  const int32_t *env_sel;       // [n_sel] the tree's environment
+  const int32_t *halton_start;  // [n_sel] the first Halton index
+  int cap;                      // nodes per tree (max_tree_nodes)
+  int mode;                     // 0: optimize2's stop rule, 1: rrt_planner's
+  double max_nodes;             // mode 0: the planner parameter
+  double safe_distance;         // the planner parameter; the launcher passes 0 without `obstacles`
+  const int32_t *goal_key;      // mode 1, [n_sel]: the goal as a graph node (landmarks in key order, then poses) ...
+  const double *goal_xy;        // ... or, the key beyond the graph, [n_sel][2] the frontier point
+  // per-tree scratch, cap nodes each
+  double *act;                  // [cap][3] edge odometry; Dubins: (library index, num_steps, 0)
+  int *link;                    // [cap][2] parent and depth; Dubins: the depth counts steps
+  int *leaf;                    // [cap] the leaves in node order; mode 1: the goal node
+  int *meta;                    // [4] nodes, leaves, next Halton index, OptimizationResult
+  int *flag;                    // [1], zeroed by the caller: the smallest of DRLGX_E_INVALID / DRLGX_E_CAPACITY any tree met
+  // outputs, any of them null
+  double *nodes_out;            // [n_sel][cap][8] x y theta parent distance | the act row
+  int32_t *n_nodes_out, *result_out, *halton_next_out;  // [n_sel]
+  DrlgxDubins lib;              // read with `dubins` only
+};
 size_t drlgx_em_tree_lds_bytes(int cap);
-void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                          int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
-                          double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
-                          int32_t *result_out, int32_t *halton_next_out, const DrlgxDubins *dubins);
+// obstacles: the kSafe = true instantiation (isSafe, the retry loop of sampleNode, the two counters of 1000, the shrink at the start
+// of the call); a tree it ends with SAMPLING_FAILURE has no leaf and touches no flag.  dubins: the kDubins = true instantiation,
+// mode 1 only; drlgx_launch_em_leaves_dubins then writes the plan: one row per step, row ti of the outputs.
+void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, DrlgxTreeArgs args, bool obstacles, bool dubins);
 void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
                                    const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions);
 // the action lists root -> leaf in drlgx_em_cost's candidate layout; per_tree_row: row ti of the outputs instead of the running count

@@ -1243,9 +1243,10 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
   HIPCHK(e, hipMemsetAsync(flag_dev, 0, sizeof(int), e->stream));
   // (the obstacle logic only where there is a distance to keep: at exactly 0 the plain growth loop is the same tree)
   const bool obstacles = e->sampler_obstacles && e->sampler_safe_distance != 0.0;
-  drlgx_launch_em_tree(e->S, e->stream, n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, obstacles,
-                       e->sampler_safe_distance, goal_key_dev, goal_xy_dev, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev,
-                       nodes_out_dev, n_nodes_out_dev, result_out_dev, halton_next_out_dev, dubins ? &e->dubins : nullptr);
+  const DrlgxTreeArgs args = {n_sel, env_sel_dev, halton_start_dev, cap, mode, e->sampler_max_nodes, e->sampler_safe_distance,
+                              goal_key_dev, goal_xy_dev, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, flag_dev,
+                              nodes_out_dev, n_nodes_out_dev, result_out_dev, halton_next_out_dev, e->dubins};
+  drlgx_launch_em_tree(e->S, e->stream, args, obstacles, dubins);
   if ((r = check_launch(e))) return r;
   meta_h.resize((size_t)n_sel * kTreeMeta + 1);
   HIPCHK(e, hipMemcpyAsync(meta_h.data(), e->tree_meta, meta_h.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));

@@ -10,23 +10,28 @@
 //                                distance = parent.distance + sqrt(sqDistanceBetweenPoses(child, parent, angle_weight))
 // and the two stop rules: optimize2 stops after max_nodes_ accepted nodes; rrt_planner stops when a new node lies within
 // max_edge_length of the goal Pose2(gx, gy, pi) (isReached, :88-99) and then connects the goal to that node.
+// Here: tree_init, sample_point, nearest_node, connect; the stop rules are the growth loop of k_em_tree, which is one turn for every
+// instantiation - sample, nearest, connect, then the refused-counter or Tree::push, then the goal test and the same connect towards
+// the goal; tree_enter checks the arguments, tree_finish writes the results.
 //
 // The chain of accepted nodes is strictly sequential - node k + 1 is attached to the nearest of nodes 0 .. k - and the only parallel
-// work per sample is that arg-min.  ONE WAVE owns a tree: the node table (x y c s distance | parent depth children) lives in LDS,
-// lanes stride over the nodes and reduce (distance, index) by butterfly with the lowest index on equal distance, every lane then
-// holds the winner and computes the same child; lane 0 stores it.  A single wave needs no cross-wave exchange per sample (a
-// 256-thread workgroup pays two barriers and an LDS round per sample to save at most three strides of the arg-min at a few hundred
-// nodes; DESIGN.md section 4 has the comparison).  Every loop is bounded by the node capacity `cap`: each turn of the growth loop
-// accepts exactly one node, so a tree that cannot finish ends with a capacity result instead of spinning.
+// work per sample is that arg-min.  ONE WAVE owns a tree: the node table (x y c s distance | parent depth children) lives in LDS
+// (struct Tree), lanes stride over the nodes and reduce (distance, index) by butterfly with the lowest index on equal distance
+// (wave_argmin), every lane then holds the winner and computes the same child; lane 0 stores it (Tree::push).  A single wave needs
+// no cross-wave exchange per sample (a 256-thread workgroup pays two barriers and an LDS round per sample to save at most three
+// strides of the arg-min at a few hundred nodes; DESIGN.md section 4 has the comparison).  Every loop is bounded by the node capacity
+// `cap`: each turn of the growth loop accepts exactly one node, so a tree that cannot finish ends with a capacity result instead of
+// spinning.
 //
 //
-// THE OBSTACLE LOGIC (kSafe = true; the engine launches it only behind drlgx_set_sampler_obstacles and a safe_distance > 0 - the
-// kSafe = false instantiation is the code above, unchanged) adds, restated from the same file:
+// THE OBSTACLE LOGIC (kSafe = true; the engine launches it only behind drlgx_set_sampler_obstacles and a safe_distance > 0 - with
+// kSafe = false none of it is compiled in) adds, restated from the same file:
 //   isSafe(node) (:48-56; Distance.cpp:78-97)   unsafe iff an estimated landmark of the environment lies strictly nearer than
 //                                safe_distance (a negative radius finds nothing).  Each lane keeps one landmark in registers (lanes
 //                                stride the rest), a ballot decides: only emptiness is asked, the landmarks' order does not matter
+//                                (point_safe)
 //   sampleNode (:101-125)        Halton points until one is safe, every drawn point consumed; the 1001st unsafe point of one call
-//                                ends the tree with SAMPLING_FAILURE
+//                                ends the tree with SAMPLING_FAILURE (sample_point)
 //   isSafe(node, parent) (:58-86), asked by connectNode after the child is scaled (:243-248): |safe_distance| < 1e-3 tests nothing;
 //                                else d = range(child, parent), unit = the child's position in the PARENT's frame / d, and for
 //                                l = sd/2; l < d; l += sd/2 (repeated addition, strict <) the point child.transform_from(l unit).
@@ -34,25 +39,24 @@
 //                                heading turned by the edge's bearing once more - not between parent and child.  Reproduced as
 //                                written: this project follows the reference's behaviour.  Waypoints serially, landmarks in
 //                                parallel, out at the first unsafe one (the branch is wave-uniform); at most 2 max_edge_length /
-//                                1e-3 turns (d <= max_edge_length, the step is at least 5e-4)
-//   the connect counter (:1070-1079, :890-899)   a refused connect adds no node; the 1001st in a row ends the tree
+//                                1e-3 turns (d <= max_edge_length, the step is at least 5e-4) (edge_safe, asked by connect)
+//   the connect counter (:1070-1079, :890-899)   a refused connect adds no node; the 1001st in a row ends the tree (the growth loop)
 //   the shrink (:1046-1054, :841-849)   when the root is nearer than safe_distance to its nearest estimated landmark, the call's
 //                                safe_distance is that distance - 0.1 (optimize2: not below 0; rrt_planner: unclamped) - IF the
 //                                landmark's KEY is smaller than the NUMBER of landmarks: searchLandmarkNearest returns the key
 //                                (Simulator2D.cpp:394-403: landmarks in key order, strict <, so the lowest key wins a tie) and the
-//                                planner compares it with getLandmarkSize().  Kept as it is
+//                                planner compares it with getLandmarkSize().  Kept as it is (tree_shrink)
 //   rrt_planner's goal edge (:910-922)   a goal whose edge is unsafe is not in the tree: SUCCESS, no leaf, an empty plan
 // ONE DEVIATION: in rrt_planner a shrunk safe_distance below -1e-3 (the root within 0.099 m of a landmark) makes the reference's
 // waypoint loop run for ever - a negative step, l < d always true.  Such a tree ends at once with SAMPLING_FAILURE, the root alone,
-// no point drawn.
+// no point drawn (tree_shrink).
 // A tree that ends with SAMPLING_FAILURE keeps the nodes accepted so far, has no leaf and no plan; the other trees of the launch are
 // not concerned, and the flag is not touched: a sampling failure is a result.  Loop bounds: cap accepted nodes, the two counters of
 // 1000, the waypoint bound.
 //
 //
 // THE DUBINS CONTROL MODEL (kDubins = true; rrt_planner only, launched when drlgx_set_dubins_library_host has loaded a library and the
-// sampler's Dubins flag is set - the kDubins = false instantiations are the code above, unchanged) replaces connectNode, restated
-// from the same file:
+// sampler's Dubins flag is set) replaces the body of connectNode - connect<kSafe, true> -, restated from the same file:
 //   the library (:1359-1414)     built by the engine on the host, SoA: the end point of every (v, w, duration) path from Pose2(0, 0, 0)
 //   sampleNode (:41-45, :110-115)   the generator has dimension 2: the same x, y in bases 2 and 3; the sample's theta is 0 and unread
 //   connectNodeDubinsPath (:157-176)   local = the sample in the parent's frame; the FIRST entry in library order with
@@ -61,9 +65,10 @@
 //                                there.  A scan that cannot match is skipped: |local| > (max_i |end_i| + tolerance_radius)(1 +
 //                                2^-30) implies |local - end_i| > tolerance_radius for every i by the triangle inequality, the factor
 //                                covering the roundings of the three square roots many times over (an infinite bound switches the
-//                                skip off: drlgx_set_dubins_prefilter).  Every thread then integrates the entry's num_steps Euler
-//                                steps from the PARENT's pose - x += v dt cos, y += v dt sin, theta = atan2(sin, cos) + w dt, the
-//                                angle through (cos, sin) at every step as Pose2(x, y, theta) does; the node is the last pose
+//                                skip off: drlgx_set_dubins_prefilter) (dubins_match).  Every thread then integrates the entry's
+//                                num_steps Euler steps from the PARENT's pose - x += v dt cos, y += v dt sin, theta = atan2(sin, cos)
+//                                + w dt, the angle through (cos, sin) at every step as Pose2(x, y, theta) does (dubins_step); the
+//                                node is the last pose
 //   isSafe(node, parent) (:59-70)   |safe_distance| < 1e-3 tests nothing; else poses 1 .. num_steps - 2 (the first and the last are
 //                                not tested) each pass isSafe(point): steps serially, landmarks in parallel, out at the first
 //                                unsafe one.  There is no waypoint loop, so a negative shrunk safe_distance is no deviation here
@@ -117,30 +122,70 @@ __device__ __forceinline__ double sq_distance(const Pose &p1, const P2 &pt, doub
   return range * range + wb * wb;
 }
 
-// (distance, index) of the whole workgroup's minimum, lowest index on equal distance, in every thread
-__device__ __forceinline__ void argmin_all(double &d, int &idx, double *red_d, int *red_i) {
+// (value, index) of one wave's minimum, the lowest index on equal value, in every lane
+__device__ __forceinline__ void wave_argmin(double &v, int &i) {
   for (int m = 1; m < 64; m <<= 1) {
-    const double od = __shfl_xor(d, m, 64);
-    const int oi = __shfl_xor(idx, m, 64);
-    if (od < d || (od == d && oi < idx)) {
-      d = od;
-      idx = oi;
+    const double ov = __shfl_xor(v, m, 64);
+    const int oi = __shfl_xor(i, m, 64);
+    if (ov < v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
     }
   }
+}
+
+// One tree in LDS, carved once from the workgroup's dynamic LDS (lds_bytes(cap)): the node table, the slots of the cross-wave
+// exchanges, and the tree's act rows in memory (the edge record of every node).
+struct Tree {
+  double *nd;     // [cap][kNd] x y c s distance
+  int *ni;        // [cap][kNi] parent depth children
+  double *red_d;  // [kWaves]
+  int *red_i;     // [kWaves]
+  double *ta;     // [cap][3], memory
+  int n;          // nodes so far
+
+  __device__ __forceinline__ Tree(double *smem, int cap, double *act_rows)
+      : nd(smem), ni(reinterpret_cast<int *>(smem + (size_t)cap * kNd + 2 * kWaves)), red_d(smem + (size_t)cap * kNd),
+        red_i(reinterpret_cast<int *>(smem + (size_t)cap * kNd + kWaves)), ta(act_rows), n(0) {}
+
+  __device__ __forceinline__ Pose pose(int j) const { return Pose{nd[kNd * j], nd[kNd * j + 1], nd[kNd * j + 2], nd[kNd * j + 3]}; }
+  __device__ __forceinline__ double dist(int j) const { return nd[kNd * j + 4]; }
+  __device__ __forceinline__ int parent(int j) const { return ni[kNi * j]; }
+  __device__ __forceinline__ int depth(int j) const { return ni[kNi * j + 1]; }
+  __device__ __forceinline__ bool is_leaf(int j) const { return ni[kNi * j + 2] == 0; }
+
+  // node n, a child of `parent` (-1: the root); every thread calls it with the same values, lane 0 stores
+  __device__ __forceinline__ void push(int parent, const Pose &child, double dist, int depth, double act0, double act1, double act2) {
+    __syncthreads();  // (every thread has read the table)
+    if (threadIdx.x == 0) {
+      nd[kNd * n] = child.x; nd[kNd * n + 1] = child.y; nd[kNd * n + 2] = child.c; nd[kNd * n + 3] = child.s;
+      nd[kNd * n + 4] = dist;
+      ni[kNi * n] = parent; ni[kNi * n + 1] = depth; ni[kNi * n + 2] = 0;
+      if (parent >= 0) ni[kNi * parent + 2] += 1;
+      ta[3 * n] = act0; ta[3 * n + 1] = act1; ta[3 * n + 2] = act2;
+    }
+    __syncthreads();
+    ++n;
+  }
+};
+
+// (distance, index) of the whole workgroup's minimum, lowest index on equal distance, in every thread
+__device__ __forceinline__ void argmin_all(double &d, int &idx, const Tree &t) {
+  wave_argmin(d, idx);
   if (kWaves > 1) {
     const int wave = threadIdx.x >> 6;
     __syncthreads();  // (the previous round's readers are done)
     if ((threadIdx.x & 63) == 0) {
-      red_d[wave] = d;
-      red_i[wave] = idx;
+      t.red_d[wave] = d;
+      t.red_i[wave] = idx;
     }
     __syncthreads();
-    d = red_d[0];
-    idx = red_i[0];
+    d = t.red_d[0];
+    idx = t.red_i[0];
     for (int w = 1; w < kWaves; ++w)
-      if (red_d[w] < d || (red_d[w] == d && red_i[w] < idx)) {
-        d = red_d[w];
-        idx = red_i[w];
+      if (t.red_d[w] < d || (t.red_d[w] == d && t.red_i[w] < idx)) {
+        d = t.red_d[w];
+        idx = t.red_i[w];
       }
   }
 }
@@ -151,6 +196,13 @@ struct Obstacles {
   double x, y;
   const double *el;
   int L;
+};
+
+// What tree_shrink leaves for the call's safety tests (kSafe = false reads none of it)
+struct Safety {
+  Obstacles ob;
+  double sd;     // the call's safe_distance, shrunk or not
+  int wp_bound;  // the waypoint loop's bound
 };
 
 // isSafe(node): no landmark strictly nearer than sd; the same answer in every thread
@@ -167,16 +219,16 @@ __device__ __forceinline__ bool point_safe(const P2 &pt, const Obstacles &ob, do
 }
 
 // isSafe(node, parent), non-Dubins: the waypoints as the reference writes them (beyond the child - see the head of the file)
-__device__ __forceinline__ bool edge_safe(const Pose &child, const Pose &par, const Obstacles &ob, double sd, int wp_bound) {
-  if (fabs(sd) < kEdgeEps) return true;
+__device__ __forceinline__ bool edge_safe(const Pose &child, const Pose &par, const Safety &sf) {
+  if (fabs(sf.sd) < kEdgeEps) return true;
   const double d = range_of<false>(child, P2{par.x, par.y}, nullptr, nullptr);
   const P2 loc = transform_to(par, P2{child.x, child.y});
-  const double half = sd / 2;
+  const double half = sf.sd / 2;
   double l = half;
-  for (int w = 0; w < wp_bound && l < d; ++w) {  // (d == 0: no waypoint)
+  for (int w = 0; w < sf.wp_bound && l < d; ++w) {  // (d == 0: no waypoint)
     const double inv = 1.0 / d;
     const P2 unit{inv * loc.x, inv * loc.y};
-    if (!point_safe(transform_from(child, P2{l * unit.x, l * unit.y}), ob, sd)) return false;
+    if (!point_safe(transform_from(child, P2{l * unit.x, l * unit.y}), sf.ob, sf.sd)) return false;
     l += half;
   }
   return true;
@@ -214,370 +266,342 @@ __device__ __forceinline__ Pose dubins_step(const Pose &p, double vdt, double wd
   return Pose{x, y, cos(th), sin(th)};
 }
 
-// connectNode under the Dubins model from `par` towards `target`: false = refused (no library path, or an unsafe intermediate pose).
-// child: the path's last pose; m, ns: the library entry and its steps; edge: distanceBetweenNodes
-template <bool kSafe>
-__device__ __forceinline__ bool dubins_connect(const DrlgxDubins &lib, const Pose &par, const P2 &target, const Obstacles &ob, double sd,
-                                               double angle_weight, int *red_i, Pose &child, int &m, int &ns, double &edge) {
-  m = dubins_match(lib, transform_to(par, target), red_i);
-  if (m < 0) return false;
-  const double v = lib.v[m], w = lib.w[m];
-  ns = min(lib.num_steps[m], lib.max_steps);
-  const double vdt = v * lib.dt, wdt = w * lib.dt;
-  const bool test = kSafe && !(fabs(sd) < kEdgeEps);
-  child = par;
-  for (int step = 0; step < ns; ++step) {
-    child = dubins_step(child, vdt, wdt);
-    if (test && step >= 1 && step <= ns - 2 && !point_safe(P2{child.x, child.y}, ob, sd)) return false;
+// What connectNode adds to its parent: the child's pose, distanceBetweenNodes, the depth the child gains (1; Dubins: the path's
+// steps) and the node's act row: the edge odometry - or, Dubins, (entry, depth, 0), kept as the integers they are until the push
+// (as doubles they cost the Dubins loops six registers)
+struct Edge {
+  Pose child;
+  double dist;
+  int depth;
+  double ax, ay, angle;
+  int entry;
+};
+
+// connectNode from `par` towards `target`, the sampled point or the goal, every thread alike: false = refused (kSafe: an unsafe
+// edge; kDubins: no library path, or an unsafe intermediate pose).  Without kSafe and kDubins it cannot refuse.
+template <bool kSafe, bool kDubins>
+__device__ __forceinline__ bool connect(const Pose &par, const P2 &target, const drlgx_config &cfg, const Safety &sf, const DrlgxDubins &lib,
+                                        int *red_i, Edge &e) {
+  if (kDubins) {
+    const int m = dubins_match(lib, transform_to(par, target), red_i);
+    if (m < 0) return false;
+    const double v = lib.v[m], w = lib.w[m];
+    const int ns = min(lib.num_steps[m], lib.max_steps);
+    const double vdt = v * lib.dt, wdt = w * lib.dt;
+    const bool test = kSafe && !(fabs(sf.sd) < kEdgeEps);
+    e.child = par;
+    for (int step = 0; step < ns; ++step) {
+      e.child = dubins_step(e.child, vdt, wdt);
+      if (test && step >= 1 && step <= ns - 2 && !point_safe(P2{e.child.x, e.child.y}, sf.ob, sf.sd)) return false;
+    }
+    e.dist = vdt * (double)ns + fabs(wdt * (double)ns) * cfg.angle_weight;
+    e.depth = ns;
+    e.entry = m;
+    return true;
   }
-  edge = vdt * (double)ns + fabs(wdt * (double)ns) * angle_weight;
+  const double d = range_of<false>(par, target, nullptr, nullptr);
+  const double angle = bearing_of<false>(par, target, nullptr, nullptr);
+  const double len = d > cfg.max_edge_length ? cfg.max_edge_length : d;
+  e.ax = len * cos(angle); e.ay = len * sin(angle); e.angle = angle;
+  e.child = compose(par, make_pose(e.ax, e.ay, angle));
+  if (kSafe && !edge_safe(e.child, par, sf)) return false;  // isSafe(node, parent) on the scaled child
+  double bb;
+  e.dist = sqrt(sq_distance(e.child, P2{par.x, par.y}, cfg.angle_weight, bb));
+  e.depth = 1;
   return true;
 }
 
-// mode 0: optimize2's stop rule; 1: rrt_planner's.  goal_key / goal_xy: mode 1 only.  nodes_out (null: not wanted): per tree
-// [cap][8] = x y theta parent distance | the edge odometry from the parent (x y theta).  flag[0] (zeroed by the caller): the smallest DRLGX_E_* code any tree met.
-// kSafe: the obstacle logic with the planner parameter safe_distance (> 0); kSafe = false never reads it.
-// kDubins: the Dubins control model with the library `lib` (mode 1 only; kDubins = false never reads it): a node's depth counts steps,
-// its act row is (library index, num_steps, 0), and lib.pose [tree][cap][4] receives the nodes' (x y cos sin) for k_em_leaves_dubins.
-template <bool kSafe, bool kDubins>
-__global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                                                int mode, double max_nodes, double safe_distance, const int32_t *goal_key,
-                                                const double *goal_xy, double *act, int *link, int *leaf, int *meta, int *flag,
-                                                double *nodes_out, int32_t *n_nodes_out, int32_t *result_out,
-                                                int32_t *halton_next_out, DrlgxDubins lib) {
-  extern __shared__ __attribute__((aligned(16))) double tree_smem[];
-  const int tid = threadIdx.x, lane = tid & 63, ti = blockIdx.x;
-  if (ti >= n_sel) return;
-  const int env = env_sel[ti];
-  int *mt = meta + (size_t)ti * M_STRIDE;
-  if (env < 0 || env >= S.n_envs) {
-    if (tid == 0) {
-      atomicMin(flag, DRLGX_E_INVALID);
-      mt[M_NODES] = mt[M_LEAVES] = 0;
-    }
-    return;
-  }
-  const drlgx_config &cfg = S.cfg;
-  const int *cnt = S.cnt + (size_t)env * DRLGX_CNT_STRIDE;
-  const int P = cnt[C_P], L = cnt[C_L];
-  if (P < 1 || P > S.P_max || L < 0 || L > S.L_max || cap < 1) {
-    if (tid == 0) {
-      atomicMin(flag, DRLGX_E_INVALID);
-      mt[M_NODES] = mt[M_LEAVES] = 0;
-    }
-    return;
-  }
-  double *nd = tree_smem;                                  // [cap][kNd]
-  double *red_d = nd + (size_t)cap * kNd;                  // [kWaves]
-  int *ni = reinterpret_cast<int *>(red_d + 2 * kWaves);   // [cap][kNi]
-  int *red_i = reinterpret_cast<int *>(red_d + kWaves);    // [kWaves]
-  const double *ep = S.est_pose + (size_t)env * S.P_max * 4;
-  const double *el = S.est_lm + (size_t)env * S.L_max * 2;
-  double *ta = act + (size_t)ti * cap * 3;
+// The edge's child becomes node t.n, at `dist` and `depth` from the root
+template <bool kDubins>
+__device__ __forceinline__ void push_edge(Tree &t, int parent, const Edge &e, double dist, int depth) {
+  if (kDubins) t.push(parent, e.child, dist, depth, (double)e.entry, (double)e.depth, 0.0);
+  else t.push(parent, e.child, dist, depth, e.ax, e.ay, e.angle);
+}
 
-  // ---- initialize: the root, max_nodes_ ----
-  int budget = 0x7fffffff;  // accepted nodes the stop rule allows
-  if (mode == 0) {
+// Where one tree reads its belief and leaves its counts
+struct Belief {
+  int P, L;
+  const double *ep, *el;  // the estimated poses (x y c s) and landmarks
+  const int *lk;          // the landmarks' keys
+  int *mt;                // the tree's meta row
+};
+
+// How a tree ended, for tree_finish
+struct Outcome {
+  int count;      // the next Halton index
+  int max_depth;  // of the plans the tree offers
+  int goal_node;  // rrt: the goal's node, -1: not in the tree
+  bool sampling_failed, full;  // full: the table filled before the stop rule was met
+};
+
+// The argument checks, with the one invalid exit: false = this workgroup has no tree to grow
+__device__ __forceinline__ bool tree_enter(const DrlgxState &S, const DrlgxTreeArgs &a, int ti, Belief &b) {
+  if (ti >= a.n_sel) return false;
+  const int env = a.env_sel[ti];
+  b.mt = a.meta + (size_t)ti * M_STRIDE;
+  bool ok = env >= 0 && env < S.n_envs && a.cap >= 1;
+  if (ok) {
+    const int *cnt = S.cnt + (size_t)env * DRLGX_CNT_STRIDE;
+    b.P = cnt[C_P];
+    b.L = cnt[C_L];
+    ok = b.P >= 1 && b.P <= S.P_max && b.L >= 0 && b.L <= S.L_max;
+  }
+  if (!ok) {
+    if (threadIdx.x == 0) {
+      atomicMin(a.flag, DRLGX_E_INVALID);
+      b.mt[M_NODES] = b.mt[M_LEAVES] = 0;
+    }
+    return false;
+  }
+  b.ep = S.est_pose + (size_t)env * S.P_max * 4;
+  b.el = S.est_lm + (size_t)env * S.L_max * 2;
+  b.lk = S.lm_key + (size_t)env * S.L_max;
+  return true;
+}
+
+// initialize: max_nodes_ from the known cells (mode 0: the accepted nodes the stop rule allows), the goal from key or point (mode
+// 1), the root
+__device__ __forceinline__ void tree_init(const DrlgxState &S, const DrlgxTreeArgs &a, const Belief &b, int ti, Tree &t, int &budget,
+                                          P2 &goal) {
+  const int tid = threadIdx.x, lane = tid & 63, env = a.env_sel[ti], P = b.P, L = b.L;
+  budget = 0x7fffffff;
+  if (a.mode == 0) {
     const double *prob = S.vm_prob + (size_t)env * S.V;
     int known = 0;
-    for (int v = tid; v < S.V; v += kT) known += prob[v] < cfg.occupancy_threshold ? 1 : 0;
+    for (int v = tid; v < S.V; v += kT) known += prob[v] < S.cfg.occupancy_threshold ? 1 : 0;
     double kd = (double)known;
     for (int m = 1; m < 64; m <<= 1) kd += __shfl_xor(kd, m, 64);
     if (kWaves > 1) {
       __syncthreads();
-      if (lane == 0) red_d[tid >> 6] = kd;
+      if (lane == 0) t.red_d[tid >> 6] = kd;
       __syncthreads();
       kd = 0.0;
-      for (int w = 0; w < kWaves; ++w) kd += red_d[w];
+      for (int w = 0; w < kWaves; ++w) kd += t.red_d[w];
       __syncthreads();
     }
-    const double mn = floor(kd * max_nodes);
+    const double mn = floor(kd * a.max_nodes);
     budget = mn < 0.0 ? 0 : (mn > 2147483647.0 ? 0x7fffffff : (int)mn);
   }
-  P2 goal{0.0, 0.0};
-  if (mode == 1) {
+  goal = P2{0.0, 0.0};
+  if (a.mode == 1) {
     // the goal: graph node goal_key (landmarks in key order, then poses - the order of the exported graph) or the frontier point
-    const int gk = goal_key[ti];
-    goal = P2{goal_xy[2 * ti], goal_xy[2 * ti + 1]};
+    const int gk = a.goal_key[ti];
+    goal = P2{a.goal_xy[2 * ti], a.goal_xy[2 * ti + 1]};
     if (gk >= 0 && gk < L) {
-      const int *lk = S.lm_key + (size_t)env * S.L_max;
       int slot = 0x7fffffff;  // the slot whose key has rank gk
       for (int j = lane; j < L; j += 64) {
         int rank = 0;
-        for (int q = 0; q < L; ++q) rank += lk[q] < lk[j] ? 1 : 0;
+        for (int q = 0; q < L; ++q) rank += b.lk[q] < b.lk[j] ? 1 : 0;
         if (rank == gk) slot = min(slot, j);
       }
       for (int m = 1; m < 64; m <<= 1) slot = min(slot, __shfl_xor(slot, m, 64));
-      if (slot < L) goal = P2{el[2 * slot], el[2 * slot + 1]};
+      if (slot < L) goal = P2{b.el[2 * slot], b.el[2 * slot + 1]};
     } else if (gk >= L && gk < L + P) {
-      goal = P2{ep[4 * (gk - L)], ep[4 * (gk - L) + 1]};
+      goal = P2{b.ep[4 * (gk - L)], b.ep[4 * (gk - L) + 1]};
     }
+  }
+  const double *root = b.ep + 4 * (P - 1);
+  t.push(-1, Pose{root[0], root[1], root[2], root[3]}, 0.0, 0, 0.0, 0.0, 0.0);
+}
+
+// The call's safety tests: the landmark registers and - the shrink - the call's safe_distance.  kSafe = false: nothing to test.
+// failed: rrt_planner's deviation, the tree ends before a point is drawn.
+template <bool kSafe, bool kDubins>
+__device__ __forceinline__ Safety tree_shrink(const drlgx_config &cfg, const DrlgxTreeArgs &a, const Belief &b, bool &failed) {
+  Safety sf{Obstacles{__builtin_huge_val(), __builtin_huge_val(), b.el, b.L}, a.safe_distance, 0};
+  if (!kSafe) return sf;
+  const int lane = threadIdx.x & 63, L = b.L;
+  if (lane < L) {
+    sf.ob.x = b.el[2 * lane];
+    sf.ob.y = b.el[2 * lane + 1];
+  }
+  // searchLandmarkNearest: the landmarks in key order, strict < - the arg-min of (distance, key); what comes back is the KEY
+  const double rx = b.ep[4 * (b.P - 1)], ry = b.ep[4 * (b.P - 1) + 1];
+  double bd = __builtin_huge_val();
+  int bk = 0x7fffffff;
+  for (int j = lane; j < L; j += 64) {
+    const double dx = b.el[2 * j] - rx, dy = b.el[2 * j + 1] - ry;
+    const double dj = sqrt(dx * dx + dy * dy);
+    if (dj < bd || (dj == bd && b.lk[j] < bk)) {
+      bd = dj;
+      bk = b.lk[j];
+    }
+  }
+  wave_argmin(bd, bk);
+  // (no landmark: the reference's search answers 1, which is not below 0.)  The key against the NUMBER of landmarks, as written
+  if (L > 0 && bk >= 0 && bk < L && bd < sf.sd) sf.sd = a.mode == 0 ? (bd - 0.1 > 0.0 ? bd - 0.1 : 0.0) : bd - 0.1;
+  // the deviation: rrt_planner's waypoint loop would not end
+  if (!kDubins && a.mode == 1 && sf.sd < -kEdgeEps) failed = true;
+  const double wb = 2.0 * cfg.max_edge_length / kEdgeEps + 2.0;
+  sf.wp_bound = wb < 2147483647.0 ? (int)wb : 0x7fffffff;
+  return sf;
+}
+
+// sampleNode: Halton point number count++ over the map's box.  (The sample's own heading, theta = 2 pi h2 with h2 the radical
+// inverse in base 5, enters nothing - nearestNode and connectNode read the sample's position only, the child's heading is the
+// parent's plus the bearing - so the third coordinate of the point is not evaluated; the point is consumed all the same.)
+// kSafe: points are drawn until one is safe, each one consumed; false = the 1001st unsafe one, which ends the tree.
+template <bool kSafe>
+__device__ __forceinline__ bool sample_point(const drlgx_config &cfg, const Safety &sf, int &count, P2 &sp) {
+  const double span_x = cfg.map_max_x - cfg.map_min_x, span_y = cfg.map_max_y - cfg.map_min_y;
+  for (int u = 0; u <= (kSafe ? kMaxFailed : 0); ++u) {
+    const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
+    ++count;
+    sp = P2{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+    if (!kSafe || point_safe(sp, sf.ob, sf.sd)) return true;
+  }
+  return false;
+}
+
+// nearestNode: the node with the smallest sq_distance to the sample, the lowest index on equal distance
+__device__ __forceinline__ int nearest_node(const Tree &t, const P2 &sp, double angle_weight) {
+  double best = __builtin_huge_val();
+  int bi = 0x7fffffff;
+  for (int j = threadIdx.x; j < t.n; j += kT) {
+    double b;
+    const double dj = sq_distance(t.pose(j), sp, angle_weight, b);
+    if (dj < best) {
+      best = dj;
+      bi = j;
+    }
+  }
+  argmin_all(best, bi, t);
+  return bi < 0 || bi >= t.n ? 0 : bi;  // (only a NaN distance to every node could leave no winner)
+}
+
+// The results: the tables to memory, the leaves in node order, meta and the flag
+template <bool kDubins>
+__device__ __forceinline__ void tree_finish(const DrlgxState &S, const DrlgxTreeArgs &a, const Belief &b, int ti, const Tree &t,
+                                            const Outcome &r) {
+  const int tid = threadIdx.x, lane = tid & 63, n = t.n, cap = a.cap;
+  int *tl = a.link + (size_t)ti * cap * 2, *lf = a.leaf + (size_t)ti * cap;
+  for (int j = tid; j < n; j += kT) {
+    const Pose p = t.pose(j);
+    tl[2 * j] = t.parent(j);
+    tl[2 * j + 1] = t.depth(j);
+    if (kDubins) {
+      double *o = a.lib.pose + ((size_t)ti * cap + j) * 4;
+      o[0] = p.x; o[1] = p.y; o[2] = p.c; o[3] = p.s;
+    }
+    if (a.nodes_out) {
+      double *o = a.nodes_out + ((size_t)ti * cap + j) * kNodeOut;
+      o[0] = p.x; o[1] = p.y;
+      o[2] = atan2(p.s, p.c);
+      o[3] = (double)t.parent(j);
+      o[4] = t.dist(j);
+      o[5] = t.ta[3 * j]; o[6] = t.ta[3 * j + 1]; o[7] = t.ta[3 * j + 2];
+    }
+  }
+  int n_leaves = 0;
+  if (a.mode == 0 && !r.sampling_failed) {
+    if (tid < 64) {  // (one wave lists: node order)
+      for (int base = 0; base < n; base += 64) {
+        const int j = base + lane;
+        const bool is_leaf = j < n && t.is_leaf(j);
+        const unsigned long long bl = __ballot(is_leaf);
+        if (is_leaf) lf[n_leaves + __popcll(bl & ((1ull << lane) - 1ull))] = j;
+        n_leaves += __popcll(bl);
+      }
+    }
+  } else if (r.goal_node >= 0) {
+    if (tid == 0) lf[0] = r.goal_node;
+    n_leaves = 1;
   }
   if (tid == 0) {
-    nd[0] = ep[4 * (P - 1)]; nd[1] = ep[4 * (P - 1) + 1]; nd[2] = ep[4 * (P - 1) + 2]; nd[3] = ep[4 * (P - 1) + 3];
-    nd[4] = 0.0;
-    ni[0] = -1; ni[1] = 0; ni[2] = 0;
-    ta[0] = ta[1] = ta[2] = 0.0;
+    const int res = ((a.mode == 1 && r.full) || r.sampling_failed) ? R_SAMPLING_FAILURE : R_SUCCESS;
+    b.mt[M_NODES] = n;
+    b.mt[M_LEAVES] = n_leaves;
+    b.mt[M_HALTON] = r.count;
+    b.mt[M_RESULT] = res;
+    if (a.n_nodes_out) a.n_nodes_out[ti] = n;
+    if (a.result_out) a.result_out[ti] = res;
+    if (a.halton_next_out) a.halton_next_out[ti] = r.count;
+    // what the whole call is refused for: optimize2's tree does not fit the table; a plan deeper than max_actions
+    // (a tree that failed to sample offers no plan: nothing of it can be too deep)
+    if ((a.mode == 0 && r.full) || (((a.mode == 0 && !r.sampling_failed) || r.goal_node >= 0) && r.max_depth > S.A_max))
+      atomicMin(a.flag, DRLGX_E_CAPACITY);
   }
-  __syncthreads();
+}
 
-  // ---- the call's safe_distance: the shrink ----
-  Obstacles ob{__builtin_huge_val(), __builtin_huge_val(), el, L};
-  double sd = safe_distance;
-  bool sampling_failed = false, goal_refused = false;
-  int wp_bound = 0;
-  if (kSafe) {
-    if (lane < L) {
-      ob.x = el[2 * lane];
-      ob.y = el[2 * lane + 1];
-    }
-    // searchLandmarkNearest: the landmarks in key order, strict < - the arg-min of (distance, key); what comes back is the KEY
-    const int *lk = S.lm_key + (size_t)env * S.L_max;
-    const double rx = ep[4 * (P - 1)], ry = ep[4 * (P - 1) + 1];
-    double bd = __builtin_huge_val();
-    int bk = 0x7fffffff;
-    for (int j = lane; j < L; j += 64) {
-      const double dx = el[2 * j] - rx, dy = el[2 * j + 1] - ry;
-      const double dj = sqrt(dx * dx + dy * dy);
-      if (dj < bd || (dj == bd && lk[j] < bk)) {
-        bd = dj;
-        bk = lk[j];
-      }
-    }
-    for (int m = 1; m < 64; m <<= 1) {
-      const double od = __shfl_xor(bd, m, 64);
-      const int ok = __shfl_xor(bk, m, 64);
-      if (od < bd || (od == bd && ok < bk)) {
-        bd = od;
-        bk = ok;
-      }
-    }
-    // (no landmark: the reference's search answers 1, which is not below 0.)  The key against the NUMBER of landmarks, as written
-    if (L > 0 && bk >= 0 && bk < L && bd < sd) sd = mode == 0 ? (bd - 0.1 > 0.0 ? bd - 0.1 : 0.0) : bd - 0.1;
-    // the deviation: rrt_planner's waypoint loop would not end
-    if (!kDubins && mode == 1 && sd < -kEdgeEps) sampling_failed = true;
-    const double wb = 2.0 * cfg.max_edge_length / kEdgeEps + 2.0;
-    wp_bound = wb < 2147483647.0 ? (int)wb : 0x7fffffff;
-  }
-
-  // ---- growth: one accepted node per turn (kSafe: or one refused connect, at most kMaxFailed in a row) ----
-  const double span_x = cfg.map_max_x - cfg.map_min_x, span_y = cfg.map_max_y - cfg.map_min_y;
-  int n = 1, count = halton_start[ti], max_depth = 0, goal_node = -1, failed = 0;
-  bool full = false;  // the table filled before the stop rule was met
+// One tree per workgroup (DrlgxTreeArgs in drlgx_dev.h).  kSafe: the obstacle logic with the planner parameter safe_distance (> 0);
+// kSafe = false never reads it.  kDubins: the Dubins control model with the library a.lib (mode 1 only; kDubins = false never reads
+// it).  Growth: one accepted node per turn - or, kSafe || kDubins, one refused connect, at most kMaxFailed in a row.
+template <bool kSafe, bool kDubins>
+__global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, DrlgxTreeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double tree_smem[];
+  const int ti = blockIdx.x, cap = a.cap, mode = a.mode;
+  Belief b;
+  if (!tree_enter(S, a, ti, b)) return;
+  const drlgx_config &cfg = S.cfg;
+  Tree t(tree_smem, cap, a.act + (size_t)ti * cap * 3);
+  int budget;
+  P2 goal;
+  tree_init(S, a, b, ti, t, budget, goal);
+  Outcome r{a.halton_start[ti], 0, -1, false, false};
+  const Safety sf = tree_shrink<kSafe, kDubins>(cfg, a, b, r.sampling_failed);
+  bool goal_refused = false;
+  int failed = 0;
   const long long max_turns = kSafe || kDubins ? (long long)cap * (kMaxFailed + 2) : (long long)cap;
-  for (long long turn = 0; turn < max_turns && !sampling_failed; ++turn) {
-    if (mode == 0 && n - 1 >= budget) break;
-    if (n >= cap) {
-      full = true;
+  for (long long turn = 0; turn < max_turns && !r.sampling_failed; ++turn) {
+    if (mode == 0 && t.n - 1 >= budget) break;
+    if (t.n >= cap) {
+      r.full = true;
       break;
     }
-    // sampleNode.  (The sample's own heading, theta = 2 pi h2 with h2 the radical inverse in base 5, enters nothing at
-    // safe_distance = 0 - nearestNode and connectNode read the sample's position only, the child's heading is the parent's plus the
-    // bearing - so the third coordinate of the point is not evaluated; the point is consumed all the same.)
-    // kSafe: points are drawn until one is safe, each one consumed; the 1001st unsafe one ends the tree.
     P2 sp{0.0, 0.0};
-    if (kSafe) {
-      bool found = false;
-      for (int u = 0; u <= kMaxFailed && !found; ++u) {
-        const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
-        ++count;
-        sp = P2{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
-        found = point_safe(sp, ob, sd);
-      }
-      if (!found) {
-        sampling_failed = true;
-        break;
-      }
-    } else {
-      const double h0 = radical_inverse(count, 2), h1 = radical_inverse(count, 3);
-      ++count;
-      sp = P2{cfg.map_min_x + h0 * span_x, cfg.map_min_y + h1 * span_y};
+    if (!sample_point<kSafe>(cfg, sf, r.count, sp)) {
+      r.sampling_failed = true;
+      break;
     }
-    // nearestNode
-    double best = __builtin_huge_val();
-    int bi = 0x7fffffff;
-    for (int j = tid; j < n; j += kT) {
-      const Pose pj{nd[kNd * j], nd[kNd * j + 1], nd[kNd * j + 2], nd[kNd * j + 3]};
-      double b;
-      const double dj = sq_distance(pj, sp, cfg.angle_weight, b);
-      if (dj < best) {
-        best = dj;
-        bi = j;
-      }
-    }
-    argmin_all(best, bi, red_d, red_i);
-    if (bi < 0 || bi >= n) bi = 0;  // (only a NaN distance to every node could leave no winner)
-    if (kDubins) {
-      // connectNode under the Dubins model, every thread alike: the whole turn, the goal edge included
-      const Pose par{nd[kNd * bi], nd[kNd * bi + 1], nd[kNd * bi + 2], nd[kNd * bi + 3]};
-      const double pdist = nd[kNd * bi + 4];
-      const int pdepth = ni[kNi * bi + 1];
-      Pose child;
-      int m, ns;
-      double edge;
-      if (!dubins_connect<kSafe>(lib, par, sp, ob, sd, cfg.angle_weight, red_i, child, m, ns, edge)) {
-        if (++failed > kMaxFailed) {
-          sampling_failed = true;
-          break;
-        }
-        continue;
-      }
-      failed = 0;
-      const double dist = pdist + edge;
-      __syncthreads();  // (every thread has read the table)
-      if (tid == 0) {
-        nd[kNd * n] = child.x; nd[kNd * n + 1] = child.y; nd[kNd * n + 2] = child.c; nd[kNd * n + 3] = child.s;
-        nd[kNd * n + 4] = dist;
-        ni[kNi * n] = bi; ni[kNi * n + 1] = pdepth + ns; ni[kNi * n + 2] = 0;
-        ni[kNi * bi + 2] += 1;
-        ta[3 * n] = (double)m; ta[3 * n + 1] = (double)ns; ta[3 * n + 2] = 0.0;
-      }
-      __syncthreads();
-      max_depth = max(max_depth, pdepth + ns);
-      ++n;
-      const double gx = child.x - goal.x, gy = child.y - goal.y;
-      if (mode == 1 && sqrt(gx * gx + gy * gy) <= cfg.max_edge_length) {
-        if (n >= cap) {
-          full = true;
-          break;
-        }
-        Pose gp;
-        int gm, gns;
-        double gedge;
-        if (!dubins_connect<kSafe>(lib, child, goal, ob, sd, cfg.angle_weight, red_i, gp, gm, gns, gedge)) {
-          goal_refused = true;  // (:915: the loop ends all the same - SUCCESS, the goal not in the tree, no plan)
-          break;
-        }
-        if (tid == 0) {
-          nd[kNd * n] = gp.x; nd[kNd * n + 1] = gp.y; nd[kNd * n + 2] = gp.c; nd[kNd * n + 3] = gp.s;
-          nd[kNd * n + 4] = dist + gedge;
-          ni[kNi * n] = n - 1; ni[kNi * n + 1] = pdepth + ns + gns; ni[kNi * n + 2] = 0;
-          ni[kNi * (n - 1) + 2] += 1;
-          ta[3 * n] = (double)gm; ta[3 * n + 1] = (double)gns; ta[3 * n + 2] = 0.0;
-        }
-        __syncthreads();
-        goal_node = n;
-        max_depth = pdepth + ns + gns;  // (of the plan: the steps of the path to the goal)
-        ++n;
+    const int bi = nearest_node(t, sp, cfg.angle_weight);
+    const Pose par = t.pose(bi);
+    Edge e;
+    if (!connect<kSafe, kDubins>(par, sp, cfg, sf, a.lib, t.red_i, e)) {  // a refused connect adds no node
+      if (++failed > kMaxFailed) {
+        r.sampling_failed = true;
         break;
       }
       continue;
     }
-    // connectNode, every thread alike
-    const Pose par{nd[kNd * bi], nd[kNd * bi + 1], nd[kNd * bi + 2], nd[kNd * bi + 3]};
-    const double pdist = nd[kNd * bi + 4];
-    const int pdepth = ni[kNi * bi + 1];
-    const double d = range_of<false>(par, sp, nullptr, nullptr);
-    const double angle = bearing_of<false>(par, sp, nullptr, nullptr);
-    const double len = d > cfg.max_edge_length ? cfg.max_edge_length : d;
-    const double ax = len * cos(angle), ay = len * sin(angle);
-    const Pose child = compose(par, make_pose(ax, ay, angle));
-    if (kSafe) {
-      // isSafe(node, parent) on the scaled child: a refused connect adds no node
-      if (!edge_safe(child, par, ob, sd, wp_bound)) {
-        if (++failed > kMaxFailed) {
-          sampling_failed = true;
-          break;
-        }
-        continue;
-      }
-      failed = 0;
-    }
-    double bb;
-    const double dist = pdist + sqrt(sq_distance(child, P2{par.x, par.y}, cfg.angle_weight, bb));
-    __syncthreads();  // (every thread has read the table)
-    if (tid == 0) {
-      nd[kNd * n] = child.x; nd[kNd * n + 1] = child.y; nd[kNd * n + 2] = child.c; nd[kNd * n + 3] = child.s;
-      nd[kNd * n + 4] = dist;
-      ni[kNi * n] = bi; ni[kNi * n + 1] = pdepth + 1; ni[kNi * n + 2] = 0;
-      ni[kNi * bi + 2] += 1;
-      ta[3 * n] = ax; ta[3 * n + 1] = ay; ta[3 * n + 2] = angle;
-    }
-    __syncthreads();
-    max_depth = max(max_depth, pdepth + 1);
-    ++n;
-    if (mode == 1) {
-      // isReached(goal, node), then connectNode(goal, node): the goal Pose2(gx, gy, pi) becomes a child of the node that reached it
-      const double gx = child.x - goal.x, gy = child.y - goal.y;
-      if (sqrt(gx * gx + gy * gy) <= cfg.max_edge_length) {
-        if (n >= cap) {
-          full = true;
-          break;
-        }
-        const double gd = range_of<false>(child, goal, nullptr, nullptr);
-        const double gang = bearing_of<false>(child, goal, nullptr, nullptr);
-        const double glen = gd > cfg.max_edge_length ? cfg.max_edge_length : gd;
-        const double gax = glen * cos(gang), gay = glen * sin(gang);
-        const Pose gp = compose(child, make_pose(gax, gay, gang));
-        if (kSafe && !edge_safe(gp, child, ob, sd, wp_bound)) {
-          goal_refused = true;  // the loop ends all the same (:910-922): SUCCESS, the goal not in the tree, no plan
-          break;
-        }
-        const double gdist = dist + sqrt(sq_distance(gp, P2{child.x, child.y}, cfg.angle_weight, bb));
-        if (tid == 0) {
-          nd[kNd * n] = gp.x; nd[kNd * n + 1] = gp.y; nd[kNd * n + 2] = gp.c; nd[kNd * n + 3] = gp.s;
-          nd[kNd * n + 4] = gdist;
-          ni[kNi * n] = n - 1; ni[kNi * n + 1] = pdepth + 2; ni[kNi * n + 2] = 0;
-          ni[kNi * (n - 1) + 2] += 1;
-          ta[3 * n] = gax; ta[3 * n + 1] = gay; ta[3 * n + 2] = gang;
-        }
-        __syncthreads();
-        goal_node = n;
-        max_depth = pdepth + 2;  // (of the plan: the path to the goal)
-        ++n;
+    failed = 0;
+    const int node = t.n, depth = t.depth(bi) + e.depth;
+    const double dist = t.dist(bi) + e.dist;
+    push_edge<kDubins>(t, bi, e, dist, depth);
+    r.max_depth = max(r.max_depth, depth);
+    // isReached(goal, node), then connectNode(goal, node): the goal Pose2(gx, gy, pi) becomes a child of the node that reached it
+    const double gx = e.child.x - goal.x, gy = e.child.y - goal.y;
+    if (mode == 1 && sqrt(gx * gx + gy * gy) <= cfg.max_edge_length) {
+      if (t.n >= cap) {
+        r.full = true;
         break;
       }
-    }
-  }
-  if (mode == 1 && goal_node < 0 && !sampling_failed && !goal_refused) full = true;  // (the turns ran out: the table is full)
-
-  // ---- results: the tables to memory, the leaves in node order ----
-  int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
-  for (int j = tid; j < n; j += kT) {
-    tl[2 * j] = ni[kNi * j];
-    tl[2 * j + 1] = ni[kNi * j + 1];
-    if (kDubins) {
-      double *o = lib.pose + ((size_t)ti * cap + j) * 4;
-      o[0] = nd[kNd * j]; o[1] = nd[kNd * j + 1]; o[2] = nd[kNd * j + 2]; o[3] = nd[kNd * j + 3];
-    }
-    if (nodes_out) {
-      double *o = nodes_out + ((size_t)ti * cap + j) * kNodeOut;
-      o[0] = nd[kNd * j]; o[1] = nd[kNd * j + 1];
-      o[2] = atan2(nd[kNd * j + 3], nd[kNd * j + 2]);
-      o[3] = (double)ni[kNi * j];
-      o[4] = nd[kNd * j + 4];
-      o[5] = ta[3 * j]; o[6] = ta[3 * j + 1]; o[7] = ta[3 * j + 2];
-    }
-  }
-  int n_leaves = 0;
-  if (mode == 0 && !sampling_failed) {
-    if (tid < 64) {  // (one wave lists: node order)
-      for (int base = 0; base < n; base += 64) {
-        const int j = base + lane;
-        const bool is_leaf = j < n && ni[kNi * j + 2] == 0;
-        const unsigned long long b = __ballot(is_leaf);
-        if (is_leaf) lf[n_leaves + __popcll(b & ((1ull << lane) - 1ull))] = j;
-        n_leaves += __popcll(b);
+      Edge g;
+      if (!connect<kSafe, kDubins>(e.child, goal, cfg, sf, a.lib, t.red_i, g)) {
+        goal_refused = true;  // the loop ends all the same (:910-922, :915): SUCCESS, the goal not in the tree, no plan
+        break;
       }
+      r.goal_node = t.n;
+      r.max_depth = depth + g.depth;  // (of the plan: the path to the goal, in edges or - Dubins - steps)
+      push_edge<kDubins>(t, node, g, dist + g.dist, depth + g.depth);
+      break;
     }
-  } else if (goal_node >= 0) {
-    if (tid == 0) lf[0] = goal_node;
-    n_leaves = 1;
   }
-  if (tid == 0) {
-    const int res = ((mode == 1 && full) || sampling_failed) ? R_SAMPLING_FAILURE : R_SUCCESS;
-    mt[M_NODES] = n;
-    mt[M_LEAVES] = n_leaves;
-    mt[M_HALTON] = count;
-    mt[M_RESULT] = res;
-    if (n_nodes_out) n_nodes_out[ti] = n;
-    if (result_out) result_out[ti] = res;
-    if (halton_next_out) halton_next_out[ti] = count;
-    // what the whole call is refused for: optimize2's tree does not fit the table; a plan deeper than max_actions
-    // (a tree that failed to sample offers no plan: nothing of it can be too deep)
-    if ((mode == 0 && full) || (((mode == 0 && !sampling_failed) || goal_node >= 0) && max_depth > S.A_max))
-      atomicMin(flag, DRLGX_E_CAPACITY);
-  }
+  if (mode == 1 && r.goal_node < 0 && !r.sampling_failed && !goal_refused) r.full = true;  // (the turns ran out: the table is full)
+  tree_finish<kDubins>(S, a, b, ti, t, r);
+}
+
+// The sum of the leaf counts before tree ti: its first candidate.  One wave, the same answer in every lane
+__device__ __forceinline__ int leaf_offset(const int *meta, int ti) {
+  int off = 0;
+  for (int q = threadIdx.x; q < ti; q += 64) off += meta[(size_t)q * M_STRIDE + M_LEAVES];
+  for (int m = 1; m < 64; m <<= 1) off += __shfl_xor(off, m, 64);
+  return off;
+}
+
+// An empty plan: the row zero, n_actions = 0.  One wave
+__device__ __forceinline__ void empty_plan(double *row, int32_t *n_actions, int A_max) {
+  for (int q = threadIdx.x; q < 3 * A_max; q += 64) row[q] = 0.0;
+  if (threadIdx.x == 0) *n_actions = 0;
 }
 
 // The action lists root -> leaf of every listed leaf, in the [cand][max_actions][3] layout drlgx_em_cost reads (zero behind the
@@ -588,18 +612,12 @@ __global__ __launch_bounds__(64) void k_em_leaves(int n_sel, const int32_t *env_
                                                   int32_t *n_actions) {
   const int ti = blockIdx.x, lane = threadIdx.x;
   if (ti >= n_sel) return;
-  int off = ti;
-  if (!per_tree_row) {
-    off = 0;
-    for (int q = lane; q < ti; q += 64) off += meta[(size_t)q * M_STRIDE + M_LEAVES];
-    for (int m = 1; m < 64; m <<= 1) off += __shfl_xor(off, m, 64);
-  }
+  const int off = per_tree_row ? ti : leaf_offset(meta, ti);
   const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
   const double *ta = act + (size_t)ti * cap * 3;
   const int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
   if (per_tree_row && nl == 0) {
-    for (int q = lane; q < 3 * A_max; q += 64) actions[(size_t)off * A_max * 3 + q] = 0.0;
-    if (lane == 0) n_actions[off] = 0;
+    empty_plan(actions + (size_t)off * A_max * 3, n_actions + off, A_max);
     return;
   }
   for (int k = lane; k < nl; k += 64) {
@@ -664,9 +682,7 @@ __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int 
                                                 int32_t *n_leaves_out) {
   const int ti = blockIdx.x, lane = threadIdx.x;
   if (ti >= n_sel) return;
-  int off = 0;
-  for (int q = lane; q < ti; q += 64) off += meta[(size_t)q * M_STRIDE + M_LEAVES];
-  for (int m = 1; m < 64; m <<= 1) off += __shfl_xor(off, m, 64);
+  const int off = leaf_offset(meta, ti);
   const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
   double best = __builtin_huge_val();
   int bi = 0x7fffffff;
@@ -677,21 +693,13 @@ __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int 
       bi = k;
     }
   }
-  for (int m = 1; m < 64; m <<= 1) {
-    const double od = __shfl_xor(best, m, 64);
-    const int oi = __shfl_xor(bi, m, 64);
-    if (od < best || (od == best && oi < bi)) {
-      best = od;
-      bi = oi;
-    }
-  }
+  wave_argmin(best, bi);
   // the first leaf is held whatever its cost: a NaN there is never replaced, an infinite one only by a smaller cost
   const double c0 = nl > 0 ? cost[off] : 0.0;
   if (nl > 0 && (c0 != c0 || bi >= nl || !(best < c0))) bi = 0;
   if (nl <= 0) {  // (a tree that failed to sample: no leaf, an empty plan)
-    for (int q = lane; q < 3 * A_max; q += 64) plan_out[(size_t)ti * A_max * 3 + q] = 0.0;
+    empty_plan(plan_out + (size_t)ti * A_max * 3, n_actions_out + ti, A_max);
     if (lane == 0) {
-      n_actions_out[ti] = 0;
       if (cost_out) cost_out[ti] = 0.0;
       if (n_leaves_out) n_leaves_out[ti] = 0;
     }
@@ -710,31 +718,16 @@ __global__ __launch_bounds__(64) void k_em_pick(int n_sel, int A_max, const int 
 
 size_t drlgx_em_tree_lds_bytes(int cap) { return kemt::lds_bytes(cap); }
 
-void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, const int32_t *halton_start, int cap,
-                          int mode, double max_nodes, bool obstacles, double safe_distance, const int32_t *goal_key, const double *goal_xy,
-                          double *act, int *link, int *leaf, int *meta, int *flag, double *nodes_out, int32_t *n_nodes_out,
-                          int32_t *result_out, int32_t *halton_next_out, const DrlgxDubins *dubins) {
+void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, DrlgxTreeArgs args, bool obstacles, bool dubins) {
+  using Kernel = void (*)(DrlgxState, DrlgxTreeArgs);
+  static const Kernel kernels[4] = {kemt::k_em_tree<false, false>, kemt::k_em_tree<true, false>, kemt::k_em_tree<false, true>,
+                                    kemt::k_em_tree<true, true>};  // [obstacles + 2 dubins]
   static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kemt::k_em_tree<false, false>), reinterpret_cast<const void *>(&kemt::k_em_tree<true, false>),
-                       reinterpret_cast<const void *>(&kemt::k_em_tree<false, true>), reinterpret_cast<const void *>(&kemt::k_em_tree<true, true>)};
+  const void *fns[4];
+  for (int i = 0; i < 4; ++i) fns[i] = reinterpret_cast<const void *>(kernels[i]);
   drlgx_ensure_lds_attr(attr_set, fns, 4, 160 * 1024);
-  const DrlgxDubins lib = dubins ? *dubins : DrlgxDubins{};
-  if (dubins && obstacles)
-    hipLaunchKernelGGL((kemt::k_em_tree<true, true>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
-                       cap, mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out,
-                       result_out, halton_next_out, lib);
-  else if (dubins)
-    hipLaunchKernelGGL((kemt::k_em_tree<false, true>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
-                       cap, mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
-                       halton_next_out, lib);
-  else if (obstacles)
-    hipLaunchKernelGGL((kemt::k_em_tree<true, false>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
-                       cap, mode, max_nodes, safe_distance, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out,
-                       result_out, halton_next_out, lib);
-  else
-    hipLaunchKernelGGL((kemt::k_em_tree<false, false>), dim3(n_sel), dim3(kemt::kT), kemt::lds_bytes(cap), st, S, n_sel, env_sel, halton_start,
-                       cap, mode, max_nodes, 0.0, goal_key, goal_xy, act, link, leaf, meta, flag, nodes_out, n_nodes_out, result_out,
-                       halton_next_out, lib);
+  if (!obstacles) args.safe_distance = 0.0;
+  hipLaunchKernelGGL(kernels[(obstacles ? 1 : 0) + (dubins ? 2 : 0)], dim3(args.n_sel), dim3(kemt::kT), kemt::lds_bytes(args.cap), st, S, args);
 }
 void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
                                    const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions) {

@@ -207,6 +207,32 @@ def test_the_connect_counter_ends_a_tree_and_a_goal_edge_without_a_path_is_an_em
         np.testing.assert_array_equal(x, y)
 
 
+# (library, environment, nodes): cases of test_trees_match_the_restatement whose tree reaches its goal, with the tree's size, the goal
+# node included - at least one per library, the smallest there are (the 64- and 320-entry libraries have none below 92 and 74)
+LAST_SLOT_CASES = [("36", 0, 10), ("36", 1, 24), ("64", 2, 92), ("66", 0, 21), ("66", 2, 18), ("320", 0, 74)]
+
+
+@pytest.mark.parametrize("name, env, size", LAST_SLOT_CASES)
+def test_a_goal_reached_by_the_node_that_fills_the_table_is_not_connected(ctx, name, env, size):
+    """A table one node short of the whole tree: the node that reaches the goal takes the last slot, the goal edge is not made -
+    SAMPLING_FAILURE, no plan, and everything up to there as with the full table."""
+    ctx.use(DC.LIBS[name])
+    start, goal, tag = DC.START_INDICES[env], DC.GOALS[name][env], "library %s env %d" % (name, env)
+    t = ctx.ref(name, env, start, goal)
+    assert DC.entitled(t) and len(t) == size and t.goal_node == size - 1, tag
+    whole = ctx.rrt([env], [goal], [start])
+    o = ctx.rrt([env], [goal], [start], cap=size - 1)
+    assert ctx.eng.status() == 0
+    assert int(whole["n_nodes"][0]) == size and int(whole["result"][0]) == R.SUCCESS, tag
+    assert int(o["result"][0]) == R.SAMPLING_FAILURE and int(o["n_nodes"][0]) == size - 1, tag
+    assert int(o["n_actions"][0]) == 0 and np.all(o["plan"][0] == 0.0), tag
+    assert int(o["halton_next"][0]) == int(whole["halton_next"][0]), tag
+    np.testing.assert_array_equal(o["nodes"][0][:size - 1], whole["nodes"][0][:size - 1], err_msg=tag)
+    short = ctx.ref(name, env, start, goal, cap=size - 1)
+    assert DC.entitled(short) and short.result == R.SAMPLING_FAILURE and len(short) == size - 1 and short.goal_node == -1, tag
+    check_tree(o, 0, short, tag)
+
+
 # ---------------------------------------------------------------- 5
 def test_refusals(ctx):
     sel, starts = ctx.i32(list(range(DC.N_ENVS))), ctx.i32(DC.START_INDICES)
