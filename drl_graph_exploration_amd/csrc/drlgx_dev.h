@@ -728,18 +728,22 @@ void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, const int32_t *
                             int n_max);
 size_t drlgx_fm2_scratch_doubles(const DrlgxState &S, int nm_max);
 // flag[0] (zeroed by the caller) = DRLGX_E_INVALID / DRLGX_E_CAPACITY if a candidate names no environment, has more than max_actions
-// actions or more than nm_max predicted measurements
+// actions or more than nm_max predicted measurements.  core ([candidate][max_actions] or null = every action): the actions that are
+// core poses - a non-core step extends the chain and predicts no measurement (null launches the kernel without the mask)
 void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *actions,
-                            const int32_t *n_actions, int nm_max, int *flag);
+                            const int32_t *n_actions, const uint8_t *core, int nm_max, int *flag);
 void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
-                             const double *actions, const int32_t *n_actions, const double *sig, size_t sig_stride, double *scratch,
-                             size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride, int32_t *n_out);
+                             const double *actions, const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride,
+                             double *scratch, size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride,
+                             int32_t *n_out);
 // Leaf evaluation of candidate plans (k_em.hip): nc candidates, one workgroup each; cov = what drlgx_launch_fm2_update left for the
-// same nc candidates ([nc][cov_stride][9]); the candidate arrays and the outputs (any of them null) start at the first of them
+// same nc candidates ([nc][cov_stride][9]); the candidate arrays and the outputs (any of them null) start at the first of them.
+// core ([nc][max_actions] or null): only the core steps enter the leaf's map; distance ([nc] or null): the leaf's distance instead
+// of the plan's own.  Both null launch the kernel without either.
 size_t drlgx_em_lds_bytes(const DrlgxState &S);
 void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
-                          const int32_t *n_actions, const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
-                          double *info_out);
+                          const int32_t *n_actions, const uint8_t *core, const double *distance, const double *cov, int cov_stride,
+                          int algorithm, double *unc_out, double *cost_out, double *info_out);
 // Expected map entropy of candidate plans (k_og.hip): nc candidates in drlgx_em_cost's layout, one workgroup each, in one launch; the
 // outputs (any of them null): entropy / cost [nc], prob [nc][V].  The check: flag[0] (zeroed by the caller) = DRLGX_E_INVALID if a
 // candidate names no environment or has more than max_actions actions
@@ -782,10 +786,14 @@ struct DrlgxTreeArgs {
 size_t drlgx_em_tree_lds_bytes(int cap);
 // obstacles: the kSafe = true instantiation (isSafe, the retry loop of sampleNode, the two counters of 1000, the shrink at the start
 // of the call); a tree it ends with SAMPLING_FAILURE has no leaf and touches no flag.  dubins: the kDubins = true instantiation,
-// mode 1 only; drlgx_launch_em_leaves_dubins then writes the plan: one row per step, row ti of the outputs.
+// either mode; drlgx_launch_em_leaves_dubins then writes the plans, one row per step: per_tree_row (mode 1), row ti of the outputs is
+// the path to the goal; else (mode 0) every leaf is a candidate as drlgx_launch_em_leaves lists them, with its core mask
+// [cand][A_max] (1 at each edge's last step) and its tree distance [cand].  cand_env / core / distance may be null.
 void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, DrlgxTreeArgs args, bool obstacles, bool dubins);
-void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
-                                   const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions);
+void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, double angle_weight,
+                                   const double *act, const int *link, const int *leaf, const int *meta, const DrlgxDubins &lib,
+                                   int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions, uint8_t *core,
+                                   double *distance);
 // the action lists root -> leaf in drlgx_em_cost's candidate layout; per_tree_row: row ti of the outputs instead of the running count
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions);

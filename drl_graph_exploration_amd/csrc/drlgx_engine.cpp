@@ -97,6 +97,13 @@ struct drlgx_engine {
   double sampler_max_nodes = 0.5, sampler_safe_distance = 0.0;
   int sampler_dubins = 0;
   int sampler_obstacles = 0;  // drlgx_set_sampler_obstacles: the sampler's obstacle logic (safe_distance > 0), off unless asked for
+  // drlgx_set_dubins_leaf_scoring: drlgx_em_plan under the Dubins control model, off unless asked for; the leaves' core masks and
+  // tree distances (grown with the candidates), the number of candidates the last served call left (drlgx_em_plan_leaves)
+  int dubins_leaf_scoring = 0;
+  uint8_t *tree_cand_core = nullptr;
+  double *tree_cand_dist = nullptr;
+  size_t tree_cand_steps_cap = 0, tree_cand_last = 0;
+  bool tree_cand_last_steps = false;
   // drlgx_set_dubins_library_host: the Dubins path library, the opt-in of the Dubins control model (dubins.n == 0: none loaded) - on
   // the device for the kernel, on the host for drlgx_dubins_library; the nodes' poses for the plan (grown with the trees' tables)
   DrlgxDubins dubins = {};
@@ -985,7 +992,7 @@ static const int kFm2Chunk = 128, kFm2MaxMeas = 256;
 // one update launch per kFm2Chunk candidates.  cov_out / n_out hold all n_cand candidates - or, chunk_out, only the chunk at hand,
 // which after(c0, nc) consumes on the engine's stream before the next chunk's launch overwrites it.
 static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                   double *cov_out, int out_stride_poses, int32_t *n_out, bool chunk_out, const std::function<void(int, int)> &after) {
+                   const uint8_t *core_dev, double *cov_out, int out_stride_poses, int32_t *n_out, bool chunk_out, const std::function<void(int, int)> &after) {
   const DrlgxState &S = e->S;
   if (!e->fm2_sig) {
     const size_t nmax = (size_t)3 * S.P_max + 2 * S.L_max;
@@ -1006,7 +1013,7 @@ static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, con
     const int nc = std::min(kFm2Chunk, n_cand - c0);
     // (the launch's first candidate through the pointers: the kernel's own offset stays 0)
     drlgx_launch_fm2_update(S, e->stream, 0, nc, cand_env_dev + c0, e->fm2_slot, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
-                            e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_scratch_stride, e->fm2_iscratch, kFm2MaxMeas,
+                            core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_scratch_stride, e->fm2_iscratch, kFm2MaxMeas,
                             chunk_out ? cov_out : cov_out + (size_t)c0 * out_stride_poses * 9, out_stride_poses,
                             chunk_out ? n_out : n_out + c0);
     after(c0, nc);
@@ -1021,15 +1028,30 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
       out_stride_poses < e->S.P_max + e->S.A_max)
     return DRLGX_E_INVALID;
   if (n_cand == 0) return DRLGX_OK;
-  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, cov_out_dev, out_stride_poses, n_out_dev, false, [](int, int) {});
+  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, cov_out_dev, out_stride_poses, n_out_dev, false,
+                 [](int, int) {});
+}
+
+// drlgx_fm2_update with a core mask: a non-core step gets its pose and its odometry factor and predicts no measurement
+int drlgx_fm2_update_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                           const uint8_t *core_dev, double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !cov_out_dev || !n_out_dev ||
+      out_stride_poses < e->S.P_max + e->S.A_max)
+    return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;
+  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, cov_out_dev, out_stride_poses, n_out_dev, false,
+                 [](int, int) {});
 }
 
 // The leaf evaluation of EMPlanner2D::optimize2 for candidate action lists: the covariance update above into the engine's scratch,
 // a chunk at a time, and k_em.hip on each chunk.  What the kernels could only report through the status word - a candidate that
 // names no environment, a plan beyond max_actions, more than kFm2MaxMeas predicted measurements - is found out first (one small
-// launch and one read of its flag), so that such a call returns its code and leaves the status word alone.
+// launch and one read of its flag), so that such a call returns its code and leaves the status word alone.  core_dev / distance_dev
+// (either may be null): the leaves of a tree whose edges have non-core steps - only core poses predict measurements and enter the
+// leaf's map, the cost takes the tree's distance.
 static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                       int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+                       const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
   const DrlgxState &S = e->S;
   if (drlgx_em_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
   const int stride = S.P_max + S.A_max;
@@ -1041,12 +1063,13 @@ static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev,
   }
   int flag = 0;
   HIPCHK(e, hipMemsetAsync(e->em_flag, 0, sizeof(int), e->stream));
-  drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, kFm2MaxMeas, e->em_flag);
+  drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, kFm2MaxMeas, e->em_flag);
   HIPCHK(e, hipMemcpyAsync(&flag, e->em_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   if (flag) return flag;
-  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->em_cov, stride, e->em_nout, true, [&](int c0, int nc) {
-    drlgx_launch_em_cost(S, e->stream, nc, cand_env_dev + c0, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0, e->em_cov, stride,
+  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, e->em_cov, stride, e->em_nout, true, [&](int c0, int nc) {
+    drlgx_launch_em_cost(S, e->stream, nc, cand_env_dev + c0, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
+                         core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, distance_dev ? distance_dev + c0 : nullptr, e->em_cov, stride,
                          algorithm, uncertainty_out_dev ? uncertainty_out_dev + c0 : nullptr, cost_out_dev ? cost_out_dev + c0 : nullptr,
                          info_out_dev ? info_out_dev + (size_t)c0 * S.V * 3 : nullptr);
   });
@@ -1059,7 +1082,20 @@ int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
       (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
     return DRLGX_E_INVALID;
   if (n_cand == 0) return DRLGX_OK;
-  return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, algorithm, uncertainty_out_dev, cost_out_dev, info_out_dev);
+  return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, nullptr, algorithm, uncertainty_out_dev, cost_out_dev,
+                     info_out_dev);
+}
+
+int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                        const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev,
+                        double *cost_out_dev, double *info_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || (!uncertainty_out_dev && !cost_out_dev) ||
+      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
+    return DRLGX_E_INVALID;
+  if (n_cand == 0) return DRLGX_OK;
+  return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, distance_dev, algorithm, uncertainty_out_dev,
+                     cost_out_dev, info_out_dev);
 }
 
 // calculateUncertainty_OG_SHANNON + costFunction for candidate action lists (k_og.hip).  The candidates are checked first, as in
@@ -1103,6 +1139,13 @@ int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled) {
   DRLGX_ENTER(e);
   if (!e) return DRLGX_E_INVALID;
   e->sampler_obstacles = enabled ? 1 : 0;
+  return DRLGX_OK;
+}
+
+int drlgx_set_dubins_leaf_scoring(drlgx_engine *e, int enabled) {
+  DRLGX_ENTER(e);
+  if (!e) return DRLGX_E_INVALID;
+  e->dubins_leaf_scoring = enabled ? 1 : 0;
   return DRLGX_OK;
 }
 
@@ -1221,7 +1264,7 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
                      const int32_t *goal_key_dev, const double *goal_xy_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev,
                      int32_t *result_out_dev, int32_t *halton_next_out_dev, std::vector<int> &meta_h) {
   int r;
-  const bool dubins = e->sampler_dubins != 0;  // (tree_args_ok: mode 1 with a library loaded)
+  const bool dubins = e->sampler_dubins != 0;  // (tree_args_ok: a library is loaded; mode 0 behind drlgx_set_dubins_leaf_scoring)
   if ((size_t)n_sel > e->tree_sel_cap) {
     if ((r = scratch_reserve(e, &e->tree_meta, (size_t)n_sel * kTreeMeta + 1))) return r;  // (+ the flag, behind the trees' rows)
     e->tree_sel_cap = (size_t)n_sel;
@@ -1255,12 +1298,12 @@ static int tree_grow(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, con
 }
 
 // The Dubins control model is served where a library is loaded (drlgx_set_dubins_library_host, the opt-in) and the planner is
-// rrt_planner; everywhere else the flag is refused.
+// rrt_planner - or optimize2 behind its own opt-in, drlgx_set_dubins_leaf_scoring; everywhere else the flag is refused.
 static bool tree_args_ok(const drlgx_engine *e, int n_sel, const void *env_sel, const void *halton_start, int cap, const void *plan_out,
                          const void *n_actions_out, bool rrt) {
   return e && n_sel >= 0 && env_sel && halton_start && plan_out && n_actions_out && cap >= 1 && cap <= kTreeMaxNodes &&
          (e->sampler_obstacles ? e->sampler_safe_distance >= 0.0 : e->sampler_safe_distance == 0.0) &&
-         (!e->sampler_dubins || (rrt && e->dubins.n > 0));
+         (!e->sampler_dubins || (e->dubins.n > 0 && (rrt || e->dubins_leaf_scoring)));
 }
 
 int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
@@ -1286,16 +1329,60 @@ int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const 
     if ((r = scratch_reserve(e, &e->tree_cost, n_cand))) return r;
     e->tree_cand_cap = n_cand;
   }
+  const bool steps = e->sampler_dubins != 0;  // the leaves have non-core steps: one row per step, the mask, the tree's distance
+  if (steps && n_cand > e->tree_cand_steps_cap) {
+    if ((r = scratch_reserve(e, &e->tree_cand_core, n_cand * S.A_max))) return r;
+    if ((r = scratch_reserve(e, &e->tree_cand_dist, n_cand))) return r;
+    e->tree_cand_steps_cap = n_cand;
+  }
+  e->tree_cand_last = 0;
   if (n_cand > 0) {  // (every tree failed to sample: nothing to score, the pick below writes the empty plans)
-    drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
-                           0, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
+    if (steps)
+      drlgx_launch_em_leaves_dubins(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, S.cfg.angle_weight, e->tree_act, e->tree_link,
+                                    e->tree_leaf, e->tree_meta, e->dubins, 0, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n,
+                                    e->tree_cand_core, e->tree_cand_dist);
+    else
+      drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
+                             0, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
     if ((r = check_launch(e))) return r;
-    if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, algorithm, nullptr, e->tree_cost, nullptr)))
+    if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, steps ? e->tree_cand_core : nullptr,
+                         steps ? e->tree_cand_dist : nullptr, algorithm, nullptr, e->tree_cost, nullptr)))
       return r;
+    e->tree_cand_last = n_cand;
+    e->tree_cand_last_steps = steps;
   }
   drlgx_launch_em_pick(e->stream, n_sel, S.A_max, e->tree_meta, e->tree_cost, e->tree_cand_act, e->tree_cand_n, plan_out_dev,
                        n_actions_out_dev, cost_out_dev, n_leaves_out_dev);
   return check_launch(e);
+}
+
+// The leaves the last served drlgx_em_plan scored, as it handed them to the body of drlgx_em_cost_steps: device-to-device copies on
+// the engine's stream.
+int drlgx_em_plan_leaves(drlgx_engine *e, int capacity, int32_t *n_out_host, int32_t *has_steps_out_host, int32_t *cand_env_out_dev,
+                         double *actions_out_dev, int32_t *n_actions_out_dev, uint8_t *core_out_dev, double *distance_out_dev,
+                         double *cost_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || !n_out_host || capacity < 0) return DRLGX_E_INVALID;
+  const size_t n = e->tree_cand_last, m = std::min(n, (size_t)capacity), A = (size_t)e->S.A_max;
+  const bool steps = e->tree_cand_last_steps;
+  if (m > 0 && !steps && distance_out_dev) return DRLGX_E_INVALID;  // (no distance was kept: refused before anything is written)
+  *n_out_host = (int32_t)n;
+  if (has_steps_out_host) *has_steps_out_host = steps ? 1 : 0;
+  if (m == 0) return DRLGX_OK;
+  auto copy = [&](void *dst, const void *src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, e->stream) : hipSuccess;
+  };
+  HIPCHK(e, copy(cand_env_out_dev, e->tree_cand_env, m * sizeof(int32_t)));
+  HIPCHK(e, copy(actions_out_dev, e->tree_cand_act, m * A * 3 * sizeof(double)));
+  HIPCHK(e, copy(n_actions_out_dev, e->tree_cand_n, m * sizeof(int32_t)));
+  HIPCHK(e, copy(cost_out_dev, e->tree_cost, m * sizeof(double)));
+  if (steps) {
+    HIPCHK(e, copy(core_out_dev, e->tree_cand_core, m * A));
+    HIPCHK(e, copy(distance_out_dev, e->tree_cand_dist, m * sizeof(double)));
+  } else {  // every action a core pose; the distance is the plan's own: none is kept
+    if (core_out_dev) HIPCHK(e, hipMemsetAsync(core_out_dev, 1, m * A, e->stream));
+  }
+  return DRLGX_OK;
 }
 
 int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *goal_key_dev, const double *goal_xy_dev,
@@ -1311,8 +1398,8 @@ int drlgx_rrt_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const
                     result_out_dev, halton_next_out_dev, meta);
   if (r) return r;
   if (e->sampler_dubins)  // one row per step, recomputed from the nodes' library entries
-    drlgx_launch_em_leaves_dubins(e->stream, n_sel, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
-                                  e->dubins, plan_out_dev, n_actions_out_dev);
+    drlgx_launch_em_leaves_dubins(e->stream, n_sel, env_sel_dev, max_tree_nodes, e->S.A_max, e->S.cfg.angle_weight, e->tree_act, e->tree_link,
+                                  e->tree_leaf, e->tree_meta, e->dubins, 1, nullptr, plan_out_dev, n_actions_out_dev, nullptr, nullptr);
   else
     drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, e->S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta, 1,
                            nullptr, plan_out_dev, n_actions_out_dev);

@@ -7,7 +7,8 @@
 // without simulating, without noise and without re-solving.  The leaf's map holds EVERY pose as a core pose with
 // information = Sigma_i^-1 (cov.inverse(), :521-523): the P old ones at the current estimate, one per action at the noise-free
 // predicted pose chained from the last estimate.  The leaf's virtual map is a copy of the root's whose information is rebuilt;
-// its probabilities stay the live environment's.  Nothing of the live environment is written.
+// its probabilities stay the live environment's.  Nothing of the live environment is written.  (k_em_cost<true>: the leaves of the
+// Dubins control model, whose edges have non-core steps that stay out of the leaf's map - see the kernel.)
 //
 // One workgroup per candidate.  The P + K poses are staged in LDS once (x y c s, the LLT factor of the information in the layout
 // kmap::predict_info reads, the skip flag).  The cell pass is cell-centric: a wave takes an 8 x 8 tile of cells, a lane walks the
@@ -50,9 +51,14 @@ __device__ __forceinline__ double plan_distance(const drlgx_config &cfg, const d
 
 // cov: [gridDim.x][cov_stride][9], the covariances k_fm2_update left for the same candidates; cand_env / actions / n_actions and the
 // outputs (any of them null) start at this launch's first candidate.
+// kSteps: the leaf of a tree whose edges have intermediate steps (the Dubins control model, Planner2D.cpp:472-551): `core`
+// ([candidate][max_actions] or null = every action) marks the actions whose pose enters the leaf's map - updateTrajectory_EM adds
+// the last pose of every edge only; a non-core step still moves the pose chain -, and `distance` ([candidate] or null) is the
+// leaf's distance as the tree accumulated it (:293-303), used instead of plan_distance.  kSteps = false reads neither.
+template <bool kSteps>
 __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *cand_env, const double *actions, const int32_t *n_actions,
                                                 const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
-                                                double *info_out) {
+                                                double *info_out, const uint8_t *core, const double *distance) {
   const DrlgxState &S = DRLGX_KS_REF;
   extern __shared__ __attribute__((aligned(16))) double em_smem[];
   const drlgx_config &cfg = S.cfg;
@@ -74,6 +80,10 @@ __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *c
   for (int i = tid; i < np; i += kT) {
     const Pose ps = leaf_pose(ep, P, act, i);
     sp[4 * i] = ps.x; sp[4 * i + 1] = ps.y; sp[4 * i + 2] = ps.c; sp[4 * i + 3] = ps.s;
+    if (kSteps && core && i >= P && !core[(size_t)ci * S.A_max + (i - P)]) {  // not in the leaf's map: nothing of it is factored
+      pskip[i] = 1;
+      continue;
+    }
     // information = cov.inverse() (Planner2D.cpp:521-523): cofactors of the symmetric 3 x 3
     const double *c = cv + (size_t)i * 9;
     const double c00 = c[0], c10 = c[3], c20 = c[6], c11 = c[4], c21 = c[7], c22 = c[8];
@@ -102,7 +112,7 @@ __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *c
     o[6] = r00; o[7] = r11; o[8] = r22;
     pskip[i] = skip;
   }
-  if (tid == kT - 1) *sdist = plan_distance(cfg, act, K);
+  if (tid == kT - 1) *sdist = kSteps && distance ? distance[ci] : plan_distance(cfg, act, K);
   __syncthreads();
 
   // ---- cell pass: one 8 x 8 tile of cells per wave and round (lane = 8 (row mod 8) + (col mod 8), as kmap::cell_pass) ----
@@ -179,11 +189,15 @@ __global__ __launch_bounds__(kT) void k_em_cost(DRLGX_KS_PARAM, const int32_t *c
 size_t drlgx_em_lds_bytes(const DrlgxState &S) { return kem::lds_bytes(S.P_max + S.A_max); }
 
 void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
-                          const int32_t *n_actions, const double *cov, int cov_stride, int algorithm, double *unc_out, double *cost_out,
-                          double *info_out) {
+                          const int32_t *n_actions, const uint8_t *core, const double *distance, const double *cov, int cov_stride,
+                          int algorithm, double *unc_out, double *cost_out, double *info_out) {
   static bool attr_set[32] = {false};
-  const void *fns[] = {reinterpret_cast<const void *>(&kem::k_em_cost)};
-  drlgx_ensure_lds_attr(attr_set, fns, 1, (int)kmap::kLdsBudget);
-  hipLaunchKernelGGL(kem::k_em_cost, dim3(nc), dim3(kem::kT), drlgx_em_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions, n_actions, cov,
-                     cov_stride, algorithm, unc_out, cost_out, info_out);
+  const void *fns[] = {reinterpret_cast<const void *>(&kem::k_em_cost<false>), reinterpret_cast<const void *>(&kem::k_em_cost<true>)};
+  drlgx_ensure_lds_attr(attr_set, fns, 2, (int)kmap::kLdsBudget);
+  if (core || distance)
+    hipLaunchKernelGGL(kem::k_em_cost<true>, dim3(nc), dim3(kem::kT), drlgx_em_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions,
+                       n_actions, cov, cov_stride, algorithm, unc_out, cost_out, info_out, core, distance);
+  else
+    hipLaunchKernelGGL(kem::k_em_cost<false>, dim3(nc), dim3(kem::kT), drlgx_em_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions,
+                       n_actions, cov, cov_stride, algorithm, unc_out, cost_out, info_out, core, distance);
 }

@@ -55,8 +55,8 @@
 // 1000, the waypoint bound.
 //
 //
-// THE DUBINS CONTROL MODEL (kDubins = true; rrt_planner only, launched when drlgx_set_dubins_library_host has loaded a library and the
-// sampler's Dubins flag is set) replaces the body of connectNode - connect<kSafe, true> -, restated from the same file:
+// THE DUBINS CONTROL MODEL (kDubins = true; launched when drlgx_set_dubins_library_host has loaded a library and the sampler's Dubins
+// flag is set - for optimize2 behind drlgx_set_dubins_leaf_scoring as well: the same growth loop, its stop rule and its shrink) replaces the body of connectNode - connect<kSafe, true> -, restated from the same file:
 //   the library (:1359-1414)     built by the engine on the host, SoA: the end point of every (v, w, duration) path from Pose2(0, 0, 0)
 //   sampleNode (:41-45, :110-115)   the generator has dimension 2: the same x, y in bases 2 and 3; the sample's theta is 0 and unread
 //   connectNodeDubinsPath (:157-176)   local = the sample in the parent's frame; the FIRST entry in library order with
@@ -77,7 +77,8 @@
 //                                node's depth counts STEPS), distance = parent.distance + v dt n + |w dt n| angle_weight
 //   the goal edge (:915)         connectNode(goal, node): the goal joins only if a library path from the node ends within
 //                                tolerance_radius of it and is safe - the goal NODE is that path's last pose; else SUCCESS, no plan
-// The node's edge record is (library index, num_steps, 0) instead of an odometry; k_em_leaves_dubins replays the steps for the plan.
+// The node's edge record is (library index, num_steps, 0) instead of an odometry; k_em_leaves_dubins replays the steps for the plans
+// and, for optimize2, marks each edge's last step as the core pose of the leaf evaluation (k_em.hip, k_fm2.hip).
 // Loop bounds: the library size, the largest num_steps, cap, the two counters of 1000.
 //
 // The live belief is only read.  Built with -ffp-contract=off: the nearest-node comparison and the safety tests are gates.
@@ -524,7 +525,7 @@ __device__ __forceinline__ void tree_finish(const DrlgxState &S, const DrlgxTree
 }
 
 // One tree per workgroup (DrlgxTreeArgs in drlgx_dev.h).  kSafe: the obstacle logic with the planner parameter safe_distance (> 0);
-// kSafe = false never reads it.  kDubins: the Dubins control model with the library a.lib (mode 1 only; kDubins = false never reads
+// kSafe = false never reads it.  kDubins: the Dubins control model with the library a.lib (either mode; kDubins = false never reads
 // it).  Growth: one accepted node per turn - or, kSafe || kDubins, one refused connect, at most kMaxFailed in a row.
 template <bool kSafe, bool kDubins>
 __global__ __launch_bounds__(kT) void k_em_tree(DrlgxState S, DrlgxTreeArgs a) {
@@ -637,41 +638,77 @@ __global__ __launch_bounds__(64) void k_em_leaves(int n_sel, const int32_t *env_
   }
 }
 
-// rrt_planner's plan under the Dubins model: one row per STEP root -> goal, Edge::getOdoms (Planner2D.h:143-151) - between(previous
-// pose, this pose), the origin moving along -, the steps integrated again from the parent's stored pose and the node's library entry.
-// Row ti of the outputs; a tree without a goal node has no plan.  Lane q takes the q-th node of the path from the goal up (at most
-// cap - 1 parents); n_actions = the goal's depth in steps (<= A_max: a deeper path has refused the call).
-__global__ __launch_bounds__(64) void k_em_leaves_dubins(int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
-                                                         const int *meta, DrlgxDubins lib, double *actions, int32_t *n_actions) {
+// The plans under the Dubins model: one row per STEP root -> leaf, Edge::getOdoms (Planner2D.h:143-151) - between(previous pose,
+// this pose), the origin moving along -, the steps integrated again from the parent's stored pose and the node's library entry.
+// per_tree_row (rrt_planner): row ti of the outputs is the path to the goal; a tree without a goal node has the empty plan.  Else
+// (optimize2) every listed leaf is a candidate of drlgx_em_cost_steps, tree ti's first at the sum of the leaf counts before it, with
+// cand_env, the core mask - 1 at the last step of every edge, the only pose of an edge that updateTrajectory_EM puts into the
+// leaf's map (Planner2D.cpp:498) - and the leaf's distance, the edges' v dt n + |w dt n| angle_weight summed from the root down as
+// the tree summed them (:293-303).  One wave per tree, the leaves one after the other; lane q takes the q-th node of the path from
+// the leaf up (at most cap - 1 parents); n_actions = the leaf's depth in steps (<= A_max: a deeper leaf has refused the call).
+__global__ __launch_bounds__(64) void k_em_leaves_dubins(int n_sel, const int32_t *env_sel, int cap, int A_max, double angle_weight,
+                                                         const double *act, const int *link, const int *leaf, const int *meta,
+                                                         DrlgxDubins lib, int per_tree_row, int32_t *cand_env, double *actions,
+                                                         int32_t *n_actions, uint8_t *core, double *distance) {
   const int ti = blockIdx.x, lane = threadIdx.x;
   if (ti >= n_sel) return;
+  const int off = per_tree_row ? ti : leaf_offset(meta, ti);
   const int nl = meta[(size_t)ti * M_STRIDE + M_LEAVES];
   const double *ta = act + (size_t)ti * cap * 3, *tp = lib.pose + (size_t)ti * cap * 4;
-  const int *tl = link + (size_t)ti * cap * 2;
-  double *row = actions + (size_t)ti * A_max * 3;
-  const int total = nl > 0 ? tl[2 * leaf[(size_t)ti * cap] + 1] : 0;
-  for (int q = lane; q < 3 * A_max; q += 64)
-    if (q >= 3 * total) row[q] = 0.0;
-  if (lane == 0) n_actions[ti] = total;
-  if (nl == 0) return;
-  int j = leaf[(size_t)ti * cap];
-  for (int k = 0; k < lane && j > 0; ++k) j = tl[2 * j];
-  for (int turn = 0; turn < cap && j > 0; turn += 64) {
-    const int par = tl[2 * j], m = (int)ta[3 * j];
-    const int ns = min((int)ta[3 * j + 1], lib.max_steps), first = tl[2 * j + 1] - ns;
-    if (m >= 0 && m < lib.n && par >= 0 && par < cap) {
-      const double vdt = lib.v[m] * lib.dt, wdt = lib.w[m] * lib.dt;
-      Pose p{tp[4 * par], tp[4 * par + 1], tp[4 * par + 2], tp[4 * par + 3]};
-      for (int s = 0; s < ns; ++s) {
-        const Pose nx = dubins_step(p, vdt, wdt);
-        const Pose od = between(p, nx, nullptr);
-        if (first + s >= 0 && first + s < A_max) {
-          row[3 * (first + s)] = od.x; row[3 * (first + s) + 1] = od.y; row[3 * (first + s) + 2] = theta_of(od);
-        }
-        p = nx;
-      }
+  const int *tl = link + (size_t)ti * cap * 2, *lf = leaf + (size_t)ti * cap;
+  if (per_tree_row && nl == 0) {
+    empty_plan(actions + (size_t)off * A_max * 3, n_actions + off, A_max);
+    return;
+  }
+  for (int k = 0; k < nl; ++k) {
+    const size_t c = (size_t)off + k;
+    const int node = lf[k], total = tl[2 * node + 1];
+    double *row = actions + c * A_max * 3;
+    for (int q = lane; q < 3 * A_max; q += 64)
+      if (q >= 3 * total) row[q] = 0.0;
+    if (core) {
+      for (int q = lane; q < A_max; q += 64) core[c * A_max + q] = 0;
+      __syncthreads();  // (the ones below come from other lanes)
     }
-    for (int k = 0; k < 64 && j > 0; ++k) j = tl[2 * j];
+    if (lane == 0) {
+      n_actions[c] = total;
+      if (cand_env) cand_env[c] = env_sel[ti];
+    }
+    int j = node;
+    for (int q = 0; q < lane && j > 0; ++q) j = tl[2 * j];
+    for (int turn = 0; turn < cap && j > 0; turn += 64) {
+      const int par = tl[2 * j], m = (int)ta[3 * j];
+      const int ns = min((int)ta[3 * j + 1], lib.max_steps), first = tl[2 * j + 1] - ns;
+      if (m >= 0 && m < lib.n && par >= 0 && par < cap) {
+        const double vdt = lib.v[m] * lib.dt, wdt = lib.w[m] * lib.dt;
+        Pose p{tp[4 * par], tp[4 * par + 1], tp[4 * par + 2], tp[4 * par + 3]};
+        for (int s = 0; s < ns; ++s) {
+          const Pose nx = dubins_step(p, vdt, wdt);
+          const Pose od = between(p, nx, nullptr);
+          if (first + s >= 0 && first + s < A_max) {
+            row[3 * (first + s)] = od.x; row[3 * (first + s) + 1] = od.y; row[3 * (first + s) + 2] = theta_of(od);
+          }
+          p = nx;
+        }
+        if (core && ns > 0 && first + ns - 1 >= 0 && first + ns - 1 < A_max) core[c * A_max + first + ns - 1] = 1;
+      }
+      for (int q = 0; q < 64 && j > 0; ++q) j = tl[2 * j];
+    }
+    if (distance && lane == 0) {
+      int ne = 0;  // edges root -> leaf (at most cap - 1)
+      for (int q = node; q > 0 && ne < cap; q = tl[2 * q]) ++ne;
+      double d = 0.0;
+      for (int i = ne - 1; i >= 0; --i) {  // the edge i parents above the leaf; the root's first
+        int q = node;
+        for (int u = 0; u < i; ++u) q = tl[2 * q];
+        const int m = (int)ta[3 * q];
+        if (m < 0 || m >= lib.n) continue;
+        const int ns = min((int)ta[3 * q + 1], lib.max_steps);
+        const double vdt = lib.v[m] * lib.dt, wdt = lib.w[m] * lib.dt;
+        d = d + (vdt * (double)ns + fabs(wdt * (double)ns) * angle_weight);
+      }
+      distance[c] = d;
+    }
   }
 }
 
@@ -729,10 +766,12 @@ void drlgx_launch_em_tree(const DrlgxState &S, hipStream_t st, DrlgxTreeArgs arg
   if (!obstacles) args.safe_distance = 0.0;
   hipLaunchKernelGGL(kernels[(obstacles ? 1 : 0) + (dubins ? 2 : 0)], dim3(args.n_sel), dim3(kemt::kT), kemt::lds_bytes(args.cap), st, S, args);
 }
-void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, int cap, int A_max, const double *act, const int *link, const int *leaf,
-                                   const int *meta, const DrlgxDubins &lib, double *actions, int32_t *n_actions) {
-  hipLaunchKernelGGL(kemt::k_em_leaves_dubins, dim3(n_sel), dim3(64), 0, st, n_sel, cap, A_max, act, link, leaf, meta, lib, actions,
-                     n_actions);
+void drlgx_launch_em_leaves_dubins(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, double angle_weight,
+                                   const double *act, const int *link, const int *leaf, const int *meta, const DrlgxDubins &lib,
+                                   int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions, uint8_t *core,
+                                   double *distance) {
+  hipLaunchKernelGGL(kemt::k_em_leaves_dubins, dim3(n_sel), dim3(64), 0, st, n_sel, env_sel, cap, A_max, angle_weight, act, link, leaf,
+                     meta, lib, per_tree_row, cand_env, actions, n_actions, core, distance);
 }
 void drlgx_launch_em_leaves(hipStream_t st, int n_sel, const int32_t *env_sel, int cap, int A_max, const double *act, const int *link,
                             const int *leaf, const int *meta, int per_tree_row, int32_t *cand_env, double *actions, int32_t *n_actions) {

@@ -180,10 +180,14 @@ __device__ inline void cov_old_new(const Cand &c, int r0, int nr, int b, double 
 
 // One workgroup per candidate.  scratch (per candidate, doubles): cov_new 9K | F 9K | Fs 9K | NN 9K^2 | J 10 nm_max | T dim_max^2
 // | U 3 dim_max ; ints: mk nm_max | mj nm_max.
+// kMask: `core` ([candidate][max_actions], the launch's first candidate first) marks the actions that are core poses; a non-core
+// step - an intermediate pose of a Dubins edge (Planner2D.cpp:659-682) - gets its pose and its odometry factor like every action,
+// and predicts no measurement.  kMask = false never reads `core`: every action is a core pose.
+template <bool kMask>
 __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const int32_t *cand_env, const int32_t *env_slot,
                                                    const double *actions, const int32_t *n_actions, const double *sig,
                                                    size_t sig_stride, double *scratch, size_t scratch_stride, int *iscratch,
-                                                   int nm_max, double *cov_out, int out_stride, int32_t *n_out) {
+                                                   int nm_max, double *cov_out, int out_stride, int32_t *n_out, const uint8_t *core) {
   __shared__ int nm_s, bad;
   __shared__ int wcount[kT / 64];
   __shared__ double gj[2 * 512];  // Gauss-Jordan row / column of T: dim = 2 nm <= 512
@@ -263,6 +267,7 @@ __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const i
   }
   // ---- predicted measurements (Planner2D.cpp:717-731): new pose b x estimated landmark j, in (b, j) order
   for (int b = 0; b < K; ++b) {
+    if (kMask && !core[(size_t)ci * S.A_max + b]) continue;  // (the same for every thread: no barrier is left out by some)
     const Pose ps{newp[4 * b], newp[4 * b + 1], newp[4 * b + 2], newp[4 * b + 3]};
     for (int j0 = 0; j0 < L; j0 += kT) {
       const int j = j0 + tid;
@@ -402,9 +407,11 @@ __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const i
 // What k_fm2_update can only report through the status word, found out BEFORE anything is launched that an entry's caller could
 // see: an environment that does not exist, a plan longer than max_actions, more predicted measurements than nm_max.  One thread
 // per candidate walks the same pose chain and the same gates (the expressions of k_fm2_update, in this translation unit: they
-// round alike); flag[0] = the smallest DRLGX_E_* code met (the caller zeroes it).
+// round alike); flag[0] = the smallest DRLGX_E_* code met (the caller zeroes it).  kMask: k_fm2_update's mask - only core poses
+// predict measurements, so only theirs count against nm_max; kMask = false never reads `core`.
+template <bool kMask>
 __global__ void k_fm2_check(DrlgxState S, int n_cand, const int32_t *cand_env, const double *actions, const int32_t *n_actions, int nm_max,
-                            int *flag) {
+                            int *flag, const uint8_t *core) {
   const int ci = blockIdx.x * blockDim.x + threadIdx.x;
   if (ci >= n_cand) return;
   const int env = cand_env[ci], K = n_actions[ci];
@@ -421,7 +428,8 @@ __global__ void k_fm2_check(DrlgxState S, int n_cand, const int32_t *cand_env, c
   for (int b = 0; b < K; ++b) {
     const double *a = actions + ((size_t)ci * S.A_max + b) * 3;
     const Pose ps = compose(origin, make_pose(a[0], a[1], a[2]));
-    for (int j = 0; j < L; ++j) {
+    const int Lb = kMask && !core[(size_t)ci * S.A_max + b] ? 0 : L;
+    for (int j = 0; j < Lb; ++j) {
       const P2 lm{el[2 * j], el[2 * j + 1]};
       const double dx = lm.x - ps.x, dy = lm.y - ps.y, rng = sqrt(dx * dx + dy * dy);
       const double bearing = bearing_of<false>(ps, lm, nullptr, nullptr);
@@ -435,8 +443,13 @@ __global__ void k_fm2_check(DrlgxState S, int n_cand, const int32_t *cand_env, c
 }  // namespace kfm2
 
 void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *actions,
-                            const int32_t *n_actions, int nm_max, int *flag) {
-  hipLaunchKernelGGL(kfm2::k_fm2_check, dim3((n_cand + 63) / 64), dim3(64), 0, st, S, n_cand, cand_env, actions, n_actions, nm_max, flag);
+                            const int32_t *n_actions, const uint8_t *core, int nm_max, int *flag) {
+  if (core)
+    hipLaunchKernelGGL(kfm2::k_fm2_check<true>, dim3((n_cand + 63) / 64), dim3(64), 0, st, S, n_cand, cand_env, actions, n_actions, nm_max,
+                       flag, core);
+  else
+    hipLaunchKernelGGL(kfm2::k_fm2_check<false>, dim3((n_cand + 63) / 64), dim3(64), 0, st, S, n_cand, cand_env, actions, n_actions, nm_max,
+                       flag, core);
 }
 void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, const int32_t *env_ids, int n_env, double *sig, size_t sig_stride,
                             int n_max) {
@@ -448,8 +461,13 @@ size_t drlgx_fm2_scratch_doubles(const DrlgxState &S, int nm_max) {
          (size_t)(kfm2::kT / 64) * 6 * nm_max + (size_t)4 * S.A_max + 64;
 }
 void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
-                             const double *actions, const int32_t *n_actions, const double *sig, size_t sig_stride, double *scratch,
-                             size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride, int32_t *n_out) {
-  hipLaunchKernelGGL(kfm2::k_fm2_update, dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig, sig_stride,
-                     scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out);
+                             const double *actions, const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride,
+                             double *scratch, size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride,
+                             int32_t *n_out) {
+  if (core)
+    hipLaunchKernelGGL(kfm2::k_fm2_update<true>, dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig,
+                       sig_stride, scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out, core);
+  else
+    hipLaunchKernelGGL(kfm2::k_fm2_update<false>, dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig,
+                       sig_stride, scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out, core);
 }

@@ -34,6 +34,7 @@ class Engine(object):
         self.h = C.c_void_p()
         self.sampler_parameter, self.sampler_obstacles = (0.5, 0.0, False), False  # (the engine's values after drlgx_create)
         self.dubins_parameter = None
+        self.dubins_leaf_scoring = False
         _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)), self.h)  # (NULL: the creation's error)
         r, c = C.c_int32(), C.c_int32()
         self.L.drlgx_vm_shape(self.h, C.byref(r), C.byref(c))
@@ -235,28 +236,49 @@ class Engine(object):
                      ("occupancy_threshold", occupancy_threshold), ("max_edge_length", max_edge_length), ("algorithm", int(algorithm))):
             setattr(self.cfg, k, v)
 
-    def fm2_update(self, cand_env, actions, n_actions):
+    def _core_mask(self, core, n):
+        if core.dtype != torch.uint8 or tuple(core.shape) != (n, self.cfg.max_actions) or not core.is_contiguous():
+            raise ValueError("core: a contiguous uint8 tensor [C, max_actions] expected")
+        return core
+
+    def fm2_update(self, cand_env, actions, n_actions, core=None):
         """FastMarginals2-style covariance look-ahead (drlgx_fm2_update): returns (cov [C, max_poses + max_actions, 3, 3]
-        float64, n_poses [C] int32); rows beyond n_poses[c] are undefined."""
+        float64, n_poses [C] int32); rows beyond n_poses[c] are undefined.  `core` (uint8 [C, max_actions] on the device, or None =
+        every action): the actions that are core poses - a non-core step extends the chain and predicts no measurement
+        (drlgx_fm2_update_steps)."""
         self.use_torch_stream()
         n = cand_env.numel()
         stride = self.cfg.max_poses + self.cfg.max_actions
         cov = torch.zeros(n, stride, 3, 3, dtype=torch.float64, device=self.device)
         n_out = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self._chk(self.L.drlgx_fm2_update(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(cov), stride, _p(n_out)))
+        if core is None:
+            self._chk(self.L.drlgx_fm2_update(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(cov), stride, _p(n_out)))
+        else:
+            self._chk(self.L.drlgx_fm2_update_steps(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(self._core_mask(core, n)),
+                                                    _p(cov), stride, _p(n_out)))
         return cov, n_out
 
-    def em_cost(self, cand_env, actions, n_actions, algorithm=0, want_info=False):
+    def em_cost(self, cand_env, actions, n_actions, algorithm=0, want_info=False, core=None, distance=None):
         """Expected look-ahead cost of candidate plans (drlgx_em_cost: the leaf evaluation of EMPlanner2D::optimize2, without
         simulating or re-solving): returns (uncertainty [C], cost [C]) float64 and, with `want_info`, the leaf virtual map's
         information [C, rows, cols, 3] (xx, xy, yy).  cand_env [C] i32, actions [C, max_actions, 3] f64, n_actions [C] i32 on the
-        device; algorithm 0 = EM_AOPT, 1 = EM_DOPT."""
+        device; algorithm 0 = EM_AOPT, 1 = EM_DOPT.  `core` (uint8 [C, max_actions]) / `distance` (f64 [C]), device tensors or
+        None: the leaves of a tree with non-core steps (drlgx_em_cost_steps) - only core poses predict measurements and enter the
+        leaf's map, the cost takes `distance` instead of the plan's own."""
         self.use_torch_stream()
         n = cand_env.numel()
         unc = torch.empty(n, dtype=torch.float64, device=self.device)
         cost = torch.empty(n, dtype=torch.float64, device=self.device)
         info = torch.empty(n, self.rows, self.cols, 3, dtype=torch.float64, device=self.device) if want_info else None
-        self._chk(self.L.drlgx_em_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), int(algorithm), _p(unc), _p(cost), _p(info)))
+        if core is None and distance is None:
+            self._chk(self.L.drlgx_em_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), int(algorithm), _p(unc), _p(cost), _p(info)))
+        else:
+            if core is not None:
+                core = self._core_mask(core, n)
+            if distance is not None and (distance.dtype != torch.float64 or distance.numel() != n or not distance.is_contiguous()):
+                raise ValueError("distance: a contiguous float64 tensor [C] expected")
+            self._chk(self.L.drlgx_em_cost_steps(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(core), _p(distance),
+                                                 int(algorithm), _p(unc), _p(cost), _p(info)))
         return (unc, cost, info) if want_info else (unc, cost)
 
     def og_cost(self, cand_env, actions, n_actions, want_prob=False):
@@ -276,7 +298,7 @@ class Engine(object):
         """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
         control model is stored and then refused by em_plan / rrt_plan (a safe_distance >= 0 is served once
         set_sampler_obstacles(True) has opted in; the Dubins control model is served by rrt_plan once set_dubins_library has loaded
-        a library).  The values last set are kept in `sampler_parameter`."""
+        a library, and by em_plan once set_dubins_leaf_scoring(True) has opted in as well).  The values last set are kept in `sampler_parameter`."""
         self._chk(self.L.drlgx_set_sampler_parameter(self.h, float(max_nodes), float(safe_distance), int(bool(dubins_control_model_enabled))))
         self.sampler_parameter = (float(max_nodes), float(safe_distance), bool(dubins_control_model_enabled))
 
@@ -288,6 +310,31 @@ class Engine(object):
         self._chk(self.L.drlgx_set_sampler_obstacles(self.h, int(bool(enabled))))
         self.sampler_obstacles = bool(enabled)
 
+    def set_dubins_leaf_scoring(self, enabled):
+        """em_plan under the Dubins control model (drlgx_set_dubins_leaf_scoring), an opt-in that is off after construction: with
+        it, a library loaded and the sampler's Dubins flag set, em_plan grows the Dubins tree with optimize2's stop rule and scores
+        every leaf with its non-core steps (one plan row per step, the core mask 1 at each edge's last step, the tree's distance).
+        Off, em_plan under the Dubins flag is refused as before.  The setting is kept in `dubins_leaf_scoring`."""
+        self._chk(self.L.drlgx_set_dubins_leaf_scoring(self.h, int(bool(enabled))))
+        self.dubins_leaf_scoring = bool(enabled)
+
+    def em_plan_leaves(self):
+        """The leaves the last served em_plan scored (drlgx_em_plan_leaves), in candidate order: a dict of device tensors cand_env
+        [C] i32, actions [C, max_actions, 3] f64, n_actions [C] i32, core [C, max_actions] u8, cost [C] f64 and, when that call ran
+        the Dubins control model (whatever the sampler's flag says now), distance [C] f64 (else None)."""
+        self.use_torch_stream()
+        n, steps = C.c_int32(0), C.c_int32(0)
+        self._chk(self.L.drlgx_em_plan_leaves(self.h, 0, C.byref(n), C.byref(steps), None, None, None, None, None, None))
+        c, A, dev = int(n.value), self.cfg.max_actions, self.device
+        o = dict(cand_env=torch.empty(c, dtype=torch.int32, device=dev), actions=torch.empty(c, A, 3, dtype=torch.float64, device=dev),
+                 n_actions=torch.empty(c, dtype=torch.int32, device=dev), core=torch.empty(c, A, dtype=torch.uint8, device=dev),
+                 cost=torch.empty(c, dtype=torch.float64, device=dev), distance=None)
+        if steps.value:
+            o["distance"] = torch.empty(c, dtype=torch.float64, device=dev)
+        self._chk(self.L.drlgx_em_plan_leaves(self.h, c, C.byref(n), None, _p(o["cand_env"]), _p(o["actions"]), _p(o["n_actions"]), _p(o["core"]),
+                                              _p(o["distance"]), _p(o["cost"])))
+        return o
+
     DUBINS_FIELDS = ("max_w", "dw", "min_v", "max_v", "dv", "dt", "min_duration", "max_duration", "tolerance_radius")
 
     def set_dubins_library(self, parameter):
@@ -295,7 +342,7 @@ class Engine(object):
         is a planner2d.DubinsParameter (or any object / sequence with its nine fields in DUBINS_FIELDS order); None clears the
         library.  The engine builds the library with the reference's loops; with one loaded and the Dubins flag of
         set_sampler_parameter set, rrt_plan is served (one plan row per step, nodes columns 5-7 = library index, num_steps, 0);
-        em_plan stays refused.  Raises DrlgxError for parameters the engine refuses.  Returns the library's size."""
+        em_plan stays refused unless set_dubins_leaf_scoring(True) has opted in.  Raises DrlgxError for parameters the engine refuses.  Returns the library's size."""
         self.dubins_parameter = None  # (the nine values of the library loaded last, for callers that would load it again)
         if parameter is None:
             self._chk(self.L.drlgx_set_dubins_library_host(self.h, None))
@@ -346,7 +393,10 @@ class Engine(object):
         taken.  env_sel, halton_start [n] i32 on the device.  Returns a dict of device tensors: plan [n, max_actions, 3] f64 (edge
         odometry root -> leaf), n_actions, result (OptimizationResult), n_leaves, halton_next, n_nodes [n] i32, cost [n] f64 and,
         with `want_nodes`, nodes [n, max_tree_nodes, 8] f64 (x y theta parent distance | edge odometry x y theta).  Raises
-        DrlgxError on a refusal (capacity: a tree beyond max_tree_nodes or deeper than cfg.max_actions)."""
+        DrlgxError on a refusal (capacity: a tree beyond max_tree_nodes or deeper than cfg.max_actions).  Under the Dubins control
+        model (set_dubins_library, the sampler's Dubins flag and set_dubins_leaf_scoring(True)) the plan has one row per step, nodes
+        columns 5-7 are (library index, num_steps, 0), and a tree can end with SAMPLING_FAILURE; em_plan_leaves() reads back what was
+        scored."""
         self.use_torch_stream()
         n = env_sel.numel()
         o = self._tree_outputs(n, max_tree_nodes, want_nodes)

@@ -103,18 +103,23 @@ class EMPlanner2D(object):
     call.  With the attribute `dubins_paths` set (an opt-in for the same reason) and `dubins_control_model_enabled`, `set_parameter`
     loads `parameter.dubins_parameter` as the engine's Dubins library and `rrt_planner` runs the Dubins control model: an edge's
     `get_odoms()` is then one odometry per step, a node's `poses` the step poses; `get_dubins_path(i)` / `iter_dubins_library()`
-    read the library; `optimize2` raises.  `optimize` and `iter_rrt` are outside the accelerated path."""
+    read the library; `optimize2` raises - unless the attribute `dubins_leaf_scoring` is set as well (an opt-in again:
+    Engine.set_dubins_leaf_scoring): `optimize2` then grows the Dubins tree and scores every leaf with its non-core steps, and
+    `iter_solution` yields the best leaf's edges, one odometry per step.  `optimize` and `iter_rrt` are outside the accelerated path."""
     MAX_TREE_NODES = 2048  # the node capacity of one tree (the engine's maximum)
     OptimizationAlgorithm = OptimizationAlgorithm
     OptimizationResult = OptimizationResult
     obstacle_logic = False  # True: the sampler's obstacle logic (Engine.set_sampler_obstacles) - a non-zero safe_distance is served
     dubins_paths = False    # True: the Dubins control model (Engine.set_dubins_library) - rrt_planner serves dubins_control_model_enabled
+    dubins_leaf_scoring = False  # True (with dubins_paths): optimize2 serves it too (Engine.set_dubins_leaf_scoring)
 
-    def __init__(self, parameter, sensor_model, control_model, obstacle_logic=False, dubins_paths=False):
+    def __init__(self, parameter, sensor_model, control_model, obstacle_logic=False, dubins_paths=False, dubins_leaf_scoring=False):
         if obstacle_logic:
             self.obstacle_logic = True
         if dubins_paths:
             self.dubins_paths = True
+        if dubins_leaf_scoring:
+            self.dubins_leaf_scoring = True
         self._ses = sensor_model._session
         if self._ses is None or control_model._session is not self._ses:
             raise ValueError("the sensor and control models must come from one Simulator2D")
@@ -133,6 +138,7 @@ class EMPlanner2D(object):
                                                    parameter.occupancy_threshold, parameter.max_edge_length, int(parameter.algorithm))
             self._ses.engine.set_sampler_parameter(parameter.max_nodes, parameter.safe_distance, parameter.dubins_control_model_enabled)
             self._ses.engine.set_sampler_obstacles(self.obstacle_logic)
+            self._ses.engine.set_dubins_leaf_scoring(self.dubins_paths and self.dubins_leaf_scoring)
             if self.dubins_paths and parameter.dubins_control_model_enabled:
                 load_dubins_library(self._ses.engine, parameter.dubins_parameter)
 
@@ -219,7 +225,7 @@ class EMPlanner2D(object):
         """One sampler call for the wrapped simulation: the parameter object as it is now, the Halton index carried on, the best
         path kept for iter_solution."""
         import torch
-        _require_sampler_scope(self._parameter, self.obstacle_logic, self.dubins_paths and rrt)
+        _require_sampler_scope(self._parameter, self.obstacle_logic, self.dubins_paths and (rrt or self.dubins_leaf_scoring))
         e = self._ses.require_engine()
         self.set_parameter(self._parameter)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
@@ -228,7 +234,8 @@ class EMPlanner2D(object):
         e.check_status()
         plan, n_act, result, nxt, nodes, n_nodes = e.fetch(o["plan"], o["n_actions"], o["result"], o["halton_next"], o["nodes"], o["n_nodes"])
         self.halton_next = int(nxt[0])
-        self._solution = solution_edges(e, self._parameter, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        last = None if rrt else best_leaf_node(e, self._parameter, o, nodes[0, :int(n_nodes[0])])
+        self._solution = solution_edges(e, self._parameter, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])], last)
         return OptimizationResult(int(result[0]))
 
     def optimize2(self, slam, virtual_map):
@@ -291,10 +298,10 @@ def _require_sampler_scope(parameter, obstacle_logic=False, dubins_rrt=False):
     """The sampler serves the non-Dubins control model at safe_distance = 0 (the engine refuses anything else with
     DRLGX_E_INVALID); the facades say so the way they say it for everything outside the accelerated path.  With `obstacle_logic`
     (the opt-in) any safe_distance >= 0 passes; the Dubins control model raises unless `dubins_rrt`: the caller is rrt_planner and
-    has opted in to Dubins paths."""
+    has opted in to Dubins paths - or optimize2 and has opted in to the Dubins leaf scoring as well."""
     if parameter.dubins_control_model_enabled and not dubins_rrt:
-        raise NotImplementedError("the tree sampler runs the Dubins control model for rrt_planner only, behind the opt-in "
-                                  "dubins_paths=True (optimize2 under Dubins paths is outside the accelerated path)")
+        raise NotImplementedError("the tree sampler runs the Dubins control model for rrt_planner behind the opt-in "
+                                  "dubins_paths=True, and for optimize2 behind dubins_paths=True with dubins_leaf_scoring=True")
     if obstacle_logic:
         if parameter.safe_distance < 0:
             raise ValueError("safe_distance must not be negative")
@@ -324,24 +331,39 @@ class Edge(object):
         return list(self._odoms)
 
 
-def solution_edges(engine, parameter, plan, nodes):
-    """The best path's edges, leaf first, for the control model of `parameter`."""
+def solution_edges(engine, parameter, plan, nodes, last=None):
+    """The best path's edges, leaf first, for the control model of `parameter`; last: the path's last node under the Dubins model
+    (None: the tree's last node, rrt_planner's goal)."""
     if parameter.dubins_control_model_enabled:
-        return _dubins_solution_edges(engine, parameter, plan, nodes)
+        return _dubins_solution_edges(engine, parameter, plan, nodes, last)
     return _solution_edges(engine, plan, nodes)
 
 
-def _dubins_solution_edges(engine, parameter, plan, nodes):
-    """rrt_planner under the Dubins model: the goal node is the last node of the tree when there is a plan; a node's columns 5-7
-    are (library index, num_steps, 0) and the plan holds one row per step, root -> goal.  A node's poses are its steps from the
-    parent's pose (connectNodeDubinsPath, Planner2D.cpp:157-176)."""
+def best_leaf_node(engine, parameter, out, nodes):
+    """optimize2 under the Dubins model, one tree: the node of the leaf em_plan picked - the leaves are the childless nodes in node
+    order, and the picked one is the first whose per-step rows are the plan's, bit for bit.  None for the other control model (the
+    plan's rows are the nodes' own columns there) and for an empty plan."""
+    if not parameter.dubins_control_model_enabled or int(out["n_actions"][0]) == 0:
+        return None
+    lv = engine.em_plan_leaves()
+    same = ((lv["actions"] == out["plan"][0]).flatten(1).all(dim=1) & (lv["n_actions"] == out["n_actions"][0])).nonzero().flatten()
+    if same.numel() == 0:
+        raise RuntimeError("the plan is not a leaf of the returned tree")
+    parents = set(int(p) for p in nodes[1:, 3])
+    return [j for j in range(len(nodes)) if j not in parents][int(same[0])]
+
+
+def _dubins_solution_edges(engine, parameter, plan, nodes, last=None):
+    """The Dubins model: the path ends at node `last` - rrt_planner's goal node is the last node of the tree when there is a plan;
+    a node's columns 5-7 are (library index, num_steps, 0) and the plan holds one row per step, root -> `last`.  A node's poses
+    are its steps from the parent's pose (connectNodeDubinsPath, Planner2D.cpp:157-176)."""
     from . import ss2d
     if len(plan) == 0:
         return []
     lib = engine.dubins_library()
     dt = float(parameter.dubins_parameter.dt)
     root_key = engine.counts(0)["poses"] - 1
-    path = [len(nodes) - 1]
+    path = [len(nodes) - 1 if last is None else int(last)]
     while path[-1] > 0:
         path.append(int(nodes[path[-1], 3]))
     path.reverse()  # root .. goal

@@ -274,10 +274,11 @@ class _Planner(object):
 
     def _call(self, run, rrt=False):
         o, pp = self._o, self._o._planner_params
-        planner2d._require_sampler_scope(pp, o.obstacle_logic, o.dubins_paths and rrt)
+        planner2d._require_sampler_scope(pp, o.obstacle_logic, o.dubins_paths and (rrt or o.dubins_leaf_scoring))
         e = o.engine
         e.set_sampler_parameter(pp.max_nodes, pp.safe_distance, pp.dubins_control_model_enabled)
         e.set_sampler_obstacles(o.obstacle_logic)
+        e.set_dubins_leaf_scoring(o.dubins_paths and o.dubins_leaf_scoring)
         if o.dubins_paths and pp.dubins_control_model_enabled:
             planner2d.load_dubins_library(e, pp.dubins_parameter)
         sel = torch.zeros(1, dtype=torch.int32, device=e.device)
@@ -286,7 +287,8 @@ class _Planner(object):
         plan, n_act, result, nxt, nodes, n_nodes = e.fetch(out["plan"], out["n_actions"], out["result"], out["halton_next"], out["nodes"],
                                                            out["n_nodes"])
         self.halton_next = int(nxt[0])
-        self._solution = planner2d.solution_edges(e, pp, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])])
+        last = None if rrt else planner2d.best_leaf_node(e, pp, out, nodes[0, :int(n_nodes[0])])
+        self._solution = planner2d.solution_edges(e, pp, plan[0, :int(n_act[0])], nodes[0, :int(n_nodes[0])], last)
         self.last = out
         return planner2d.OptimizationResult(int(result[0]))
 
@@ -321,12 +323,15 @@ class EMExplorer(SS2D):
     safe_distance as the ini file gives it, with the sampler's obstacle logic (Engine.set_sampler_obstacles); off, a non-zero
     planner safe_distance raises NotImplementedError as before.  `dubins_paths` (an opt-in too): with `[Planner]
     dubins_control_model_enabled = true` rrt_plan() runs the Dubins control model with the ini file's [Dubins] library
-    (Engine.set_dubins_library), an edge's get_odoms() then holds one odometry per step; plan() raises; off, the flag raises
-    NotImplementedError as before.  Executing the intermediate steps (simulate(core=False)) stays outside the accelerated path."""
+    (Engine.set_dubins_library), an edge's get_odoms() then holds one odometry per step; plan() raises unless
+    `dubins_leaf_scoring` (one more opt-in, Engine.set_dubins_leaf_scoring) is set as well: plan() then runs optimize2 with the
+    Dubins tree and the leaf evaluation that knows non-core steps, and iter_solution() yields the best leaf's edges, one odometry
+    per step; off, the flag raises NotImplementedError as before.  Executing the intermediate steps (simulate(core=False)) stays outside the accelerated path."""
 
     def __init__(self, *args, **kwargs):
         self.obstacle_logic = bool(kwargs.pop("obstacle_logic", False))
         self.dubins_paths = bool(kwargs.pop("dubins_paths", False))
+        self.dubins_leaf_scoring = bool(kwargs.pop("dubins_leaf_scoring", False))
         super(EMExplorer, self).__init__(*args, **kwargs)
         self._planner = _Planner(self)
 

@@ -204,16 +204,42 @@ class VecExplorationEnv(object):
             e.set_sampler_parameter(*old_par)
             e.set_sampler_obstacles(old_obs)
 
-    def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0, safe_distance=None):
+    def _with_dubins(self, dubins, leaf_scoring, run):
+        """`run` under the Dubins control model with the library of `dubins` (Engine.set_dubins_library, kept loaded for the next
+        such call) and - leaf_scoring - the opt-in of em_plan; the engine's Dubins flag and that opt-in come back after it."""
+        from .planner2d import load_dubins_library
+
+        def wrapped():
+            e = self.engine
+            load_dubins_library(e, dubins)
+            now, old_ls = e.sampler_parameter, e.dubins_leaf_scoring
+            e.set_sampler_parameter(now[0], now[1], True)
+            if leaf_scoring:
+                e.set_dubins_leaf_scoring(True)
+            try:
+                return run()
+            finally:
+                e.set_sampler_parameter(*now)
+                if leaf_scoring:
+                    e.set_dubins_leaf_scoring(old_ls)
+        return wrapped
+
+    def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0, safe_distance=None, dubins=None):
         """ExplorationEnv.plan for all envs in one call (EMPlanner2D::optimize2, Engine.em_plan): per env the tree, the leaves' expected
         costs with the configured algorithm, the best leaf's action list.  Returns (actions [n_envs, max_actions, 3] f64 edge
         odometry, n_actions [n_envs] i32, result [n_envs] i32) on the device; every env's Halton index carries on from call to
         call.  `safe_distance` (None: 0, as before): a value runs this call with the sampler's obstacle logic at that planner
-        safe_distance (an env can then have result SAMPLING_FAILURE and no actions) and restores the engine's sampler settings."""
+        safe_distance (an env can then have result SAMPLING_FAILURE and no actions) and restores the engine's sampler settings.
+        `dubins` (a planner2d.DubinsParameter; None: the non-Dubins control model as before): this call runs optimize2 under the
+        Dubins control model with that library - it sets the library, the Dubins flag and the opt-in of the Dubins leaf scoring
+        (Engine.set_dubins_leaf_scoring), the actions are then one odometry per step, an env can have result SAMPLING_FAILURE -
+        and the engine's Dubins flag and opt-in come back after it."""
         sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
         start = self._halton(planner_seed)
-        o = self._with_safe_distance(max_nodes, safe_distance,
-                                     lambda: self.engine.em_plan(sel, start, max_tree_nodes, int(self.cfg.algorithm)))
+        run = lambda: self.engine.em_plan(sel, start, max_tree_nodes, int(self.cfg.algorithm))
+        if dubins is not None:
+            run = self._with_dubins(dubins, True, run)
+        o = self._with_safe_distance(max_nodes, safe_distance, run)
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]
 
@@ -230,18 +256,7 @@ class VecExplorationEnv(object):
         run = lambda: self.engine.rrt_plan(sel, goal_key.to(torch.int32).contiguous(), frontier.to(torch.float64).contiguous(), start,
                                            max_tree_nodes)
         if dubins is not None:
-            from .planner2d import load_dubins_library
-            plain = run
-
-            def run():
-                e = self.engine
-                load_dubins_library(e, dubins)
-                now = e.sampler_parameter
-                e.set_sampler_parameter(now[0], now[1], True)
-                try:
-                    return plain()
-                finally:
-                    e.set_sampler_parameter(*now)
+            run = self._with_dubins(dubins, False, run)
         o = self._with_safe_distance(None, safe_distance, run)
         self._halton_next = o["halton_next"]
         return o["plan"], o["n_actions"], o["result"]

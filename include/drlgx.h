@@ -177,6 +177,16 @@ int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebui
  * measurements per candidate (DRLGX_E_CAPACITY beyond). */
 int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                      double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev);
+/* drlgx_fm2_update for action lists with NON-CORE steps, as the edges of the Dubins control model have them (Planner2D.cpp:659-682,
+ * :714-731): core_dev uint8[n_cand*max_actions] marks the actions that are core poses; NULL = every action, and the call is then
+ * drlgx_fm2_update (the same kernel, the same bits).  Every action still appends its predicted pose and its odometry factor - the
+ * chain of covariances runs through every step -, but only a core pose predicts measurements, so the 256-measurement capacity
+ * applies to the masked count.  cov_out_dev holds one 3x3 block per pose as before, the P old poses and EVERY step, each with the
+ * full update Sigma' applied (the reference's FastMarginals2::update corrects the blocks of `updated_keys` only - the old poses and
+ * each edge's last pose - and leaves the intermediate steps at their propagated covariance, which nothing reads; for those steps
+ * this entry returns the posterior marginal instead).  Any mask is legal, trailing non-core steps included. */
+int drlgx_fm2_update_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                           const uint8_t *core_dev, double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev);
 /* The leaf evaluation of EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1095-1104) for n_cand candidates (environment,
  * action list) the caller supplies (drlgx_em_plan below grows optimize2's tree and feeds its leaves to this entry's body):
  *   updateTrajectory_EM (:472-551): the covariances of drlgx_fm2_update; every pose becomes a core pose of the leaf's map with
@@ -199,6 +209,21 @@ int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, c
  * alone. */
 int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                   int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev);
+/* drlgx_em_cost for the leaves of a tree whose edges have NON-CORE steps (the Dubins control model: updateNodeInformation_EM,
+ * Planner2D.cpp:659-682, adds one odometry factor and one pose per step, predicts measurements at the edge's last pose only, :714-731,
+ * and updateTrajectory_EM puts only that last pose into the leaf's map, :498, :514-524):
+ *   core_dev uint8[n_cand*max_actions] or NULL (= every action is a core pose): the covariances are those of
+ *     drlgx_fm2_update_steps; the leaf's map holds the P old poses and the CORE new poses only - a non-core step is marked skipped
+ *     before its information is factored, so it can never raise DRLGX_E_NUMERIC -, while the pose chain still composes every row;
+ *   distance_dev double[n_cand] or NULL: the leaf's distance as the tree accumulated it (v dt n + |w dt n| angle_weight per edge,
+ *     :293-303), used in the cost instead of sum_k sqrt(x_k^2 + y_k^2 + angle_weight theta_k^2).
+ * With both NULL the call is drlgx_em_cost: the same kernels, the same bits.  Everything else - the other arguments, the checks
+ * before anything is launched (the 256-measurement capacity counts the predicted measurements of core poses only), the single
+ * synchronisation, a refused call leaving live state and the status word alone - is drlgx_em_cost's.  Any mask is legal, trailing
+ * non-core steps included. */
+int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                        const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev,
+                        double *cost_out_dev, double *info_out_dev);
 
 /* calculateUncertainty_OG_SHANNON (src/em_exploration/Planner2D.cpp:368-392) and costFunction (:418-420) for n_cand candidates
  * (environment, action list) the caller supplies - the Shannon entropy of the occupancy map after the plan's poses have swept it:
@@ -224,7 +249,8 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
  * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
  * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
  * drlgx_em_plan / drlgx_rrt_plan (a safe_distance > 0 is served once drlgx_set_sampler_obstacles, below, has opted in; the Dubins
- * control model is served by drlgx_rrt_plan once drlgx_set_dubins_library_host, below, has loaded a library).  After
+ * control model is served by drlgx_rrt_plan once drlgx_set_dubins_library_host, below, has loaded a library, and by drlgx_em_plan
+ * once drlgx_set_dubins_leaf_scoring has opted in as well).  After
  * drlgx_create: max_nodes 0.5, safe_distance 0, Dubins off. */
 int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_distance, int dubins_control_model_enabled);
 /* The sampler's obstacle logic, an OPT-IN (default 0: every call behaves as described above and below, a non-zero safe_distance is
@@ -253,7 +279,8 @@ int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_d
  * A tree that ends with SAMPLING_FAILURE reports result 0, n_actions 0, no leaves, the nodes accepted so far in n_nodes / nodes_out,
  * and in halton_next the index after the last drawn point; the other trees of the call are not concerned, it offers no candidate to
  * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  optimize (RRT*) and
- * SLAM_OG_SHANNON stay out of scope; Dubins paths are served for drlgx_rrt_plan only (below). */
+ * SLAM_OG_SHANNON stay out of scope; Dubins paths are served for drlgx_rrt_plan, and for drlgx_em_plan behind
+ * drlgx_set_dubins_leaf_scoring (below). */
 int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled);
 /* The Dubins control model's path library (EMPlanner2D::initializeDubinsPathLibrary, Planner2D.cpp:1359-1414), and with it the
  * OPT-IN of that control model: with no library loaded the Dubins flag of drlgx_set_sampler_parameter is refused as before.
@@ -268,8 +295,9 @@ int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled);
  * entry.  DRLGX_E_CAPACITY: more than 131 072 entries (the shipped [Dubins] section gives 78 030), a path of more than 4 096
  * steps, or more than 2^20 (v, w) pairs; the library loaded before is then kept.
  * With a library loaded and the Dubins flag set, drlgx_rrt_plan is served at safe_distance = 0, or >= 0 under
- * drlgx_set_sampler_obstacles; drlgx_em_plan still returns DRLGX_E_INVALID (its leaf scoring treats every action as a core pose
- * with measurements, the reference's Dubins edges have non-core steps).  What changes in the tree (Planner2D.cpp):
+ * drlgx_set_sampler_obstacles; drlgx_em_plan still returns DRLGX_E_INVALID unless drlgx_set_dubins_leaf_scoring, below, has opted
+ * in (the reference's Dubins edges have non-core steps, which only drlgx_em_cost_steps scores).  What changes in the tree
+ * (Planner2D.cpp):
  *   sampleNode (:41-45, :110-115): the same x, y (Halton bases 2 and 3); the sample's theta is 0 and is not read;
  *   connectNodeDubinsPath (:157-176): local = the sample in the parent's frame; the FIRST entry in library order with
  *     |local - end_i| < tolerance_radius (strict) wins; the node's poses are num_steps Euler steps of that (v, w) from the parent's
@@ -295,6 +323,29 @@ int drlgx_dubins_library(drlgx_engine *e, int capacity, int32_t *n_out, double *
  * (the largest |end_i| + tolerance_radius)(1 + 2^-30) cannot match any entry (triangle inequality), so the scan is skipped.
  * enabled = 0 scans every time; the results are identical (tests compare them). */
 int drlgx_set_dubins_prefilter(drlgx_engine *e, int enabled);
+/* drlgx_em_plan under the Dubins control model, an OPT-IN (default 0: drlgx_em_plan with the Dubins flag set returns
+ * DRLGX_E_INVALID as before).  With enabled != 0, a library loaded and the Dubins flag set, drlgx_em_plan is served at
+ * safe_distance = 0, or >= 0 under drlgx_set_sampler_obstacles; with enabled != 0 and NO library it returns DRLGX_E_INVALID and
+ * touches nothing.  The tree is the Dubins tree described at drlgx_set_dubins_library_host with optimize2's stop rule (max_nodes_
+ * accepted nodes; the connect counter of 1000 runs at safe_distance = 0 too, so a tree can end with SAMPLING_FAILURE) and
+ * optimize2's shrink (max(0, distance - 0.1), Planner2D.cpp:1046-1054).  Every leaf, in node order, becomes a candidate of
+ * drlgx_em_cost_steps: one row per STEP root -> leaf (between(previous pose, this pose)), the core mask 1 at each edge's last step,
+ * and the leaf's tree distance; the pick is drlgx_em_plan's.  plan_out_dev / n_actions_out_dev then hold the best leaf's per-step
+ * rows; nodes_out columns 5-7 are (library index, num_steps, 0).  A leaf of more steps than max_actions refuses the whole call
+ * with DRLGX_E_CAPACITY before anything is written.  Executing non-core steps (simulate(core = false)) and optimize (RRT*) stay
+ * out of scope. */
+int drlgx_set_dubins_leaf_scoring(drlgx_engine *e, int enabled);
+/* The leaves the last served drlgx_em_plan handed to its scoring, in candidate order (tree by tree, each tree's leaves in node
+ * order): *n_out_host = their number, *has_steps_out_host (may be NULL) = 1 if that call ran the Dubins control model - whatever the
+ * sampler's flag says now -, else 0; up to `capacity` of them are copied on the engine's stream into the DEVICE arrays (each may
+ * be NULL) cand_env int32[.], actions double[.*max_actions*3], n_actions int32[.], core uint8[.*max_actions] (all ones without the
+ * Dubins control model), distance double[.] (only after a call with steps: otherwise DRLGX_E_INVALID before anything is written -
+ * the cost then took the plan's own distance), cost double[.].  Part of the facade path: under the Dubins control model the plan's
+ * rows are per-step odometries, not node columns, and EMPlanner2D / EMExplorer find the picked leaf's node for iter_solution() by
+ * comparing the plan with these rows; feeding the leaves to drlgx_em_cost_steps reproduces the costs bit for bit (the tests do). */
+int drlgx_em_plan_leaves(drlgx_engine *e, int capacity, int32_t *n_out_host, int32_t *has_steps_out_host, int32_t *cand_env_out_dev,
+                         double *actions_out_dev, int32_t *n_actions_out_dev, uint8_t *core_out_dev, double *distance_out_dev,
+                         double *cost_out_dev);
 /* EMPlanner2D::optimize2 (src/em_exploration/Planner2D.cpp:1043-1128) for the n_sel environments env_sel_dev names: per environment
  * one tree grown on the device from its live belief (k_em_tree.hip) -
  *   initialize (:1281-1357): root = the current pose estimate; max_nodes_ = floor(#{p_v < occupancy_threshold} * max_nodes);
@@ -319,7 +370,7 @@ int drlgx_set_dubins_prefilter(drlgx_engine *e, int enabled);
  * n_nodes_out_dev int32[n_sel] or NULL.  max_tree_nodes: the node capacity of one tree (root included), 1 .. 2048; every device
  * loop is bounded by it.
  * DRLGX_E_INVALID: a bad argument or algorithm, an environment that does not exist, a non-zero safe_distance or the Dubins control
- * model (drlgx_set_sampler_parameter).  DRLGX_E_CAPACITY: a tree needs more than max_tree_nodes nodes, a tree is deeper than
+ * model (drlgx_set_sampler_parameter; the opt-ins drlgx_set_sampler_obstacles and drlgx_set_dubins_leaf_scoring serve them).  DRLGX_E_CAPACITY: a tree needs more than max_tree_nodes nodes, a tree is deeper than
  * max_actions, or a leaf is refused by drlgx_em_cost (more than 256 predicted measurements); the outputs are then unspecified,
  * live state and the status word are untouched, and the remedy is a larger max_tree_nodes or an engine created with a larger
  * max_actions.  The call synchronises twice: once to read the leaf counts and the capacity flag, once in drlgx_em_cost's check. */

@@ -12,6 +12,17 @@ with bench.py's script to 36 poses):
       of the winner's stride of 64).  A tree whose connect counter fires (1001 refused in a row) ends early: trees_failed.
 
     python scripts/micro/em_plan_dubins.py [--repeats 5] [--envs 256] [--no-dubins] >> profiles/em_plan_dubins.txt
+
+--optimize2: what one EM-baseline decision costs under the Dubins control model instead (Engine.em_plan behind
+set_dubins_leaf_scoring: the Dubins tree with optimize2's stop rule, every leaf scored with its non-core steps, the pick), per
+library: HIP events around the whole call, and around Engine.em_cost(core, distance) on the leaves read back - the share of the
+scoring (argument check, prior, covariance update, k_em_cost); the rest is tree + leaves + pick.  The engine of this mode has
+max_actions = 128 (a plan has one row per STEP, up to 20 per edge with the shipped library), and max_nodes starts at
+--optimize2-max-nodes and is halved while a leaf deeper than that refuses the call.  The per-kernel split (k_em_tree /
+k_em_leaves_dubins / k_fm2_check, k_fm2_prior, k_fm2_update, k_em_cost / k_em_pick) comes from a kernel trace of a run of its own
+(rocprofv3 --kernel-trace --stats -- python scripts/micro/em_plan_dubins.py --optimize2 --repeats 1).
+
+    python scripts/micro/em_plan_dubins.py --optimize2 [--repeats 5] [--envs 256] >> profiles/em_plan_dubins_optimize2.txt
 """
 import argparse
 import json
@@ -48,6 +59,51 @@ def timed(fn, repeats):
     return out
 
 
+def optimize2(args):
+    from drl_graph_exploration_amd._lib import DrlgxError
+    n = args.envs
+    cfg = default_config(MAP, num_landmarks=NUM_LM, max_poses=41, max_actions=128)
+    eng = Engine(cfg, n, 0)
+    from oracle import oracle as O
+    starts = np.array([O.start_pose(lo, MAP / 2 + 20) for lo in range(n)]) + np.array([0.3183, -0.2718, 0.1234])
+    eng.reset(np.arange(n), np.arange(n), starts=starts)
+    for act in WARM_SCRIPT:
+        eng.step(torch.tensor([act] * n, dtype=torch.float64, device=eng.device))
+    eng.check_status()
+    dev = eng.device
+    sel = torch.arange(n, dtype=torch.int32, device=dev)
+    h0 = halton_start_index(0)
+    start = torch.full((n,), h0, dtype=torch.int32, device=dev)
+    eng.set_dubins_leaf_scoring(True)
+    rows = []
+    for name, params in LIBRARIES.items():
+        size = eng.set_dubins_library(params)
+        max_nodes, refused, o = args.optimize2_max_nodes, 0, None
+        while o is None:
+            eng.set_sampler_parameter(max_nodes, dubins_control_model_enabled=True)
+            try:
+                o = eng.em_plan(sel, start, 2048, int(cfg.algorithm))  # (and the warm-up of this setting)
+            except DrlgxError:
+                refused, max_nodes = refused + 1, max_nodes / 2
+        n_nodes, n_leaves, n_act, res, nxt = (o[k].cpu().numpy() for k in ("n_nodes", "n_leaves", "n_actions", "result", "halton_next"))
+        lv = eng.em_plan_leaves()
+        whole = timed(lambda: eng.em_plan(sel, start, 2048, int(cfg.algorithm)), args.repeats)
+        score = timed(lambda: eng.em_cost(lv["cand_env"], lv["actions"], lv["n_actions"], int(cfg.algorithm), core=lv["core"],
+                                          distance=lv["distance"]), args.repeats)
+        steps = lv["n_actions"].cpu().numpy()
+        rows.append(dict(setting="optimize2, dubins %s" % name, library=size, max_nodes=max_nodes, calls_refused_for_depth=refused,
+                         nodes_mean=float(n_nodes.mean()), trees_failed=int((res == 0).sum()), leaves_total=int(n_leaves.sum()),
+                         leaf_steps_mean=float(steps.mean()) if len(steps) else 0.0, leaf_steps_max=int(steps.max()) if len(steps) else 0,
+                         core_steps_mean=float(lv["core"].sum(dim=1).double().mean()) if len(steps) else 0.0,
+                         best_plan_steps_mean=float(n_act.mean()), drawn_total=int((nxt - h0).sum()),
+                         em_plan_ms_median=statistics.median(whole), em_plan_ms=[round(x, 3) for x in whole],
+                         em_cost_on_leaves_ms_median=statistics.median(score), em_cost_on_leaves_ms=[round(x, 3) for x in score],
+                         tree_leaves_pick_ms=statistics.median(whole) - statistics.median(score)))
+    eng.check_status()
+    print(json.dumps(dict(envs=n, lib=os.environ.get("DRLGX_LIB_DEV", "libdrlgx.so"), repeats=args.repeats, settings=rows)))
+    eng.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -55,7 +111,11 @@ def main(argv=None):
     ap.add_argument("--max-nodes", type=float, default=0.5)
     ap.add_argument("--safe-distance", type=float, default=1.0)
     ap.add_argument("--no-dubins", action="store_true")
+    ap.add_argument("--optimize2", action="store_true")
+    ap.add_argument("--optimize2-max-nodes", type=float, default=0.1)
     args = ap.parse_args(argv)
+    if args.optimize2:
+        return optimize2(args)
     n = args.envs
     cfg = default_config(MAP, num_landmarks=NUM_LM, max_poses=41, max_actions=64)
     eng = Engine(cfg, n, 0)
