@@ -1,11 +1,15 @@
 """CPU tests of the g-U-Net modules (scripts/Networks.py:125-449): construction, `state_dict` layout and init without a GPU, checkpoint
-exchange with the plain-torch restatement, the refused constructor arguments, and the restatement itself on a case done by hand."""
+exchange with the plain-torch restatement, the refused constructor arguments, and the restatement itself on a case done by hand; the cases of
+tests/test_gpu_unet_edges.py (tests/unet_cases.py): the regime each reaches, the sparse augment reference against the dense one, the
+score gaps of the trunk cases."""
 import io
 import math
 
 import pytest
 import torch
 
+import test_gpu_unet as TU
+import unet_cases as UC
 import unet_ref
 
 
@@ -129,3 +133,103 @@ def test_restatement_trunk_runs_and_every_parameter_gets_a_gradient():
     out.sum().backward()
     assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.parameters())
     assert float(m.pools[0].weight.grad.abs().max()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_gpu_unet_edges.py: what they reach, their reference and their preconditions
+# ---------------------------------------------------------------------------------------------------------------------
+def same_entries(a, b):
+    return a[0].tolist() == b[0].tolist() and a[1].tolist() == b[1].tolist() and a[2] == b[2]
+
+
+def test_the_regime_formulas_on_the_figures_worked_by_hand():
+    """T = min(256, (lds_words - n) / (2 n + 2 ceil(n / 32))) with the whole budget: below the node count from 126 nodes, 64 -> 63 at
+    246 -> 247, 78 at 200, 15 at 1 025, 3 at the cap; a 61-node graph beside a 200-node one has 256 rows, a 62-node one 255."""
+    assert UC.launch_lds_words(71, 71) == 71 + 71 * (142 + 6) and UC.launch_lds_words(126, 126) == UC.LDS_WORDS
+    full = [UC.rows_in_flight(n, UC.LDS_WORDS) for n in (125, 126, 200, 246, 247, 1025, 4095, 4096)]
+    assert full == [126, 125, 78, 64, 63, 15, 3, 3]
+    assert UC.regime([125], [125], 125) == [(125, 1)]  # (its own launch asks for 125 rows only)
+    assert UC.regime([4096], [7], 4096) == [(3, 3)] and UC.regime([61, 62, 200], [61, 62, 200], 200) == [(256, 1), (255, 1), (78, 3)]
+
+
+@pytest.mark.parametrize("case", UC.AUGMENT_CASES, ids=UC.AUGMENT_IDS)
+def test_augment_cases_reach_their_regime_and_the_sparse_reference_equals_the_dense_one(case):
+    inp = UC.augment_inputs(case)
+    expect = [case["expect"][j] for j in inp["order"]]
+    assert UC.regime(inp["sizes"], inp["ks"], inp["max_nodes"]) == expect
+    assert max(inp["sizes"]) <= inp["max_nodes"] <= UC.MAX_GRAPH_NODES
+    ei, ew, counts, largest = UC.augment_reference(inp)
+    assert 0 < largest < UC.EXACT_LIMIT  # float32 sums of these integers are exact
+    assert bool((ew == ew.round()).all())
+    if max(inp["sizes"]) <= UC.DENSE_REF_NODES:
+        assert same_entries((ei, ew, counts), UC.augment_reference(inp, dense=True))
+    for (kind, n, keep), k, c in zip([case["graphs"][j] for j in inp["order"]], inp["ks"], counts):
+        assert c <= k * (k - 1)
+        if kind == "star":
+            assert c == k * (k - 1) and k == n  # the dense product: no free slot
+    if case.get("foreign"):
+        used = inp["edge_index"][:, :inp["used"]]
+        assert int((used == -1).all(0).sum()) >= 40 and inp["edge_index"].shape[1] > inp["used"]
+        g0 = used[:, :int(inp["edge_off"][1])]
+        assert int(((g0[0] >= 200) ^ (g0[1] >= 200)).sum()) == 12  # one endpoint in the neighbouring graph
+
+
+def test_boundary_halves_hold_or_lack_both_sides_of_each_word_boundary():
+    for n in (33, 65, 97):
+        for keep, inside in (("with", True), ("without", False)):
+            kept = UC.kept_rows(n, keep, torch.Generator().manual_seed(n)).tolist()
+            assert len(kept) == (n + 1) // 2 and kept == sorted(set(kept))
+            assert all((c in kept) == inside for c in UC.BOUNDARY_COLUMNS if c < n)
+
+
+def test_mixed_batch_reversed_holds_the_same_graphs():
+    fwd, rev = (UC.augment_inputs(c) for c in UC.AUGMENT_CASES if c["id"] in ("mixed", "mixed-reversed"))
+    assert rev["sizes"] == fwd["sizes"][::-1] and rev["order"] == fwd["order"][::-1]
+    for j in range(len(fwd["sizes"])):
+        g = len(fwd["sizes"]) - 1 - j
+        a = fwd["edge_index"][:, int(fwd["edge_off"][j]):int(fwd["edge_off"][j + 1])] - int(fwd["node_off"][j])
+        b = rev["edge_index"][:, int(rev["edge_off"][g]):int(rev["edge_off"][g + 1])] - int(rev["node_off"][g])
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("kind", ["fan", "star_in", "star_out", "star_both", "star_drop_hub", "isolated", "duplicates", "batch"])
+def test_sparse_reference_equals_the_dense_one_on_the_existing_cases(kind):
+    gen = torch.Generator().manual_seed(17)
+    sizes, ei, ew, perm = TU.augment_case(kind, gen)
+    if perm is None:
+        perm, _ = unet_ref.select(torch.rand(sum(sizes), generator=gen), sizes, 0.5)
+        ks = [unet_ref.keep_count(n, 0.5) for n in sizes]
+    else:
+        ks = [int(perm.numel())]
+    assert same_entries(unet_ref.augment_filter_sparse(ei, ew.double(), sizes, perm, ks), unet_ref.augment_filter(ei, ew.double(), sizes, perm, ks))
+
+
+@pytest.mark.parametrize("case", UC.TRUNK_CASES, ids=UC.TRUNK_IDS)
+def test_trunk_cases_keep_every_kth_place_clear(case):
+    """The precondition of the GPU comparison, on the float64 reference alone: a case that loses its gap fails here first."""
+    _, kind, hidden, depth, out_dim, with_mask, ratio, seed = case
+    model, x, ei, ea, sizes, mask, d_out = UC.trunk_case(kind, hidden, depth, out_dim, with_mask, ratio, seed)
+    m = unet_ref.RefGraphUNet(5, hidden, depth, ratio, out_dim).double()
+    m.load_state_dict({k: v.double() for k, v in model.state_dict().items()})
+    with torch.no_grad():
+        m(x.double(), ei, ea.double(), None, sizes)
+    assert TU.GAP == 1e-3 and len(m.levels) == depth
+    TU.assert_gaps(m.levels)
+    want = unet_ref.level_sizes([x.shape[0]] if sizes is None else sizes, ratio, depth)
+    assert [lv["sizes"] for lv in m.levels] == want[1:]
+    if kind == "n200":
+        assert [s[0] for s in want] == [200, 160, 128, 103, 83]
+    if kind == "mixed":
+        assert max(sizes) > 125 and 1 in sizes
+    if ratio == 1.0:  # every node kept at every level: the identity
+        assert all(lv["perm"].tolist() == list(range(x.shape[0])) and min(lv["gaps"]) == math.inf for lv in m.levels)
+
+
+def test_module_case_at_depth_4_keeps_every_kth_place_clear():
+    from drl_graph_exploration_amd.networks import GraphUNet
+    x, ei, ea, sizes, _ = TU.module_batch()
+    torch.manual_seed(UC.MODULE_SEED)
+    model = GraphUNet(5, 1000, 1000, 4)
+    m64, _ = TU.module_reference(model, x, ei, ea, None, None, sizes, torch.float64)
+    assert len(m64.levels) == 4 and len(list(model.parameters())) == 24
+    TU.assert_gaps(m64.levels)

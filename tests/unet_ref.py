@@ -73,6 +73,57 @@ def augment_filter(edge_index, edge_attr, sizes, perm, new_sizes):
     return torch.cat(eis, 1), torch.cat(ews), counts
 
 
+def augment_rows_sparse(edge_index, edge_attr, sizes, perm, new_sizes):
+    """The same rule as `augment_filter` without a dense matrix, in plain Python over rows of dictionaries: per graph the list of
+    (kept local node i, {local column j: ((A + I)^2)[i][j]}) for the KEPT rows only, every structurally non-zero column (the diagonal
+    and dropped columns included).  M[i] = {j: summed weight} with the 1 of the identity added on the diagonal; a key is structure,
+    whatever its value.  Cost: the edges once, then per kept row its neighbours' rows."""
+    src, dst, w = edge_index[0].tolist(), edge_index[1].tolist(), edge_attr.tolist()
+    perm = perm.tolist()
+    graphs, off, noff = [], 0, 0
+    for n, k in zip(sizes, new_sizes):
+        M = {}
+        for a, b, v in zip(src, dst, w):
+            if off <= a < off + n and off <= b < off + n:
+                row = M.setdefault(a - off, {})
+                row[b - off] = row.get(b - off, 0.0) + v
+        rows = []
+        for i in (p - off for p in perm[noff:noff + k]):
+            left = dict(M.get(i, {}))
+            left[i] = left.get(i, 0.0) + 1.0
+            acc = {}
+            for m, v in left.items():
+                right = dict(M.get(m, {}))
+                right[m] = right.get(m, 0.0) + 1.0
+                for j, u in right.items():
+                    acc[j] = acc.get(j, 0.0) + v * u
+            rows.append((i, acc))
+        graphs.append(rows)
+        off += n
+        noff += k
+    return graphs
+
+
+def augment_filter_sparse(edge_index, edge_attr, sizes, perm, new_sizes):
+    """`augment_filter` from `augment_rows_sparse`: the same three results, for graphs too large for the dense product."""
+    graphs = augment_rows_sparse(edge_index, edge_attr, sizes, perm, new_sizes)
+    perm = perm.tolist()
+    r, c, ws, counts, off, noff = [], [], [], [], 0, 0
+    for n, k, rows in zip(sizes, new_sizes, graphs):
+        new = {p - off: noff + m for m, p in enumerate(perm[noff:noff + k])}
+        before = len(r)
+        for i, acc in rows:
+            for j in sorted(acc):
+                if j != i and j in new:
+                    r.append(new[i])
+                    c.append(new[j])
+                    ws.append(acc[j])
+        counts.append(len(r) - before)
+        off += n
+        noff += k
+    return torch.tensor([r, c], dtype=torch.long).view(2, -1), torch.tensor(ws, dtype=edge_attr.dtype), counts
+
+
 class GCNConv(torch.nn.Module):
     def __init__(self, in_channels, out_channels):
         super().__init__()
