@@ -588,6 +588,10 @@ int drlgx_gcn_backward(void *hip_stream, int n_nodes, int n_edges, int in_dim, i
  * out = (relu(h) [* dropout mask]) Wf^T + bf.  All pointers DEVICE, fp32 (edge_index int64 as PyG); weight, b_ih, b_hh and
  * the mask 16-byte aligned.  n_graphs > 0: the batch's graph boundaries as drlgx_gcn_forward_batched takes them (both CSRs in one
  * launch while no graph has more than 2 048 edges); n_graphs <= 0: the generic CSR build.  Same results bit for bit.
+ * Edges: repeated edges add up; an edge with an endpoint outside [0, n_nodes) is ignored, with graph boundaries also one whose
+ * endpoints are not both in the graph that owns its slot (the generic build keeps an in-range edge between two graphs: give it
+ * none); an explicit self loop (i, i) is the node's self weight, of which there is ONE per node: of two self loops on one node
+ * only one counts, and which is not defined (both builds).
  * ws_dev: workspace of drlgx_ggnn_workspace_bytes(); it keeps what the backward call needs (both CSRs and per layer h, A h,
  * a and the gates r, z, n, W_hn h + b_hn).  DRLGX_E_INVALID: in_dim > 8, in_dim > hidden, hidden & 3, n_layers < 1 (or > 16),
  * null pointers. */

@@ -6,16 +6,20 @@ of tests/test_ggnn_cpu.py and tests/test_gpu_ggnn.py.  CPU, float64 or float32 (
 
 The aggregation is `index_add_` at the TARGET node, the products `torch.nn.functional.linear`, the cell a real
 `torch.nn.GRUCell`.  `state_dict` keys as the reference's classes: gconv1.weight, gconv1.rnn.{weight,bias}_{ih,hh},
-fully_con1.{weight,bias}."""
+fully_con1.{weight,bias}.
+
+`dense=True` is a second restatement of the aggregation alone, independent of `index_add_`: the adjacency as a dense matrix,
+A[dst, src] += w (`index_put_` with accumulate: repeated edges add up, an explicit self loop is a diagonal entry), and
+a = A @ (h @ weight[l]).  tests/test_ggnn_cpu.py holds the two against each other in float64."""
 import math
 
 import torch
 
 
 class GatedGraphConv(torch.nn.Module):
-    def __init__(self, out_channels, num_layers):
+    def __init__(self, out_channels, num_layers, dense=False):
         super().__init__()
-        self.out_channels, self.num_layers = out_channels, num_layers
+        self.out_channels, self.num_layers, self.dense = out_channels, num_layers, dense
         self.weight = torch.nn.Parameter(torch.empty(num_layers, out_channels, out_channels))
         self.rnn = torch.nn.GRUCell(out_channels, out_channels)
         bound = 1.0 / math.sqrt(out_channels)
@@ -24,9 +28,14 @@ class GatedGraphConv(torch.nn.Module):
 
     def forward(self, x, edge_index, edge_weight):
         h = torch.cat([x, x.new_zeros(x.shape[0], self.out_channels - x.shape[1])], dim=1)
+        if self.dense:
+            A = x.new_zeros(x.shape[0], x.shape[0]).index_put_((edge_index[1], edge_index[0]), edge_weight, accumulate=True)
         for l in range(self.num_layers):
             m = torch.nn.functional.linear(h, self.weight[l].t())  # h @ weight[l]
-            a = torch.zeros_like(m).index_add_(0, edge_index[1], edge_weight.unsqueeze(1) * m[edge_index[0]])
+            if self.dense:
+                a = A @ m
+            else:
+                a = torch.zeros_like(m).index_add_(0, edge_index[1], edge_weight.unsqueeze(1) * m[edge_index[0]])
             h = self.rnn(a, h)
         return h
 
@@ -35,13 +44,17 @@ class RefGGNN(torch.nn.Module):
     """The trunk shared by GGNN (out_dim 1), PolicyGGNN (1) and ValueGGNN (100); `mask`: the dropout mask (0 or 1 / (1 - p)) that
     F.dropout would have applied, or None."""
 
-    def __init__(self, hidden=1000, num_layers=3, out_dim=1):
+    def __init__(self, hidden=1000, num_layers=3, out_dim=1, dense=False):
         super().__init__()
-        self.gconv1 = GatedGraphConv(hidden, num_layers)
+        self.gconv1 = GatedGraphConv(hidden, num_layers, dense)
         self.fully_con1 = torch.nn.Linear(hidden, out_dim)
 
     def forward(self, x, edge_index, edge_attr, mask=None):
-        h = torch.relu(self.gconv1(x, edge_index, edge_attr))
+        return self.read_out(self.gconv1(x, edge_index, edge_attr), mask)
+
+    def read_out(self, h_last, mask=None):
+        """From h_L (what `gconv1` returns, before the relu) on: relu, the mask, the linear layer."""
+        h = torch.relu(h_last)
         if mask is not None:
             h = h * mask
         return self.fully_con1(h)

@@ -1,11 +1,13 @@
 """CPU tests of the GG-NN modules (scripts/Networks.py:73-122): construction, `state_dict` layout and init without a GPU, the
-reference's checkpoints' keys, and the trainers' model factory."""
+reference's checkpoints' keys, and the trainers' model factory; then the cases of tests/test_gpu_ggnn_edges.py (tests/ggnn_cases.py):
+the regime each reaches, its distance from the ReLU's kink, and the dense restatement of the aggregation against the `index_add_` one."""
 import io
 import math
 
 import pytest
 import torch
 
+import ggnn_cases as GC
 import ggnn_ref
 
 KEYS = {
@@ -91,3 +93,86 @@ def test_restatement_aggregates_at_the_target_node():
     want0 = conv.rnn(torch.zeros(1, 2, dtype=torch.float64), x[0:1])
     want1 = conv.rnn(3.0 * x[0:1], x[1:2])
     assert torch.allclose(h[0:1], want0) and torch.allclose(h[1:2], want1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_gpu_ggnn_edges.py: their regimes, their distance from the ReLU's kink, and the checker itself
+# ---------------------------------------------------------------------------------------------------------------------
+def _rel(a, ref):
+    d, m = float((a - ref).abs().max()) if ref.numel() else 0.0, float(ref.abs().max()) if ref.numel() else 0.0
+    return d / m if m > 0 else (0.0 if d == 0 else math.inf)
+
+
+@pytest.mark.parametrize("cid", GC.IDS)
+def test_edge_case_reaches_the_regime_its_table_row_says(cid):
+    case = GC.BY_ID[cid]
+    with_segments, generic = GC.expected(case)
+    assert GC.regime(case, False) == generic
+    if case["ways"] == "both":
+        assert GC.regime(case, True) == with_segments
+    sizes, counts = GC.graph_sizes(case)
+    ei, ea, kind = GC.edges(case)
+    assert ei.shape == (2, sum(counts)) and ea.shape == (sum(counts),)
+    # grouped by graph: every live edge inside its graph's nodes, every cross edge with exactly one endpoint outside, dead slots (-1, -1)
+    node_off = torch.tensor([0] + sizes).cumsum(0)
+    slot_graph = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(counts))
+    lo, hi = node_off[slot_graph], node_off[slot_graph + 1]
+    inside = (ei >= lo) & (ei < hi)
+    assert bool(inside[:, kind == 0].all()) and bool((inside[:, kind == 2].sum(0) == 1).all()) and bool((ei[:, kind == 1] == -1).all())
+    assert bool(((ei[:, kind == 2] >= 0) & (ei[:, kind == 2] < sum(sizes))).all())  # (in range: the generic build would keep them)
+    assert 1 <= case["layers"] <= GC.MAX_LAYERS and case["in_dim"] <= min(8, case["hidden"]) and case["hidden"] % 4 == 0
+    loops = ei[0] == ei[1]
+    assert torch.unique(ei[0][loops & (kind == 0)]).numel() == int((loops & (kind == 0)).sum())  # never two self loops on one node
+
+
+def test_edge_case_table_covers_what_it_claims():
+    reg = {c["id"]: (GC.regime(c, c["ways"] == "both"), c) for c in GC.CASES}
+    one = [r for r, c in reg.values() if r["build"] == "one-launch"]
+    passes = [p for r in one for p in r["csr"]]
+    assert {p[0] for p in passes} >= {0, 1, 2, 3} and {p[1] for p in passes} >= {0, 1, 2, 3, 8}
+    assert [GC.graph_sizes(c)[1][0] - GC.RAW_MAX_EDGES for _, c in reg.values() if c["id"].startswith("A3-e")] == [-1, 0, 1]
+    assert reg["A3-e2048"][0]["build"] == "one-launch" and reg["A3-e2049"][0]["build"] == "generic" and reg["A3-5+11+e2049"][0]["build"] == "generic"
+    assert {r["scan"] for r, c in reg.values() if "scan" in r} >= {1, 2, 3}
+    assert (128, 8) in {r["thin"] for r, _ in reg.values()} and {r["splitk"] for r, _ in reg.values()} >= {1, 2, 8}
+    assert {c["in_dim"] for c in GC.CASES} == {1, 3, 4, 5, 8} and {c["layers"] for c in GC.CASES} >= {4, 5, GC.MAX_LAYERS}
+    assert {c["out_dim"] for c in GC.CASES} >= {GC.THIN_OUT - 1, GC.THIN_OUT, GC.THIN_OUT + 1}
+    assert sorted(c["hidden"] for c in GC.CASES if not c["mask"]) == [4, 8, 12]  # the unmasked cases are small panels
+
+
+@pytest.mark.parametrize("cid", GC.IDS)
+def test_edge_case_keeps_the_relu_gate_out_of_the_comparison(cid):
+    """tau = 32 x the float32 restatement's error on h_L.  Masked cases: every entry within tau of zero is masked, at most 0.1 % of the
+    panel.  Unmasked cases: no entry within tau, and the case's seed is the first of its searched range with that property."""
+    case = GC.BY_ID[cid]
+    b = GC.build(cid)
+    assert b["tau"] > 0 and GC.gate_is_clear(b)
+    print("\n%s tau %.3e  smallest |h_L| %.3e  within tau %d of %d (%.4f %%)" % (cid, b["tau"], float(b["h64"].abs().min()), b["near"], b["h64"].numel(),
+                                                                              100.0 * b["near"] / b["h64"].numel()))
+    if b["mask"] is not None:
+        assert b["near"] <= GC.MASKED_SHARE * b["h64"].numel()
+        assert not bool(((b["h64"].abs() < b["tau"]) & (b["mask"] != 0)).any())
+        assert set(b["mask"].unique().tolist()) <= {0.0, 2.0}
+    else:
+        assert case["searched"] == (1, case["seed"])
+        assert b["near"] == 0 and float(b["h64"].abs().min()) >= b["tau"]
+        assert not any(GC.seed_is_clear(case, s) for s in range(1, case["seed"]))
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in GC.CASES if sum(GC.graph_sizes(c)[0]) <= GC.DENSE_REF_NODES])
+def test_dense_restatement_agrees_with_the_index_add_one(cid):
+    """Repeated edges add up and an explicit self loop is a diagonal entry of A, independently of `index_add_`: float64, 1e-12."""
+    b = GC.build(cid)
+    dense = GC.reference(b["model"], b["x"], b["ref_ei"], b["ref_ea"], b["mask"], b["d_out"], torch.float64, dense=True)
+    for name, d, r in zip(GC.NAMES, dense, b["ref"]):
+        assert d.shape == r.shape and _rel(d, r) <= 1e-12, (name, _rel(d, r))
+
+
+def test_dense_restatement_by_hand():
+    """Edge 0 -> 1 given twice (weights 3 and -1) and a self loop of weight 2 on node 1: A = [[0, 0], [2, 2]]."""
+    conv = ggnn_ref.GatedGraphConv(2, 1, dense=True).double()
+    with torch.no_grad():
+        conv.weight[0] = torch.eye(2)
+    x = torch.tensor([[1.0, 2.0], [5.0, 7.0]], dtype=torch.float64)
+    h = conv(x, torch.tensor([[0, 1, 0], [1, 1, 1]]), torch.tensor([3.0, 2.0, -1.0], dtype=torch.float64))
+    want1 = conv.rnn(2.0 * x[0:1] + 2.0 * x[1:2], x[1:2])
+    assert torch.allclose(h[0:1], conv.rnn(torch.zeros(1, 2, dtype=torch.float64), x[0:1])) and torch.allclose(h[1:2], want1)
