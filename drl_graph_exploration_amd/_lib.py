@@ -43,6 +43,7 @@ SYMBOLS = [
     "drlgx_segment_softmax", "drlgx_segment_softmax_backward", "drlgx_mean_pool", "drlgx_mean_pool_backward",
     "drlgx_ggnn_workspace_bytes", "drlgx_ggnn_forward", "drlgx_ggnn_backward",
     "drlgx_greedy_plans",
+    "drlgx_set_env_obstacles", "drlgx_obstacle_flags", "drlgx_follow_plans",
     "drlgx_unet_workspace_bytes", "drlgx_unet_forward", "drlgx_unet_backward", "drlgx_unet_topk", "drlgx_unet_augment_filter", "drlgx_unet_kept_nodes",
 ]
 
@@ -77,7 +78,11 @@ def lib():
     L.drlgx_step_plans.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.drlgx_step_plans_traced.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp]
     L.drlgx_greedy_plans.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 5 + [C.c_int, C.c_int, vp, vp, vp]
-    L.drlgx_stage_reset_host.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_uint32), dp]
+    if os.environ.get("DRLGX_LIB_DEV") is None or hasattr(L, "drlgx_follow_plans"):  # (a variant library of an earlier commit lacks them)
+        L.drlgx_set_env_obstacles.argtypes = [vp, C.c_int]
+        L.drlgx_obstacle_flags.argtypes = [vp, vp]
+        L.drlgx_follow_plans.argtypes = [vp, vp, vp, vp, vp, C.c_int, dp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp]
+    L.drlgx_stage_reset_host.argtypes =[vp, C.c_int, ip, C.POINTER(C.c_uint32), dp]
     L.drlgx_stage_set_prior_information_host.argtypes = [vp, C.c_int, dp]
     L.drlgx_stage_set_prior_pose_host.argtypes = [vp, C.c_int, dp]
     L.drlgx_stage_move.argtypes = [vp, vp, vp]

@@ -20,7 +20,11 @@
 // cnt[] slots
 enum { C_P = 0, C_L = 1, C_M = 2, C_STEP = 3, C_ISAM = 4, C_NEWP = 5, C_NEWL = 6, C_FLAG = 7 };
 // red[] slots (outputs of the map kernel)
-enum { R_UTR = 0, R_KNOWN = 1, R_EXPL = 2, R_UDET = 3, R_UWTR = 4, R_DIST = 5 };
+// ... and two of the simulator's: the travelled distance, and - written only under the obstacle opt-in (drlgx_set_env_obstacles,
+// ksim::k_sim_step_obs) - SS2D.simulate's obstacle state as 0.0 / 1.0: R_OBS the last step's flag, R_LATCH 1.0 while the
+// reference's `_cleared` is False (pyss2d.py:132,183-197).  k_reset zeroes the slice: no obstacle, cleared.  They travel with the
+// field `red` of the copy table (class 0: snapshot, restore - lazy or not -, instance copies).
+enum { R_UTR = 0, R_KNOWN = 1, R_EXPL = 2, R_UDET = 3, R_UWTR = 4, R_DIST = 5, R_OBS = 6, R_LATCH = 7 };
 
 // All per-instance arrays live in ONE HBM allocation; instance-major, contiguous per instance so a
 // workgroup streams its own slice with coalesced accesses.
@@ -693,6 +697,8 @@ void drlgx_launch_presim(const DrlgxState &S, hipStream_t st, LaunchSel sel, con
                          unsigned char *simlog, size_t simlog_roll, int simlog_act);
 void drlgx_launch_sim(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride,
                       int n_measure);
+// the same stage (n_measure = 2) with the obstacle flag of SS2D.simulate (red[R_OBS], red[R_LATCH])
+void drlgx_launch_sim_obs(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride);
 // p_bound: host-side upper bound of the pose count of every selected instance after this launch (<= P_max); it picks
 // the kernel variant (the kernels flag DRLGX_E_CAPACITY instead of overrunning if the bound is violated)
 void drlgx_launch_slam(const DrlgxState &S, hipStream_t st, LaunchSel sel, int p_bound);
@@ -804,6 +810,14 @@ void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, do
 // behind action index a of the chosen plans: the per-action record and the device-side stop at done (k_plan_record)
 void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,
                               int max_steps, double *trace, int32_t *done);
+// drlgx_follow_plans: what every env executes (act [n_envs][A_max][3], n_exec, stop), from its plan, its planner result and `steps`
+// (fallback: HOST double[3]); then behind action index a the record with the cuts at done, an obstacle flag (obstacles != 0) and a
+// rejected next odometry (k_follow_select / k_follow_record)
+void drlgx_launch_follow_select(const DrlgxState &S, hipStream_t st, const double *plan, const int32_t *n_actions, const int32_t *result,
+                                const uint8_t *active, int steps, const double *fallback, double *act, int32_t *n_exec, int32_t *stop);
+void drlgx_launch_follow_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, const double *act, int32_t *n_exec, int obstacles,
+                                double done_explored, int max_steps, double *trace, int32_t *done, int32_t *stop);
+void drlgx_launch_obstacle_flags(const DrlgxState &S, hipStream_t st, uint8_t *out);  // uint8 [2][n_envs]: flag, cleared
 void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length, double *angle);
 void drlgx_launch_line_plan(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *goal,
                             double *actions, int32_t *n_actions);

@@ -97,6 +97,10 @@ struct drlgx_engine {
   double sampler_max_nodes = 0.5, sampler_safe_distance = 0.0;
   int sampler_dubins = 0;
   int sampler_obstacles = 0;  // drlgx_set_sampler_obstacles: the sampler's obstacle logic (safe_distance > 0), off unless asked for
+  // drlgx_set_env_obstacles: SS2D.simulate's obstacle flag at cfg.safe_distance > 0, off unless asked for; drlgx_follow_plans'
+  // selected actions [n_envs][max_actions][3] (allocated on first use)
+  int env_obstacles = 0;
+  double *follow_act = nullptr;
   // drlgx_set_dubins_leaf_scoring: drlgx_em_plan under the Dubins control model, off unless asked for; the leaves' core masks and
   // tree distances (grown with the candidates), the number of candidates the last served call left (drlgx_em_plan_leaves)
   int dubins_leaf_scoring = 0;
@@ -785,10 +789,14 @@ int drlgx_reset_host(drlgx_engine *e, int n, const int32_t *env_ids, const uint3
 // One belief step of a selection, in the form its pose bound pb allows: the fused kernel around the dense solver, the same
 // fusion around the pose-chain solver (longer trajectories), or the three stage kernels - also in timing mode 2, where each
 // stage gets its own span (timers 0-2; the fused forms: timer 5).  n_measure: the simulator's stream selector.
-static void launch_belief_step(drlgx_engine *e, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int pb, bool may_split) {
+// obstacles: a step of LIVE envs under the obstacle opt-in (env_obstacles_on) - always the three stage kernels, the simulator stage in
+// its flag-raising form (k_sim_step_obs); the beliefs are those of the other forms bit for bit (the stage kernels against the fused
+// ones: tests/test_gpu_step_edges.py; the flag's simulator against the plain one: tests/test_gpu_obstacle.py).
+static void launch_belief_step(drlgx_engine *e, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int pb, bool may_split,
+                               bool obstacles = false) {
   const DrlgxState &S = e->S;
   sel.pcap = pb;  // (the kernels size their per-pose LDS tables with the launch's bound, not with the capacity)
-  if (drlgx_step_fusable(S, pb) && !e->per_stage) {
+  if (drlgx_step_fusable(S, pb) && !e->per_stage && !obstacles) {
     ScopedTimer t(e, 5);
     // more instances than CUs: simulator + SLAM fused, the map as its own launch in the two-workgroups-per-CU form (k_map_c) - at one
     // workgroup per CU the fused map stage cannot overlap anything, two map workgroups per CU cover each other's barriers
@@ -799,13 +807,14 @@ static void launch_belief_step(drlgx_engine *e, LaunchSel sel, const double *odo
       sel.skip_map = 0;
       drlgx_launch_map(S, e->stream, sel, 1);
     }
-  } else if (drlgx_step_arrow_fusable(S) && !e->per_stage) {
+  } else if (drlgx_step_arrow_fusable(S) && !e->per_stage && !obstacles) {
     ScopedTimer t(e, 5);
     drlgx_launch_step_arrow(S, e->stream, sel, odom, odom_stride, n_measure);
   } else {
     {
       ScopedTimer t(e, 0);
-      drlgx_launch_sim(S, e->stream, sel, odom, odom_stride, n_measure);
+      if (obstacles) drlgx_launch_sim_obs(S, e->stream, sel, odom, odom_stride);
+      else drlgx_launch_sim(S, e->stream, sel, odom, odom_stride, n_measure);
     }
     {
       ScopedTimer t(e, 1);
@@ -818,6 +827,9 @@ static void launch_belief_step(drlgx_engine *e, LaunchSel sel, const double *odo
   }
 }
 
+// the obstacle opt-in is live: asked for, and the ini file's [Environment] safe_distance can flag anything
+static bool env_obstacles_on(const drlgx_engine *e) { return e->env_obstacles && e->S.cfg.safe_distance > 0.0; }
+
 int drlgx_step(drlgx_engine *e, const double *odom_dev, const uint8_t *active_dev) {
   DRLGX_ENTER_OWING(e);
   if (!e || !odom_dev) return DRLGX_E_INVALID;
@@ -827,7 +839,7 @@ int drlgx_step(drlgx_engine *e, const double *odom_dev, const uint8_t *active_de
   e->owed_slot = -1;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
   advance_pbound(e, 1);
-  launch_belief_step(e, sel, odom_dev, 3, 2, pb, true);
+  launch_belief_step(e, sel, odom_dev, 3, 2, pb, true, env_obstacles_on(e));
   {
     ScopedTimer t(e, 7);  // empty span: the event-pair overhead, so that callers can subtract it
   }
@@ -845,7 +857,7 @@ int drlgx_step_plan(drlgx_engine *e, const double *actions_dev, const int32_t *n
   sel.map_last_only = map_last_only ? 1 : 0;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
   advance_pbound(e, 1);
-  launch_belief_step(e, sel, actions_dev, e->S.A_max * 3, 2, pb, false);
+  launch_belief_step(e, sel, actions_dev, e->S.A_max * 3, 2, pb, false, env_obstacles_on(e));
   return check_launch(e);
 }
 
@@ -908,7 +920,8 @@ int drlgx_step_plans(drlgx_engine *e, const double *actions_dev, const int32_t *
   if (max_n_actions == 0) return DRLGX_OK;
   LaunchSel sel{0, e->S.n_envs, nullptr, n_actions_dev, 0};
   sel.map_last_only = map_last_only ? 1 : 0;
-  const int a_begin = launch_action_range(e, sel, actions_dev, 2, max_bound(e), max_n_actions, false, false);  // (all of them or none)
+  // (all of them or none; under the obstacle opt-in none: every action raises or clears its env's flag in drlgx_step_plan's form)
+  const int a_begin = env_obstacles_on(e) ? 0 : launch_action_range(e, sel, actions_dev, 2, max_bound(e), max_n_actions, false, false);
   advance_pbound(e, a_begin);
   for (int a = a_begin; a < max_n_actions; ++a) {
     const int r = drlgx_step_plan(e, actions_dev, n_actions_dev, a, map_last_only);
@@ -931,6 +944,46 @@ int drlgx_step_plans_traced(drlgx_engine *e, const double *actions_dev, int32_t 
     if (r) return r;
     drlgx_launch_plan_record(e->S, e->stream, sigma0, a, n_actions_dev, done_explored, max_steps, trace_dev, done_dev);
   }
+  return check_launch(e);
+}
+
+// A plan FOLLOWED (EMExplorer.follow_path, explore()'s switch on the planner's result: scripts/envs/pyplanner2d.py:100-109,170-187):
+// k_follow_select turns (plan, result, steps) into every env's actions, then drlgx_step_plans_traced's loop with k_follow_record
+// behind each action index, which also cuts at an obstacle flag and in front of a rejected odometry.  No host round trip.
+int drlgx_follow_plans(drlgx_engine *e, const double *plan_dev, const int32_t *n_actions_dev, const int32_t *result_dev, const uint8_t *active_dev,
+                       int steps, const double *fallback_xytheta, double sigma0, double done_explored, int max_steps, double *trace_dev,
+                       int32_t *n_exec_dev, int32_t *done_dev, int32_t *stop_dev) {
+  DRLGX_ENTER(e);
+  if (!e || !plan_dev || !n_actions_dev || !result_dev || !fallback_xytheta || !trace_dev || !n_exec_dev || !done_dev || !stop_dev || steps < 0)
+    return DRLGX_E_INVALID;
+  const DrlgxState &S = e->S;
+  if (!e->follow_act) {
+    int r = dev_alloc(e, &e->follow_act, (size_t)S.n_envs * S.A_max * 3);
+    if (r) return r;
+  }
+  drlgx_launch_follow_select(S, e->stream, plan_dev, n_actions_dev, result_dev, active_dev, steps, fallback_xytheta, e->follow_act, n_exec_dev,
+                             stop_dev);
+  const int n_launch = std::min(std::max(steps, 1), S.A_max);  // (steps = 0 still runs a SAMPLING_FAILURE's fallback move)
+  for (int a = 0; a < n_launch; ++a) {
+    const int r = drlgx_step_plan(e, e->follow_act, n_exec_dev, a, 0);
+    if (r) return r;
+    drlgx_launch_follow_record(S, e->stream, sigma0, a, e->follow_act, n_exec_dev, env_obstacles_on(e) ? 1 : 0, done_explored, max_steps,
+                               trace_dev, done_dev, stop_dev);
+  }
+  return check_launch(e);
+}
+
+int drlgx_set_env_obstacles(drlgx_engine *e, int enabled) {
+  DRLGX_ENTER(e);
+  if (!e) return DRLGX_E_INVALID;
+  e->env_obstacles = enabled ? 1 : 0;
+  return DRLGX_OK;
+}
+
+int drlgx_obstacle_flags(drlgx_engine *e, uint8_t *out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || !out_dev) return DRLGX_E_INVALID;
+  drlgx_launch_obstacle_flags(e->S, e->stream, out_dev);
   return check_launch(e);
 }
 

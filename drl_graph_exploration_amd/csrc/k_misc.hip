@@ -313,6 +313,78 @@ __global__ __launch_bounds__(256) void k_plan_record(DrlgxState S, double sigma0
   }
 }
 
+// ---- following a plan (EMExplorer.follow_path and explore()'s result switch, scripts/envs/pyplanner2d.py:100-109,170-187) ----
+// SS2D.simulate's bounds test of an odometry increment (pyss2d.py:173-176) - ksim::odom_in_bounds (k_sim.hip) restated for this unit
+__device__ __forceinline__ bool follow_odom_ok(const drlgx_config &cfg, const double *a) {
+  return (cfg.map_min_x < a[0] && a[0] < cfg.map_max_x) && (cfg.map_min_y < a[1] && a[1] < cfg.map_max_y);
+}
+
+// What every env executes, one wave per env: SUCCESS (3) the first min(steps, n_actions) rows of its plan, SAMPLING_FAILURE (0)
+// the fallback move, anything else - or an inactive env - nothing (stop 4 / 5 for NO_SOLUTION / TERMINATION, else 0).  A first
+// action outside the map box is a rejected odometry before anything ran: no action, stop 3.
+__global__ __launch_bounds__(64) void k_follow_select(DrlgxState S, const double *plan, const int32_t *n_actions, const int32_t *result,
+                                                      const uint8_t *active, int steps, double fx, double fy, double fth, double *act,
+                                                      int32_t *n_exec, int32_t *stop) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  const int res = result[e];
+  const bool on = !active || active[e];
+  int n = 0;
+  if (on && res == 3) n = min(min(max(steps, 0), max(n_actions[e], 0)), S.A_max);
+  else if (on && res == 0) n = 1;
+  const double *src = plan + (size_t)e * S.A_max * 3;
+  double *dst = act + (size_t)e * S.A_max * 3;
+  const double fb[3] = {fx, fy, fth};
+  for (int k = lane; k < 3 * S.A_max; k += 64) dst[k] = k >= 3 * n ? 0.0 : res == 0 ? fb[k] : src[k];
+  if (lane == 0) {
+    const double first[3] = {res == 0 ? fx : src[0], res == 0 ? fy : src[1], 0.0};
+    const bool rejected = n > 0 && !follow_odom_ok(S.cfg, first);
+    n_exec[e] = rejected ? 0 : n;
+    stop[e] = rejected ? 3 : res == 1 ? 4 : res == 2 ? 5 : 0;
+  }
+}
+
+// k_plan_record for a followed plan: the same row and the same `done` cut (stop 1), then the two cuts of follow_path - the step
+// raised the obstacle flag (red[R_OBS], written under drlgx_set_env_obstacles only: stop 2, the step itself stays executed and
+// recorded), or the env's NEXT action is a rejected odometry (stop 3: it is never launched) - each by cutting n_exec behind this action.
+__global__ __launch_bounds__(256) void k_follow_record(DrlgxState S, double sigma0, int a, const double *act, int32_t *n_exec,
+                                                       int obstacles, double done_explored, int max_steps, double *trace, int32_t *done, int32_t *stop) {
+  __shared__ double red[3][4];
+  const int e = blockIdx.x;
+  if (a >= n_exec[e]) return;  // (the whole workgroup: nobody waits at metrics_of's barrier)
+  double m[3];
+  metrics_of(S, e, sigma0, red, m);
+  if (threadIdx.x == 0) {
+    double *t = trace + ((size_t)e * S.A_max + a) * 4;
+    const double explored = S.red[(size_t)e * DRLGX_RED_STRIDE + R_EXPL] / (double)S.count_explored;
+    t[0] = m[0];
+    t[1] = m[1];
+    t[2] = m[2];
+    t[3] = explored;
+    int why = 0;
+    if (explored > done_explored || S.cnt[(size_t)e * DRLGX_CNT_STRIDE + C_STEP] > max_steps) {
+      done[e] = 1;
+      why = 1;
+    } else if (obstacles && S.red[(size_t)e * DRLGX_RED_STRIDE + R_OBS] != 0.0) {
+      why = 2;
+    } else if (a + 1 < n_exec[e] && !follow_odom_ok(S.cfg, act + ((size_t)e * S.A_max + a + 1) * 3)) {
+      why = 3;
+    }
+    if (why) {
+      n_exec[e] = a + 1;
+      stop[e] = why;
+    }
+  }
+}
+
+// out[e] = the last step's obstacle flag, out[n_envs + e] = the cleared latch (pyss2d.py:132,183-197)
+__global__ void k_obstacle_flags(DrlgxState S, uint8_t *out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S.n_envs) return;
+  const double *red = S.red + (size_t)e * DRLGX_RED_STRIDE;
+  out[e] = red[R_OBS] != 0.0 ? 1 : 0;
+  out[S.n_envs + e] = red[R_LATCH] != 0.0 ? 0 : 1;
+}
+
 // numpy's arg-max order over (value, index) pairs: a NaN beats every number, among equals (and among NaNs) the lower index wins;
 // index < 0 = no element
 __device__ __forceinline__ bool pick_beats(float v, int i, float bv, int bi) {
@@ -393,6 +465,19 @@ void drlgx_launch_metrics(const DrlgxState &S, hipStream_t st, double sigma0, do
 void drlgx_launch_plan_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, int32_t *n_actions, double done_explored,
                               int max_steps, double *trace, int32_t *done) {
   hipLaunchKernelGGL(k_plan_record, dim3(S.n_envs), dim3(256), 0, st, S, sigma0, a, n_actions, done_explored, max_steps, trace, done);
+}
+void drlgx_launch_follow_select(const DrlgxState &S, hipStream_t st, const double *plan, const int32_t *n_actions, const int32_t *result,
+                                const uint8_t *active, int steps, const double *fallback, double *act, int32_t *n_exec, int32_t *stop) {
+  hipLaunchKernelGGL(k_follow_select, dim3(S.n_envs), dim3(64), 0, st, S, plan, n_actions, result, active, steps, fallback[0], fallback[1],
+                     fallback[2], act, n_exec, stop);
+}
+void drlgx_launch_follow_record(const DrlgxState &S, hipStream_t st, double sigma0, int a, const double *act, int32_t *n_exec, int obstacles,
+                                double done_explored, int max_steps, double *trace, int32_t *done, int32_t *stop) {
+  hipLaunchKernelGGL(k_follow_record, dim3(S.n_envs), dim3(256), 0, st, S, sigma0, a, act, n_exec, obstacles, done_explored, max_steps, trace,
+                     done, stop);
+}
+void drlgx_launch_obstacle_flags(const DrlgxState &S, hipStream_t st, uint8_t *out) {
+  hipLaunchKernelGGL(k_obstacle_flags, dim3((S.n_envs + 127) / 128), dim3(128), 0, st, S, out);
 }
 void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length, double *angle) {
   hipLaunchKernelGGL(k_cov_array, dim3((S.V + 255) / 256, S.n_envs), dim3(256), 0, st, S, length, angle);

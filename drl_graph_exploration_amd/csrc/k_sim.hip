@@ -90,8 +90,16 @@ __device__ inline int scan_in_range(SimCtx &c, int *inr, const GtPrefetch *pf = 
 // workgroup, which would otherwise wait for them to come back from HBM: factor M0 + r has its bearing / range in
 // nrm[2 r], nrm[2 r + 1] and its landmark slot in inr[r] (in place: r <= the index a lane read its own inputs from), new
 // landmark L0 + r its initial estimate in lmbox[2 r], lmbox[2 r + 1].
+// kObs (the obstacle opt-in, drlgx_set_env_obstacles; record, lead = 2 n_in, no lmbox): the `lead` variates are those of
+// SS2D.simulate's first measure() and are KEPT (nrm: 4 n_in + 1 doubles) - one draw of the same length as without the flag, so
+// the stream and its image advance identically.  That first list decides the step's obstacle flag (pyss2d.py:183-197): a
+// measurement that passes the sensor gates with range < safe_distance counts when the latch is up (`cleared`) or its key has no
+// landmark slot yet - "yet" = before this call's own appends, which is when the slots are read here.  The reference stops at the
+// first hit, but no branch of its scan does anything else, so the rule is order-free: a ballot.  Nothing else changes.
+template <bool kObs = false>
 __device__ inline void measure(SimCtx &c, bool record, double *nrm, const int *inr, int n_in, int32_t *exp_keys = nullptr,
-                               double *exp_br = nullptr, int32_t *exp_count = nullptr, int lead = 0, double *lmbox = nullptr) {
+                               double *exp_br = nullptr, int32_t *exp_count = nullptr, int lead = 0, double *lmbox = nullptr,
+                               bool cleared = true, bool *obstacle = nullptr) {
   const DrlgxState &S = c.S;
   const drlgx_config &cfg = S.cfg;
   const double *gl = S.gt_lm + (size_t)S.parent[c.inst] * S.LG * 2;
@@ -113,7 +121,27 @@ __device__ inline void measure(SimCtx &c, bool record, double *nrm, const int *i
       }
     }
   }
-  draw_normals(c.sensor, c.ns_sensor, lead + 2 * n_in, nrm, c.lane, (record || exp_keys) ? lead : lead + 2 * n_in);
+  draw_normals(c.sensor, c.ns_sensor, lead + 2 * n_in, nrm, c.lane, kObs ? 0 : (record || exp_keys) ? lead : lead + 2 * n_in);
+  if constexpr (kObs) {
+    bool hit = false;
+    for (int base = 0; base < n_in; base += 64) {
+      const int k = base + c.lane;
+      const bool v = k < n_in;
+      const bool pf = base < 128;
+      const int key = pf ? pf_key[base >> 6] : (v ? inr[k] : 0);
+      const P2 lm = pf ? P2{pf_x[base >> 6], pf_y[base >> 6]} : P2{gl[2 * key], gl[2 * key + 1]};
+      const double bn = (v ? nrm[2 * k] : 0.0) * cfg.bearing_noise + 0.0;
+      const double rn = (v ? nrm[2 * k + 1] : 0.0) * cfg.range_noise + 0.0;
+      const double bearing = bearing_of<false>(c.veh, lm, nullptr, nullptr) + bn;
+      const double range = range_of<false>(c.veh, lm, nullptr, nullptr) + rn;
+      const bool ok = v && bearing < cfg.max_bearing && bearing > cfg.min_bearing && range < cfg.max_range && range > cfg.min_range;
+      const bool near = ok && range < cfg.safe_distance;
+      const int slot = near ? (pf ? pf_slot[base >> 6] : key_slot[key]) : 0;
+      hit = hit || __ballot(near && (cleared || slot < 0)) != 0ull;
+    }
+    *obstacle = hit;
+    nrm += lead;  // (the second call's variates)
+  }
   if (exp_keys) {
     int n_out = 0;
     for (int base = 0; base < n_in; base += 64) {
@@ -354,7 +382,9 @@ __device__ __forceinline__ void sim_preload(const DrlgxState &S, int inst, int l
 // lds0 / lds1: 626 words each, dyn: (2 LG + 2) doubles + LG ints of LDS scratch.
 // kMove / exp_*: the staged interface runs the move (with addOdometry) and a single exporting measure() as separate
 // launches (drlgx_stage_move / drlgx_stage_measure); the fused step is <true> with n_measure = 2 and no export.
-template <bool kMove = true>
+// kObs: the obstacle opt-in (measure<true>; n_measure = 2, no export, no LDS hand-over; dyn: (4 LG + 2) doubles + LG ints).  The
+// step's flag and the latch go to red[R_OBS], red[R_LATCH] with the counts; a rejected move reports no obstacle and leaves the latch alone.
+template <bool kMove = true, bool kObs = false>
 __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchSel &sel, const double *odom, int odom_stride,
                                               int n_measure, uint32_t *lds0, uint32_t *lds1, double *dyn, int lane,
                                               int32_t *exp_keys = nullptr, double *exp_br = nullptr, int32_t *exp_count = nullptr,
@@ -362,7 +392,7 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
                                               int known_P = -1, int known_L = 0, int known_M = 0, const SimPre &pre_in = SimPre{}) {
   uint32_t *lds[2] = {lds0, lds1};
   double *nrm = dyn;
-  int *inr = reinterpret_cast<int *>(dyn + 2 * S.LG + 2);
+  int *inr = reinterpret_cast<int *>(dyn + (kObs ? 4 : 2) * S.LG + 2);
   const int i = drlgx_bid();
   if (!sel.on(i)) return;
   const int inst = sel.base + i;
@@ -373,7 +403,10 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
     const double *od = odom + (size_t)i * odom_stride + (size_t)sel.act_idx * 3;
     ox = od[0]; oy = od[1]; oth = od[2];
     if (!odom_in_bounds(cfg, ox, oy)) {
-      if (lane == 0) cnt[C_FLAG] = 1;
+      if (lane == 0) {
+        cnt[C_FLAG] = 1;
+        if constexpr (kObs) S.red[(size_t)inst * DRLGX_RED_STRIDE + R_OBS] = 0.0;
+      }
       return;
     }
   }
@@ -384,6 +417,7 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
   if (kMove && c.P >= S.P_max) {
     if (lane == 0) {
       cnt[C_FLAG] = 1;
+      if constexpr (kObs) S.red[(size_t)inst * DRLGX_RED_STRIDE + R_OBS] = 0.0;
       atomicMin(S.status, DRLGX_E_CAPACITY);
     }
     return;
@@ -399,6 +433,8 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
   if (!pre.have) sim_preload(S, inst, lane, n_measure, pre);
   const double *ep = S.est_pose + ((size_t)inst * S.P_max + (c.P - 1)) * 4;
   const Pose last_est{ep[0], ep[1], ep[2], ep[3]};
+  bool cleared = true, obstacle = false;
+  if constexpr (kObs) cleared = S.red[(size_t)inst * DRLGX_RED_STRIDE + R_LATCH] == 0.0;
   c.veh = pre.veh;
   const int step0 = pre.step0;
   const double dist0 = pre.dist0;
@@ -437,7 +473,9 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
   }
   if (n_measure > 0) {
     const int n_in = scan_in_range(c, inr, &gtp);
-    if (n_measure == 2 && !exp_keys) {
+    if constexpr (kObs) {
+      measure<true>(c, true, nrm, inr, n_in, nullptr, nullptr, nullptr, 2 * n_in, nullptr, cleared, &obstacle);
+    } else if (n_measure == 2 && !exp_keys) {
       // SS2D.simulate's two measure() calls (pyss2d.py:171-206): the first one only advances the sensor stream (obstacle
       // logic, inert at safe_distance = 0) - its 2 n_in variates are drawn and dropped together with the second call's
       DRLGX_PROF(S, 11);
@@ -463,6 +501,10 @@ __device__ __forceinline__ void sim_step_body(const DrlgxState &S, const LaunchS
       cnt[C_FLAG] = 0;
       cnt[C_STEP] = step0 + 1;
       S.red[(size_t)inst * DRLGX_RED_STRIDE + R_DIST] = dist_new;
+      if constexpr (kObs) {  // pyss2d.py:183-197: the step's flag, and the latch that a clear step re-arms
+        S.red[(size_t)inst * DRLGX_RED_STRIDE + R_OBS] = obstacle ? 1.0 : 0.0;
+        S.red[(size_t)inst * DRLGX_RED_STRIDE + R_LATCH] = obstacle ? 1.0 : 0.0;
+      }
     }
   }
   store_ctx(c, park_streams, mail);
@@ -678,6 +720,15 @@ __global__ __launch_bounds__(64) void k_sim_step(DRLGX_KS_PARAM, LaunchSel sel, 
   sim_step_body(S, sel, odom, odom_stride, n_measure, lds[0], lds[1], dyn, threadIdx.x);
 }
 
+// The simulator stage with the obstacle opt-in (drlgx_set_env_obstacles at cfg.safe_distance > 0): the belief step then runs as
+// the three stage kernels, this one first.  dyn: nrm[4 LG + 2] doubles (both measure() calls' variates), inr[LG] ints.
+__global__ __launch_bounds__(64) void k_sim_step_obs(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int odom_stride) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  __shared__ __attribute__((aligned(16))) uint32_t lds[2][DRLGX_MT_STRIDE];
+  extern __shared__ double dyn[];
+  sim_step_body<true, true>(S, sel, odom, odom_stride, 2, lds[0], lds[1], dyn, threadIdx.x);
+}
+
 // drlgx_stage_move (mode 0): Simulator2D::move + SLAM2D::addOdometry.  drlgx_stage_measure (mode 1): one
 // Simulator2D::measure whose valid measurements are exported: keys [n][LG], br [n][LG][2], count [n].
 __global__ __launch_bounds__(64) void k_sim_stage(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int mode, int32_t *keys,
@@ -770,4 +821,8 @@ void drlgx_launch_sim(const DrlgxState &S, hipStream_t st, LaunchSel sel, const 
                       int n_measure) {
   const size_t dyn = (size_t)(2 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
   hipLaunchKernelGGL(ksim::k_sim_step, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, odom_stride, n_measure);
+}
+void drlgx_launch_sim_obs(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride) {
+  const size_t dyn = (size_t)(4 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
+  hipLaunchKernelGGL(ksim::k_sim_step_obs, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, odom_stride);
 }

@@ -4,6 +4,7 @@ Bulk inputs/outputs are torch CUDA tensors (torch is used only for device memory
 `*_host` getters return numpy arrays and mirror the getters of the reference's pybind modules.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -35,6 +36,7 @@ class Engine(object):
         self.sampler_parameter, self.sampler_obstacles = (0.5, 0.0, False), False  # (the engine's values after drlgx_create)
         self.dubins_parameter = None
         self.dubins_leaf_scoring = False
+        self.env_obstacles = False
         _lib.check(self.L.drlgx_create(C.byref(cfg), n_envs, n_rollouts, device, C.byref(self.h)), self.h)  # (NULL: the creation's error)
         r, c = C.c_int32(), C.c_int32()
         self.L.drlgx_vm_shape(self.h, C.byref(r), C.byref(c))
@@ -154,6 +156,47 @@ class Engine(object):
         self._chk(self.L.drlgx_step_plans_traced(self.h, _p(actions), _p(n_exec), int(max_n_actions), float(sigma0),
                                                  float(done_explored), int(max_steps), _p(trace), _p(done)))
         return trace, n_exec, done
+
+    def set_env_obstacles(self, enabled):
+        """SS2D.simulate's obstacle flag at cfg.safe_distance > 0 (drlgx_set_env_obstacles): an opt-in, off after creation - the ini
+        files' [Environment] safe_distance is otherwise inert.  The beliefs do not change; every step also leaves obstacle_flags()."""
+        self._chk(self.L.drlgx_set_env_obstacles(self.h, 1 if enabled else 0))
+        self.env_obstacles = bool(enabled)
+
+    def obstacle_flags(self):
+        """(obstacle [n_envs] uint8: the last step's flag, cleared [n_envs] uint8: the latch) on the device (drlgx_obstacle_flags)."""
+        self.use_torch_stream()
+        out = torch.empty(2, self.n_envs, dtype=torch.uint8, device=self.device)
+        self._chk(self.L.drlgx_obstacle_flags(self.h, _p(out)))
+        return out[0], out[1]
+
+    STOP_RAN, STOP_DONE, STOP_OBSTACLE, STOP_REJECTED, STOP_NO_SOLUTION, STOP_TERMINATION = range(6)
+
+    def follow_plans(self, plan, n_actions, result, steps=5, active=None, fallback=(0.0, 0.0, math.pi / 4), sigma0=1.0, done_explored=0.85,
+                     max_steps=5000):
+        """Every env follows its plan as EMExplorer.follow_path / explore() do (drlgx_follow_plans, pyplanner2d.py:100-109,170-187):
+        SUCCESS (3) the first min(steps, n_actions) rows, SAMPLING_FAILURE (0) the fallback move, NO_SOLUTION / TERMINATION or an
+        inactive env nothing; an env stops behind a step that is done or raises the obstacle flag (set_env_obstacles) and in front
+        of a rejected odometry - on the device.  Returns device tensors (trace [n_envs, max_actions, 4] f64, NaN beyond the
+        executed actions; n_executed, done, stop [n_envs] i32 - stop: the STOP_* codes)."""
+        self.use_torch_stream()
+        A = self.cfg.max_actions
+        if not (plan.is_cuda and plan.dtype == torch.float64 and plan.is_contiguous() and tuple(plan.shape) == (self.n_envs, A, 3)):
+            raise ValueError("plan: contiguous CUDA float64 [n_envs, max_actions, 3]")
+        n_actions = n_actions.to(torch.int32).contiguous()
+        result = result.to(torch.int32).contiguous()
+        if n_actions.numel() != self.n_envs or result.numel() != self.n_envs:
+            raise ValueError("n_actions, result: [n_envs]")
+        if active is not None:
+            active = active.to(torch.uint8).contiguous()
+        trace = torch.full((self.n_envs, A, 4), float("nan"), dtype=torch.float64, device=self.device)
+        n_exec = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        done = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        stop = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+        fb = (C.c_double * 3)(*[float(v) for v in fallback])
+        self._chk(self.L.drlgx_follow_plans(self.h, _p(plan), _p(n_actions), _p(result), _p(active), int(steps), fb, float(sigma0),
+                                            float(done_explored), int(max_steps), _p(trace), _p(n_exec), _p(done), _p(stop)))
+        return trace, n_exec, done, stop
 
     @staticmethod
     def greedy_plans(score, seg_begin, n_frontier, actions_pad, n_act_pad, active=None):

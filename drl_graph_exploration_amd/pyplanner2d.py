@@ -332,8 +332,34 @@ class EMExplorer(SS2D):
         self.obstacle_logic = bool(kwargs.pop("obstacle_logic", False))
         self.dubins_paths = bool(kwargs.pop("dubins_paths", False))
         self.dubins_leaf_scoring = bool(kwargs.pop("dubins_leaf_scoring", False))
+        self.env_obstacles = bool(kwargs.pop("env_obstacles", False))
         super(EMExplorer, self).__init__(*args, **kwargs)
         self._planner = _Planner(self)
+        if self.env_obstacles:  # (after the reset: the latch starts up either way, pyss2d.py:132)
+            self.engine.set_env_obstacles(True)
+
+    def simulate(self, odom, core=True):
+        """pyss2d.py:171-206.  `env_obstacles` (an opt-in, off by default: Engine.set_env_obstacles): True also when the step raised
+        the obstacle flag of the ini file's [Environment] safe_distance; without it True for a rejected odometry only, as before."""
+        if super(EMExplorer, self).simulate(odom, core):
+            return True
+        if not self.env_obstacles:
+            return False
+        (flag,) = self.engine.fetch(self.engine.obstacle_flags()[0])
+        return bool(flag[0])
+
+    def follow_path(self, steps=3):
+        """pyplanner2d.py:100-109: the first `steps` edges of the last plan, root first; True when a step was rejected or - under
+        `env_obstacles` - met an obstacle (the path is left there), None otherwise, as the reference."""
+        if self._planner_params.dubins_control_model_enabled:
+            raise NotImplementedError("follow_dubins_path executes intermediate poses with simulate(core=False), which is outside the "
+                                      "accelerated path")
+        path = []
+        for edge in self._planner.iter_solution():
+            path.insert(0, edge.get_odoms()[0])
+        for odom in path[:steps]:
+            if self.simulate((odom.x, odom.y, odom.theta), core=True):
+                return True
 
     def plan(self):
         """pyplanner2d.py:70-71: EMPlanner2D::optimize2 on the device; the path is then `self._planner.iter_solution()`."""
@@ -362,3 +388,45 @@ class EMExplorer(SS2D):
         n = torch.tensor([len(actions)], dtype=torch.int32, device=self.engine.device)
         ce = torch.zeros(1, dtype=torch.int32, device=self.engine.device)
         return float(self.engine.lookahead(ce, acts, n)[0])
+
+
+def explore(config_file, max_distance=450, verbose=False, save_history=False, save_fig=False):
+    """scripts/envs/pyplanner2d.py:155-195: four scanning turns, then plan / follow_path(5) until the planner reports NO_SOLUTION or
+    TERMINATION, 200 steps have passed or the travelled distance exceeds `max_distance`; returns (status, mean planning time).
+    The planner's obstacle logic and SS2D.simulate's obstacle flag are switched on from the ini file's [Planner] and [Environment]
+    safe_distance.  The switch reads the planner's result itself (the reference compares plan()'s bool with the enum, so its first
+    three branches never run).  Plots and history dumps are out of scope: save_fig / save_history raise."""
+    from time import time
+    if save_fig or save_history:
+        raise NotImplementedError("explore(): plots (save_fig) and .npz history dumps (save_history) are out of scope")
+    cp = load_config(config_file) if isinstance(config_file, str) else config_file
+    _, prm = config_from_ini(cp)
+    explorer = EMExplorer(cp, verbose, obstacle_logic=prm["planner"].safe_distance != 0.0,
+                          env_obstacles=prm["environment"].safe_distance > 0.0)
+    status = 'MAX_DISTANCE'
+    planning_count = 0
+    planning_time = 0.0
+    try:
+        for step in range(200):
+            if step < 4:
+                explorer.simulate((0, 0, math.pi / 2.0), core=True)
+            else:
+                start = time()
+                result = explorer._planner.optimize2()
+                planning_time += time() - start
+                planning_count += 1
+                if result == planner2d.OptimizationResult.SAMPLING_FAILURE:
+                    explorer.simulate((0, 0, math.pi / 4), True)
+                elif result == planner2d.OptimizationResult.NO_SOLUTION:
+                    status = 'NO SOLUTION'
+                    break
+                elif result == planner2d.OptimizationResult.TERMINATION:
+                    status = 'TERMINATION'
+                    break
+                else:
+                    explorer.follow_path(5)
+                if explorer.distance > max_distance:
+                    break
+    finally:
+        explorer.engine.close()
+    return status, planning_time / max(planning_count, 1)

@@ -350,6 +350,25 @@ class VecExplorationEnv(object):
         self._graph = None
         return trace, n_exec, done
 
+    def follow(self, plan, n_actions, result, steps=5, active=None, sigma0=1.0):
+        """Every env follows its plan the way the reference's explore() loop does (scripts/envs/pyplanner2d.py:100-109,170-187,
+        Engine.follow_plans): `result` (em_plan's) selects the first min(steps, n_actions) edges, the fallback turn (0, 0, pi/4) of a
+        SAMPLING_FAILURE, or nothing; an env stops behind the action at which done() holds or the obstacle flag is raised
+        (Engine.set_env_obstacles) and in front of a rejected odometry, all on the device.  Returns device tensors (trace
+        [n_envs, max_actions, 4], n_executed, done, stop [n_envs] i32 - Engine.STOP_*) and no synchronisation: the caller reads
+        them - and the status word - with one `engine.fetch`.  self.dist advances by the executed actions' lengths."""
+        A = self.cfg.max_actions
+        if plan.shape[1] < A:
+            plan = torch.cat([plan, plan.new_zeros(plan.shape[0], A - plan.shape[1], 3)], dim=1)
+        plan = plan.contiguous()
+        trace, n_exec, done, stop = self.engine.follow_plans(plan, n_actions, result, steps=steps, active=active, sigma0=sigma0,
+                                                             done_explored=0.85, max_steps=self._max_steps)
+        # (a fallback move has no length: only the plan's executed rows count, and those only for an env whose plan was followed)
+        live = (torch.arange(A, device=self.device)[None, :] < n_exec[:, None]) & (result.to(self.device) == 3)[:, None]
+        self.dist += (torch.sqrt(plan[:, :, 0] ** 2 + plan[:, :, 1] ** 2) * live).sum(dim=1)
+        self._graph = None
+        return trace, n_exec, done, stop
+
     def status(self):
         return self.engine.explored()
 
