@@ -683,6 +683,13 @@ __host__ __device__ inline size_t drlgx_sim_lds_bytes(int LG, int P_max) {
 
 // ---- launchers implemented in the kernel translation units ------------------------------------
 struct DrlgxField;
+// LDS of one workgroup of a simulator launch (k_sim.hip), static + dynamic, as a function of LG = max(cfg.num_landmarks, 1): the
+// launchers size their dynamic part with the same expression.  These launches set no hipFuncAttributeMaxDynamicSharedMemorySize,
+// so kSimLdsLimit - what every launch of this project beyond it asks drlgx_ensure_lds_attr for first - bounds them (check_config,
+// drlgx_set_env_obstacles).  n_measure: k_presim's measure() calls per action (the look-ahead: 1).
+enum DrlgxSimLaunch { DRLGX_SIM_RESET, DRLGX_SIM_STEP, DRLGX_SIM_STEP_OBS, DRLGX_SIM_STAGE, DRLGX_SIM_PRESIM };
+constexpr size_t kSimLdsLimit = 64 * 1024;
+size_t drlgx_sim_launch_lds(DrlgxSimLaunch which, int LG, int n_measure = 1, size_t *dyn_out = nullptr);
 void drlgx_launch_reset(const DrlgxState &S, hipStream_t st, int n, const int32_t *env_ids_dev, const uint32_t *seeds_dev,
                         const double *start_dev, int first_measure = 1);
 // staged interface: mode 0 = move + addOdometry, mode 1 = one exporting measure (keys [n][LG], br [n][LG][2], count [n])

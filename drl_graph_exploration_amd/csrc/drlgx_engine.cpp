@@ -246,6 +246,16 @@ static int check_config(const drlgx_config *cfg, int n_envs, int n_rollouts) {
     g_create_error = "map too large for the LDS tables of the map kernel";
     return DRLGX_E_INVALID;
   }
+  // the simulator kernels keep a measure() call's variates and its in-range list in LDS, per listed landmark (k_sim.hip); their
+  // launches set no LDS attribute, so kSimLdsLimit bounds them: k_reset and the step's simulator stage for every engine, k_presim
+  // (one measure() per action) for one with look-ahead rollouts.  The obstacle opt-in has its own, lower bound (sim_obs_fits).
+  const int LG = std::max(cfg->num_landmarks, 1);
+  if (drlgx_sim_launch_lds(DRLGX_SIM_RESET, LG) > kSimLdsLimit || drlgx_sim_launch_lds(DRLGX_SIM_STEP, LG) > kSimLdsLimit ||
+      drlgx_sim_launch_lds(DRLGX_SIM_STAGE, LG) > kSimLdsLimit ||
+      (n_rollouts > 0 && drlgx_sim_launch_lds(DRLGX_SIM_PRESIM, LG, 1) > kSimLdsLimit)) {
+    g_create_error = "num_landmarks too large for the LDS of the simulator kernels (k_reset / k_sim_step / k_presim)";
+    return DRLGX_E_INVALID;
+  }
   return DRLGX_OK;
 }
 
@@ -976,6 +986,13 @@ int drlgx_follow_plans(drlgx_engine *e, const double *plan_dev, const int32_t *n
 int drlgx_set_env_obstacles(drlgx_engine *e, int enabled) {
   DRLGX_ENTER(e);
   if (!e) return DRLGX_E_INVALID;
+  // k_sim_step_obs keeps BOTH measure() calls' variates in LDS: an engine with more listed landmarks than that launch serves keeps
+  // the opt-in off (its plain steps are not concerned)
+  if (enabled && drlgx_sim_launch_lds(DRLGX_SIM_STEP_OBS, e->S.LG) > kSimLdsLimit) {
+    e->env_obstacles = 0;
+    e->last_error = "num_landmarks too large for the LDS of k_sim_step_obs: the obstacle opt-in stays off";
+    return DRLGX_E_CAPACITY;
+  }
   e->env_obstacles = enabled ? 1 : 0;
   return DRLGX_OK;
 }

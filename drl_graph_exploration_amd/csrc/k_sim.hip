@@ -11,6 +11,10 @@
 
 namespace ksim {
 
+// the static LDS of the kernels below: images of the mt19937 streams (k_reset seeds three, a step carries two); drlgx_sim_launch_lds
+// counts them
+constexpr int kResetStreams = 3, kSimStreams = 2;
+
 struct SimCtx {
   const DrlgxState &S;
   int inst, lane;
@@ -264,7 +268,7 @@ __device__ inline void store_ctx(SimCtx &c, bool park = false, int *mail = nullp
 __global__ __launch_bounds__(64) void k_reset(DRLGX_KS_PARAM, int first_measure, const int32_t *env_ids, const uint32_t *seeds,
                                               const double *start) {
   const DrlgxState &S = DRLGX_KS_REF;
-  __shared__ uint32_t lds[3][DRLGX_MT_STRIDE];
+  __shared__ uint32_t lds[kResetStreams][DRLGX_MT_STRIDE];
   extern __shared__ double dyn[];  // nrm[2 LG + 2] doubles, inr[LG] ints
   double *nrm = dyn;
   int *inr = reinterpret_cast<int *>(dyn + 2 * S.LG + 2);
@@ -530,7 +534,7 @@ constexpr int kLogHdr = 32, kLogRec = 24;
 __global__ __launch_bounds__(64) void k_presim(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end,
                                                unsigned char *simlog, size_t simlog_roll, int simlog_act) {
   const DrlgxState &S = DRLGX_KS_REF;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2][DRLGX_MT_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSimStreams][DRLGX_MT_STRIDE];
   extern __shared__ double dyn[];  // nrm[2 * n_measure * LG + 2] doubles, inr[LG] ints, kslot[LG] ints
   const int lane = threadIdx.x, i = blockIdx.x;
   if (sel.active && !sel.active[i]) return;
@@ -715,7 +719,7 @@ __device__ __forceinline__ void replay_step_body(const DrlgxState &S, const Laun
 __global__ __launch_bounds__(64) void k_sim_step(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int odom_stride,
                                                  int n_measure) {
   const DrlgxState &S = DRLGX_KS_REF;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2][DRLGX_MT_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSimStreams][DRLGX_MT_STRIDE];
   extern __shared__ double dyn[];  // nrm[2 LG + 2] doubles, inr[LG] ints
   sim_step_body(S, sel, odom, odom_stride, n_measure, lds[0], lds[1], dyn, threadIdx.x);
 }
@@ -724,7 +728,7 @@ __global__ __launch_bounds__(64) void k_sim_step(DRLGX_KS_PARAM, LaunchSel sel, 
 // the three stage kernels, this one first.  dyn: nrm[4 LG + 2] doubles (both measure() calls' variates), inr[LG] ints.
 __global__ __launch_bounds__(64) void k_sim_step_obs(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int odom_stride) {
   const DrlgxState &S = DRLGX_KS_REF;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2][DRLGX_MT_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSimStreams][DRLGX_MT_STRIDE];
   extern __shared__ double dyn[];
   sim_step_body<true, true>(S, sel, odom, odom_stride, 2, lds[0], lds[1], dyn, threadIdx.x);
 }
@@ -734,7 +738,7 @@ __global__ __launch_bounds__(64) void k_sim_step_obs(DRLGX_KS_PARAM, LaunchSel s
 __global__ __launch_bounds__(64) void k_sim_stage(DRLGX_KS_PARAM, LaunchSel sel, const double *odom, int mode, int32_t *keys,
                                                   double *br, int32_t *count) {
   const DrlgxState &S = DRLGX_KS_REF;
-  __shared__ __attribute__((aligned(16))) uint32_t lds[2][DRLGX_MT_STRIDE];
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kSimStreams][DRLGX_MT_STRIDE];
   extern __shared__ double dyn[];
   const int i = blockIdx.x;
   if (mode == 0)
@@ -797,15 +801,28 @@ __global__ void k_add_measurements(DRLGX_KS_PARAM, LaunchSel sel, const int32_t 
 
 }  // namespace ksim
 
+// static + dynamic LDS of one workgroup of each launch below (drlgx_dev.h); *dyn_out: the dynamic part, which the launcher requests
+size_t drlgx_sim_launch_lds(DrlgxSimLaunch which, int LG, int n_measure, size_t *dyn_out) {
+  const size_t lg = (size_t)LG, image = (size_t)DRLGX_MT_STRIDE * sizeof(uint32_t);
+  size_t stat = ksim::kSimStreams * image, dyn = (2 * lg + 2) * sizeof(double) + lg * sizeof(int);  // nrm[2 LG + 2], inr[LG]
+  if (which == DRLGX_SIM_RESET) stat = ksim::kResetStreams * image;
+  if (which == DRLGX_SIM_STEP_OBS) dyn = (4 * lg + 2) * sizeof(double) + lg * sizeof(int);  // both measure() calls' variates
+  if (which == DRLGX_SIM_PRESIM)  // nrm[2 n_measure LG + 2], inr[LG], kslot[LG]
+    dyn = (2 * (size_t)(n_measure > 0 ? n_measure : 1) * lg + 2) * sizeof(double) + 2 * lg * sizeof(int);
+  if (dyn_out) *dyn_out = dyn;
+  return stat + dyn;
+}
 size_t drlgx_simlog_entry_bytes(const DrlgxState &S) { return ((size_t)ksim::kLogHdr + (size_t)ksim::kLogRec * S.LG + 31) & ~(size_t)31; }
 void drlgx_launch_presim(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride, int n_measure, int a_end,
                          unsigned char *simlog, size_t simlog_roll, int simlog_act) {
-  const size_t dyn = (size_t)(2 * (n_measure > 0 ? n_measure : 1) * S.LG + 2) * sizeof(double) + (size_t)2 * S.LG * sizeof(int);
+  size_t dyn;
+  drlgx_sim_launch_lds(DRLGX_SIM_PRESIM, S.LG, n_measure, &dyn);
   hipLaunchKernelGGL(ksim::k_presim, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, odom_stride, n_measure, a_end, simlog, simlog_roll, simlog_act);
 }
 void drlgx_launch_sim_stage(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int mode, int32_t *keys,
                             double *br, int32_t *count) {
-  const size_t dyn = (size_t)(2 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
+  size_t dyn;
+  drlgx_sim_launch_lds(DRLGX_SIM_STAGE, S.LG, 1, &dyn);
   hipLaunchKernelGGL(ksim::k_sim_stage, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, mode, keys, br, count);
 }
 void drlgx_launch_add_measurements(const DrlgxState &S, hipStream_t st, LaunchSel sel, const int32_t *keys, const double *br,
@@ -814,15 +831,18 @@ void drlgx_launch_add_measurements(const DrlgxState &S, hipStream_t st, LaunchSe
 }
 void drlgx_launch_reset(const DrlgxState &S, hipStream_t st, int n, const int32_t *env_ids_dev,
                         const uint32_t *seeds_dev, const double *start_dev, int first_measure) {
-  const size_t dyn = (size_t)(2 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
+  size_t dyn;
+  drlgx_sim_launch_lds(DRLGX_SIM_RESET, S.LG, 1, &dyn);
   hipLaunchKernelGGL(ksim::k_reset, dim3(n), dim3(64), dyn, st, DRLGX_KS_ARG(S), first_measure, env_ids_dev, seeds_dev, start_dev);
 }
 void drlgx_launch_sim(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride,
                       int n_measure) {
-  const size_t dyn = (size_t)(2 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
+  size_t dyn;
+  drlgx_sim_launch_lds(DRLGX_SIM_STEP, S.LG, 1, &dyn);
   hipLaunchKernelGGL(ksim::k_sim_step, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, odom_stride, n_measure);
 }
 void drlgx_launch_sim_obs(const DrlgxState &S, hipStream_t st, LaunchSel sel, const double *odom, int odom_stride) {
-  const size_t dyn = (size_t)(4 * S.LG + 2) * sizeof(double) + (size_t)S.LG * sizeof(int);
+  size_t dyn;
+  drlgx_sim_launch_lds(DRLGX_SIM_STEP_OBS, S.LG, 1, &dyn);
   hipLaunchKernelGGL(ksim::k_sim_step_obs, dim3(sel.n), dim3(64), dyn, st, DRLGX_KS_ARG(S), sel, odom, odom_stride);
 }

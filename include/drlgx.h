@@ -54,7 +54,10 @@ typedef struct drlgx_config {
   int32_t num_samples; /* only 1 is supported (the shipped value); >1 re-averages identical maps */
   /* [Simulator] */
   double sigma_x0, sigma_y0, sigma_theta0;
-  int32_t num_landmarks; /* Simulator.num: ground-truth landmarks sampled per env */
+  int32_t num_landmarks; /* Simulator.num: ground-truth landmarks sampled per env.  The simulator kernels keep 20 B of LDS per
+                          * landmark (24 B in the look-ahead's pre-simulation) beside 5 024 - 7 528 B, within 64 KB:
+                          * drlgx_create refuses (DRLGX_E_INVALID) more than 2 900, with n_rollouts > 0 more than 2 521;
+                          * drlgx_set_env_obstacles(1) needs 36 B per landmark and refuses more than 1 680 */
   /* [Planner]  EMPlanner2D::Parameter (include/em_exploration/Planner2D.h; src/Planner2D.cpp:26-41) */
   double angle_weight, distance_weight0, distance_weight1, occupancy_threshold, max_edge_length;
   int32_t algorithm; /* DRLGX_ALG_* */
@@ -145,7 +148,9 @@ int drlgx_step_plans_traced(drlgx_engine *e, const double *actions_dev, int32_t 
  * without the opt-in.  Under the opt-in the step runs as the three stage kernels (timers 0-2, not 5), drlgx_step_plans as one
  * drlgx_step_plan per action index.  Look-ahead rollouts (drlgx_lookahead, drlgx_em_cost ...) have no obstacle logic
  * (Planner2D.cpp:1432-1460) and neither read nor write the flags.  Off, or with cfg.safe_distance <= 0: nothing changes, the flags
- * keep their last values. */
+ * keep their last values.  DRLGX_E_CAPACITY (the opt-in stays off, plain steps go on as before): enabled != 0 on an engine with more
+ * than 1 680 listed landmarks - the flag's simulator stage keeps both measure() calls' variates in LDS, 36 num_landmarks + 5 024 B,
+ * and its launch stays within 64 KB. */
 int drlgx_set_env_obstacles(drlgx_engine *e, int enabled);
 /* out_dev: DEVICE uint8 [2][n_envs] - plane 0 the last step's obstacle flag, plane 1 cleared. */
 int drlgx_obstacle_flags(drlgx_engine *e, uint8_t *out_dev);
