@@ -100,6 +100,8 @@ struct DrlgxState {
   //   jc[inst][row][jc_ld]: rows 3 i + r = pose i, 3 P_max + 2 j + e = landmark j; columns 0..2 = the current (newest) pose,
   //   3 + 2 j + e = landmark j.  jd[inst][P_max][6]: pose marginal covariance (xx yx yy tx ty tt).
   //   jc_meta[inst][4] = {valid, P, L, M at the update that left the panel}.  inc_stats[2] = {incremental, full} updates.
+  //   valid = 1 | kPanelInSrc: the header and jd are this instance's, the body still lies in the snapshot instance a lazy restore
+  //   copied from (LaunchSel::vm_from); the belief step reads it there and stores here, everyone else settles first.
   double *jc;
   size_t jc_stride;
   int jc_ld;
@@ -170,6 +172,32 @@ __device__ __forceinline__ int drlgx_tid() {
   return t;
 }
 
+// bit of jc_meta[inst][0] beside the valid flag: the panel's body is still in the instance a lazy restore copied from
+constexpr int kPanelInSrc = (int)0x80000000u;
+
+// The live body (3 P + 2 L rows x 3 + 2 L columns) of the covariance panel of instance s -> d by kNT threads, as share `part` of
+// `nparts`: every nparts-th group of kNT / 32 rows, 32 threads x 16 bytes per row, four rows' loads in flight per thread.
+template <int kNT>
+__device__ __forceinline__ void drlgx_copy_panel_body(const double *jc, size_t jc_stride, int jc_ld, int P_max, int s, int d, int P, int L,
+                                                      int part, int nparts, int tid) {
+  const double *ps = jc + (size_t)s * jc_stride;
+  double *pd = const_cast<double *>(jc) + (size_t)d * jc_stride;
+  const int npair = (3 + 2 * L + 1) >> 1, rows = 3 * P + 2 * L;
+  const int cp0 = tid & 31, r0 = (tid >> 5) + (kNT / 32) * part, rs = (kNT / 32) * nparts;
+  auto roff = [&](int q) -> size_t { return (size_t)(q < 3 * P ? q : q - 3 * P + 3 * P_max) * jc_ld; };
+  for (int cp = cp0; cp < npair; cp += 32)
+    for (int q = r0; q < rows; q += 4 * rs) {
+      const int q1 = q + rs, q2 = q + 2 * rs, q3 = q + 3 * rs;
+      const size_t o0 = roff(q), o1 = roff(min(q1, rows - 1)), o2 = roff(min(q2, rows - 1)), o3 = roff(min(q3, rows - 1));
+      const double2 v0 = reinterpret_cast<const double2 *>(ps + o0)[cp], v1 = reinterpret_cast<const double2 *>(ps + o1)[cp];
+      const double2 v2 = reinterpret_cast<const double2 *>(ps + o2)[cp], v3 = reinterpret_cast<const double2 *>(ps + o3)[cp];
+      reinterpret_cast<double2 *>(pd + o0)[cp] = v0;
+      if (q1 < rows) reinterpret_cast<double2 *>(pd + o1)[cp] = v1;
+      if (q2 < rows) reinterpret_cast<double2 *>(pd + o2)[cp] = v2;
+      if (q3 < rows) reinterpret_cast<double2 *>(pd + o3)[cp] = v3;
+    }
+}
+
 struct LaunchSel {
   int base;                // first instance
   int n;                   // number of instances (= grid size)
@@ -197,7 +225,9 @@ struct LaunchSel {
   // >= 0: a lazy restore (drlgx_restore) left the virtual-map planes of instance base + i in instance vm_from + i (its
   // snapshot).  The map stage rebuilds every cell of an accepted move without reading them; where it does not rebuild (an
   // instance switched off, a rejected move, a capacity error) it copies them over, so that after the launch every selected
-  // instance holds its planes again.
+  // instance holds its planes again.  The same holds for the body of a covariance panel whose header carries kPanelInSrc:
+  // the incremental update reads it from instance vm_from + i and stores into base + i (k_inc.hip); every path that does not
+  // rewrite the whole panel copies it first (kslam::inc_settle).
   int vm_from = -1;
   __host__ __device__ __forceinline__ int cap(int P_max) const { return pcap > 0 && pcap < P_max ? pcap : P_max; }
   __device__ __forceinline__ bool map_on(int i) const {
@@ -727,7 +757,8 @@ void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t s
                        const int32_t *dst, int src_off, int dst_off, int skip_mask,  // skip fields with cls & mask
                        const int *cnt = nullptr,  // S.cnt: copy the live part of per-pose / -landmark / -factor fields only
                        const DrlgxState *panel = nullptr,  // &S: the same launch copies the instances' covariance panels too
-                       int only_cls = -1);  // >= 0: the fields of this class only (a class-0 field cannot be skipped by the mask)
+                       int only_cls = -1,  // >= 0: the fields of this class only (a class-0 field cannot be skipped by the mask)
+                       int panel_mode = 1);  // 1: whole panels; 2: a lazy restore leaves valid bodies behind; 3: those bodies (k_misc.hip)
 void drlgx_launch_rebase(const DrlgxState &S, hipStream_t st, int base0, int n);
 // head of a packed status read: the status word + n_envs pose counts, rounded up to 16 bytes (k_fetch_pack)
 inline size_t drlgx_fetch_head_bytes(int n_envs) { return ((size_t)(n_envs + 1) * sizeof(int) + 15) & ~(size_t)15; }

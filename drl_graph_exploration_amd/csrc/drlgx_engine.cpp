@@ -119,8 +119,9 @@ struct drlgx_engine {
   std::vector<double> dub_end_h, dub_v_h, dub_w_h;  // end: x y theta per entry
   std::vector<int> dub_steps_h;
   // Lazy restore: drlgx_restore leaves the virtual-map planes (field class 1) in the snapshot - the next belief step rebuilds
-  // every cell of them without reading them (LaunchSel::vm_from) - and records the slot here (-1: every env holds its own).
-  // Any other entry point settles the debt first (settle: one copy of the planes).  DRLGX_RESTORE_EAGER=1: the full copy.
+  // every cell of them without reading them (LaunchSel::vm_from) - and the bodies of the valid covariance panels, which that step
+  // reads there and stores into the env (kPanelInSrc in the panel's header); it records the slot here (-1: every env holds its own).
+  // Any other entry point settles the debt first (settle: one copy of planes and bodies).  DRLGX_RESTORE_EAGER=1: the full copy.
   int owed_slot = -1;
   bool restore_eager = false;
 };
@@ -271,7 +272,7 @@ static void read_env_switches(drlgx_engine *e) {
   e->spin_sync = env_flag("DRLGX_SYNC_SPIN", true);
   e->la_presim = env_flag("DRLGX_LOOKAHEAD_PRESIM", true);  // 0: every rollout action simulates inside its belief step (the A/B of the parity test)
   e->la_loop = env_flag("DRLGX_LOOKAHEAD_LOOP", true);  // 0: one launch per action index (the A/B of the look-ahead tests)
-  e->restore_eager = env_flag("DRLGX_RESTORE_EAGER", false);  // 1: a restore copies the virtual-map planes too (the A/B of the lazy restore)
+  e->restore_eager = env_flag("DRLGX_RESTORE_EAGER", false);  // 1: a restore copies the virtual-map planes and panel bodies too (the A/B of the lazy restore)
 }
 
 static double p2l(double p) { return std::log(p / (1.0 - p)); }
@@ -659,11 +660,11 @@ static void state_sync(drlgx_engine *e) {
 // snapshot instance of env 0 in slot `slot`
 static int snapshot_base(const drlgx_engine *e, int slot) { return 2 * e->S.n_envs + e->S.n_roll + slot * e->S.n_envs; }
 
-// what a lazy restore still owes: the planes of every env from the restored slot, in one copy
+// what a lazy restore still owes: the planes and the marked covariance panel bodies of every env from the restored slot, in one copy
 static void settle(drlgx_engine *e) {
   if (e->owed_slot < 0) return;
   drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, e->S.n_envs, nullptr, nullptr, snapshot_base(e, e->owed_slot), 0, 0,
-                    nullptr, nullptr, 1);
+                    nullptr, &e->S, 1, 3);
   e->owed_slot = -1;
 }
 
@@ -844,7 +845,8 @@ int drlgx_step(drlgx_engine *e, const double *odom_dev, const uint8_t *active_de
   DRLGX_ENTER_OWING(e);
   if (!e || !odom_dev) return DRLGX_E_INVALID;
   LaunchSel sel{0, e->S.n_envs, active_dev, nullptr, 0};
-  // every form of the step runs the map stage (kmap::map_body) for every env: it takes over what a lazy restore owes
+  // every form of the step runs the map stage (kmap::map_body) and the SLAM stage's head (kslam::inc_settle or the fused step's own)
+  // for every env: they take over what a lazy restore owes
   if (e->owed_slot >= 0) sel.vm_from = snapshot_base(e, e->owed_slot);
   e->owed_slot = -1;
   const int pb = std::min(max_bound(e) + 1, e->S.P_max);
@@ -1914,9 +1916,10 @@ int drlgx_restore(drlgx_engine *e, int slot) {
   const DrlgxState &S = e->S;
   ScopedTimer t(e, 3);
   // lazy: everything but the virtual-map planes (43 % of an instance's live bytes at the bench state), which the next belief step
-  // rebuilds without reading them - or settle() copies before anything else touches the envs
+  // rebuilds without reading them, and the bodies of the valid covariance panels, which it reads where they are - or settle() copies
+  // both before anything else touches the envs
   drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, snapshot_base(e, slot), 0,
-                    e->restore_eager ? 0 : 1, e->S.cnt, &S);
+                    e->restore_eager ? 0 : 1, e->S.cnt, &S, -1, e->restore_eager ? 1 : 2);
   e->owed_slot = e->restore_eager ? -1 : slot;
   e->pbound = e->snap_pbound[slot];
   return check_launch(e);
@@ -1957,6 +1960,31 @@ int drlgx_inc_stats_host(drlgx_engine *e, int64_t out[2], int reset) {
   HIPCHK(e, hipStreamSynchronize(e->stream));
   out[0] = (int64_t)v[0];
   out[1] = (int64_t)v[1];
+  return DRLGX_OK;
+}
+
+// ---- development aid: the covariance panel of one instance (env, look-ahead copy or snapshot) --------------------
+int drlgx_debug_panel_host(drlgx_engine *e, int inst, int32_t meta[4], double *panel, size_t panel_cap) {
+  DRLGX_ENTER(e);  // (reads a panel: whatever a lazy restore owes is settled first)
+  if (!INST_OK(e, inst) || !meta) return DRLGX_E_INVALID;
+  const DrlgxState &S = e->S;
+  meta[0] = meta[1] = meta[2] = meta[3] = 0;
+  if (!S.jc) return DRLGX_OK;
+  int r = fetch(e, meta, S.jc_meta + (size_t)inst * 4, 4 * sizeof(int32_t));
+  if (r) return r;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (!panel || meta[0] != 1) return DRLGX_OK;
+  const int P = meta[1], L = meta[2];
+  if (P < 0 || P > S.P_max || L < 0 || L > S.L_max) return DRLGX_E_INVALID;
+  const size_t cols = 3 + 2 * (size_t)L, rows = 3 * (size_t)P + 2 * (size_t)L;
+  if (rows * cols > panel_cap) return DRLGX_E_INVALID;
+  const double *src = S.jc + (size_t)inst * S.jc_stride;
+  // the pose rows, then the landmark rows (which start at row 3 P_max of the instance's panel)
+  if (P > 0) HIPCHK(e, hipMemcpy2DAsync(panel, cols * 8, src, (size_t)S.jc_ld * 8, cols * 8, 3 * (size_t)P, hipMemcpyDeviceToHost, e->stream));
+  if (L > 0)
+    HIPCHK(e, hipMemcpy2DAsync(panel + 3 * (size_t)P * cols, cols * 8, src + 3 * (size_t)S.P_max * S.jc_ld, (size_t)S.jc_ld * 8, cols * 8,
+                               2 * (size_t)L, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   return DRLGX_OK;
 }
 

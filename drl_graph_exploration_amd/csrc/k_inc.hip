@@ -197,8 +197,13 @@ __device__ __forceinline__ bool inc_plan(const DrlgxState &S, int inst, int P, i
 // pose's theta is then formed from the commanded odometry with the expressions the simulator evaluates (as SlamCtx::front).
 // kLds: the panel is staged in LDS (two instantiations rather than one body on generic pointers: flat accesses count on both
 // memory counters, so every LDS read waited for all panel loads in flight).
+// src_panel (or null): the panel of the snapshot instance that still holds this one's body (kPanelInSrc, LaunchSel::vm_from).  Loads
+// of what this update has not stored yet go there, every store goes to the instance's own panel: staged in LDS, the stage-in reads it
+// and inc_post's write-back stores every live row; in place, this half leaves columns 0 .. 2 and the new pose's rows in the
+// instance and inc_post goes on from there.  A second base pointer in the global address space, uniform over the workgroup.
 template <bool kLds, bool kSub>
-__device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, int tid, const double *odom3, SubBarrier sb) {
+__device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, int tid, const double *odom3, SubBarrier sb,
+                                        const double *src_panel = nullptr) {
   const int ft = kSub ? tid - 64 : tid, fn = kSub ? kThreads - 64 : kThreads, lane = tid & 63;
   auto bar = [&]() {
     if constexpr (kSub) sb.sync(lane);
@@ -206,7 +211,9 @@ __device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, in
   };
   const int inst = x.inst, P = x.P, pn = x.pn, pp = x.pp, L0 = x.L0, n1 = x.n1, a0 = x.a0;
   double *gpan = S.jc + (size_t)inst * S.jc_stride;
+  const double *span = src_panel ? src_panel : gpan;
   auto growp = [&](int q) -> double * { return gpan + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld; };
+  auto srowp = [&](int q) -> const double * { return span + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld; };
   auto rowp = [&](int q) -> double * {
     if constexpr (kLds) return x.cwl + (size_t)q * x.ldw;
     else return gpan + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld;
@@ -257,7 +264,7 @@ __device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, in
       for (int qq = r0; qq < nr; qq += 4 * rs) {
         // (clamped row indices: the loads are unconditional, the stores are not)
         const int q0 = qq, q1 = qq + rs, q2 = qq + 2 * rs, q3 = qq + 3 * rs;
-        auto src = [&](int q) { const int c = min(q, nr - 1); return reinterpret_cast<const double2 *>(growp(c < 3 * pn ? c : c + 3))[cp]; };
+        auto src = [&](int q) { const int c = min(q, nr - 1); return reinterpret_cast<const double2 *>(srowp(c < 3 * pn ? c : c + 3))[cp]; };
         const double2 v0 = src(q0), v1 = src(q1), v2 = src(q2), v3 = src(q3);
         auto dst = [&](int q, const double2 &v) { if (q < nr) reinterpret_cast<double2 *>(rowp(q < 3 * pn ? q : q + 3))[cp] = v; };
         dst(q0, v0); dst(q1, v1); dst(q2, v2); dst(q3, v3);
@@ -276,7 +283,9 @@ __device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, in
     for (int qq = ft; qq < n1 - 3; qq += fn) {
       const int q = qq < 3 * pn ? qq : qq + 3;
       double *r = rowp(q);
-      const double t0 = r[0], t1 = r[1], t2 = r[2];
+      const double *rs = r;
+      if constexpr (!kLds) rs = srowp(q);
+      const double t0 = rs[0], t1 = rs[1], t2 = rs[2];
       r[0] = f00 * t0 + f01 * t1 + f02 * t2;
       r[1] = f10 * t0 + f11 * t1 + f12 * t2;
       r[2] = f20 * t0 + f21 * t1 + f22 * t2;
@@ -285,7 +294,12 @@ __device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, in
   bar();
   for (int e = ft; e < 3 * a0; e += fn) {
     const int r = e / a0, c = e - r * a0;
-    double v = fq[3 * r] * rowp(3 * pp)[c] + fq[3 * r + 1] * rowp(3 * pp + 1)[c] + fq[3 * r + 2] * rowp(3 * pp + 2)[c];
+    // (in place: the three columns the loop above stored are the instance's, the others still the source's)
+    auto prev = [&](int k) -> double {
+      if constexpr (kLds) return rowp(3 * pp + k)[c];
+      else return (c < 3 ? rowp(3 * pp + k) : srowp(3 * pp + k))[c];
+    };
+    double v = fq[3 * r] * prev(0) + fq[3 * r + 1] * prev(1) + fq[3 * r + 2] * prev(2);
     if (c == r) v += 1.0 / (c < 2 ? S.w_trans : S.w_rot);  // Q = J2^T W^-1 J2 = diag(sigma_t^2, sigma_t^2, sigma_r^2)
     rowp(3 * pn + r)[c] = v;
   }
@@ -300,9 +314,12 @@ __device__ __forceinline__ void inc_pre(const DrlgxState &S, const IncCtx &x, in
 // (the HBM panel, if inc_pre already moved it, is marked invalid); uniform over the workgroup.
 // hand (k_step; or null): LDS that receives what the map stage reads next - est_pose [P][4] and, at hand + 4 hand_cap,
 // pose_info [P][6] (as SlamCtx::back leaves them) - and the landmark estimates are left in x.thl for the same reason.
+// src_panel (or null; never with the streamed form): as inc_pre.  In place, columns 0 .. 2 and the new pose's rows are the
+// instance's by now; every other entry is read from the source until the first batch's tile pass has stored it - that pass stores
+// every (row tile, column pair) of the live extent, so a second batch and everything behind the batches read the instance only.
 template <bool kLds, int kSNT = ISNT>
 __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, int L, int M, const SimBox &box, int tid,
-                                         double *hand = nullptr, int hand_cap = 0) {
+                                         double *hand = nullptr, int hand_cap = 0, const double *src_panel = nullptr) {
   const int lane = tid & 63, wave = tid >> 6, lc = lane & 15, lr = lane >> 4;
   const int inst = x.inst, P = x.P, pn = x.pn, L0 = x.L0, M0 = x.M0, n1 = x.n1, n1p = x.n1p, a0 = x.a0;
   int *meta = inc_meta(S, inst);
@@ -311,10 +328,16 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
   int *fre = x.fre, *fnew = x.fnew, *fslot = x.fslot, *ictl = x.ictl;
   double *recs = x.recs, *gs = x.gs, *vvec = x.vvec, *wks = x.wks, *thp = x.thp, *thl = x.thl, *dl = x.dl, *Dl = x.Dl, *Y = x.Y;
   double *gpan = S.jc + (size_t)inst * S.jc_stride;
+  const double *span = (!kLds && src_panel) ? src_panel : gpan;  // (set to gpan once the instance holds every entry)
   auto growp = [&](int q) -> double * { return gpan + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld; };
   auto rowp = [&](int q) -> double * {
     if constexpr (kLds) return x.cwl + (size_t)q * x.ldw;
     else return gpan + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld;
+  };
+  // row q where its columns >= 3 are read: the new pose's rows are the instance's from the start
+  auto srowp = [&](int q) -> const double * {
+    if constexpr (kLds) return x.cwl + (size_t)q * x.ldw;
+    else return ((q >= 3 * pn && q < 3 * P) ? gpan : span) + (size_t)(q < 3 * P ? q : q + 3 * (S.P_max - P)) * S.jc_ld;
   };
   int *cnt = S.cnt + (size_t)inst * DRLGX_CNT_STRIDE;
   double *d_pose = S.d_pose + (size_t)inst * S.P_max * 3;
@@ -382,8 +405,9 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
         double c0[4], c1[4], c2[4], l0[4], l1[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const double *r = rowp(min(q0 + u * RS, n1 - 1));
-          c0[u] = r[0]; c1[u] = r[1]; c2[u] = r[2]; l0[u] = r[cl]; l1[u] = r[cl + 1];
+          const int qc = min(q0 + u * RS, n1 - 1);
+          const double *r = rowp(qc), *rs = srowp(qc);
+          c0[u] = r[0]; c1[u] = r[1]; c2[u] = r[2]; l0[u] = rs[cl]; l1[u] = rs[cl + 1];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -501,9 +525,11 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
         const int it = e / npr, pr = e - it * npr, I = wave + kWaves * it;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const double *rw = rowp(16 * I + lr + 4 * r) + 32 * pr + lc;
-          c0[r] = rw[0];
-          c1[r] = rw[16];
+          // (only the first tile of column pair 0 has lanes on the columns 0 .. 2)
+          const int q = 16 * I + lr + 4 * r, c = 32 * pr + lc;
+          const double *rs = srowp(q);
+          c0[r] = (c < 3 ? rowp(q) : rs)[c];
+          c1[r] = rs[c + 16];
         }
       };
       auto unit = [&](int e, v4d &acc0, v4d &acc1) {
@@ -940,6 +966,17 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
         batch(b0, nb, std::false_type{});
         b0 += nb;
       }
+      span = gpan;
+    }
+    if constexpr (!kLds) {
+      if (span != gpan) {  // nothing re-observed: no tile pass has brought the other columns over
+        for (int qq = wave; qq < n1 - 3; qq += kWaves) {
+          const int q = qq < 3 * pn ? qq : qq + 3;
+          for (int c = 3 + lane; c < a0; c += 64) rowp(q)[c] = srowp(q)[c];
+        }
+        span = gpan;
+        __syncthreads();
+      }
     }
   }
   DRLGX_PROF(S, 3);
@@ -1066,6 +1103,21 @@ __device__ __forceinline__ void panel_invalidate(const DrlgxState &S, int inst, 
   }
 }
 
+// A lazy restore left the body of this workgroup's panel in instance sel.vm_from + bi (kPanelInSrc) and nothing in this launch reads
+// it through a second base pointer (only the fused dense step does: k_step.hip): bring it over and clear the mark.  Every thread of
+// the workgroup calls it, before anything reads or writes the panel - also for an instance the launch leaves alone.
+__device__ __forceinline__ void inc_settle(const DrlgxState &S, const LaunchSel &sel) {
+  if (!S.jc || sel.vm_from < 0) return;
+  const int tid = drlgx_tid(), bi = drlgx_bid();
+  int *meta = inc_meta(S, sel.base + bi);
+  const int m0 = meta[0];
+  if (!(m0 & kPanelInSrc)) return;
+  drlgx_copy_panel_body<kThreads>(S.jc, S.jc_stride, S.jc_ld, S.P_max, sel.vm_from + bi, sel.base + bi, meta[1], meta[2], 0, 1, tid);
+  __syncthreads();
+  if (tid == 0) meta[0] = m0 & ~kPanelInSrc;
+  __syncthreads();
+}
+
 #pragma clang fp contract(fast)
 
 // The incremental update as a stage (k_slam / k_slam_arrow / k_step_arrow, after the simulator): true when it served the
@@ -1073,6 +1125,7 @@ __device__ __forceinline__ void panel_invalidate(const DrlgxState &S, int inst, 
 template <int kSNT>
 __device__ __forceinline__ bool inc_stage(const DrlgxState &S, const LaunchSel &sel, int lds_bytes, size_t smem_off) {
   const int tid = drlgx_tid(), bi = drlgx_bid();
+  inc_settle(S, sel);  // (the streamed form and the solvers behind this stage know one panel base only)
   if (!S.jc || !sel.on(bi)) return false;
   const int inst = sel.base + bi;
   const int *cnt = S.cnt + (size_t)inst * DRLGX_CNT_STRIDE;

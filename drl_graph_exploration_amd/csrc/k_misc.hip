@@ -12,36 +12,28 @@ namespace {
 // flight per thread.  (Eight parts since the lazy restore leaves the virtual-map planes to the step: the panels are then two thirds
 // of a restore's bytes - 11.9 against 12.3 us per restore with four parts, 13.2 with sixteen; profiles/lazy_restore_ab.txt)
 constexpr int kCopySplit = 8;
-__device__ __forceinline__ void copy_panel_part(const DrlgxState &S, int s, int d, int part) {
+// mode 1: header, jd and body.  mode 2 (a lazy restore): a valid panel's body stays in s - the header says so (kPanelInSrc) and the
+// belief step that follows reads it there (k_inc.hip).  mode 3 (settling that debt): the bodies mode 2 left behind, and the header's
+// valid word without the mark; s is a snapshot instance, which nothing writes, so its header still says which bodies those are.
+__device__ __forceinline__ void copy_panel_part(const DrlgxState &S, int s, int d, int part, int mode) {
   const int *ms = S.jc_meta + (size_t)s * 4;
   int *md = S.jc_meta + (size_t)d * 4;
-  const int valid = ms[0], P = ms[1], L = ms[2], M = ms[3];
+  const int valid = ms[0] & ~kPanelInSrc, P = ms[1], L = ms[2], M = ms[3];
   if (threadIdx.x == 0 && part == 0) {
-    md[0] = valid; md[1] = P; md[2] = L; md[3] = M;
+    if (mode != 3) {
+      md[0] = (mode == 2 && valid == 1) ? (valid | kPanelInSrc) : valid; md[1] = P; md[2] = L; md[3] = M;
+    } else if (valid == 1) {
+      md[0] = valid;
+    }
   }
   if (valid != 1) return;
-  const double *ps = S.jc + (size_t)s * S.jc_stride;
-  double *pd = S.jc + (size_t)d * S.jc_stride;
-  const int npair = (3 + 2 * L + 1) >> 1, rows = 3 * P + 2 * L;
-  const int cp0 = threadIdx.x & 31, r0 = (threadIdx.x >> 5) + 8 * part, rs = 8 * kCopySplit;
-  auto roff = [&](int q) -> size_t { return (size_t)(q < 3 * P ? q : q - 3 * P + 3 * S.P_max) * S.jc_ld; };
-  for (int cp = cp0; cp < npair; cp += 32)
-    for (int q = r0; q < rows; q += 4 * rs) {
-      const int q1 = q + rs, q2 = q + 2 * rs, q3 = q + 3 * rs;
-      const size_t o0 = roff(q), o1 = roff(min(q1, rows - 1)), o2 = roff(min(q2, rows - 1)), o3 = roff(min(q3, rows - 1));
-      const double2 v0 = reinterpret_cast<const double2 *>(ps + o0)[cp], v1 = reinterpret_cast<const double2 *>(ps + o1)[cp];
-      const double2 v2 = reinterpret_cast<const double2 *>(ps + o2)[cp], v3 = reinterpret_cast<const double2 *>(ps + o3)[cp];
-      reinterpret_cast<double2 *>(pd + o0)[cp] = v0;
-      if (q1 < rows) reinterpret_cast<double2 *>(pd + o1)[cp] = v1;
-      if (q2 < rows) reinterpret_cast<double2 *>(pd + o2)[cp] = v2;
-      if (q3 < rows) reinterpret_cast<double2 *>(pd + o3)[cp] = v3;
-    }
-  if (part == 0)
+  if (mode != 2) drlgx_copy_panel_body<256>(S.jc, S.jc_stride, S.jc_ld, S.P_max, s, d, P, L, part, kCopySplit, threadIdx.x);
+  if (part == 0 && mode != 3)
     for (int e = threadIdx.x; e < 6 * P; e += 256) S.jd[(size_t)d * S.P_max * 6 + e] = S.jd[(size_t)s * S.P_max * 6 + e];
 }
 
 // copy every field of instance src[i] to dst[i] whose class is not in skip_mask (and is only_cls, if that is >= 0) and - panel
-// != 0 - its covariance panel: one launch for everything an instance copy (snapshot / restore, env -> base -> rollout) moves
+// != 0: copy_panel_part's mode - its covariance panel: one launch for everything an instance copy (snapshot / restore, env -> base -> rollout) moves
 __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields, int n_fields, const int32_t *src,
                                                         const int32_t *dst, int src_off, int dst_off, int skip_mask, int only_cls,
                                                         const int *cnt, DrlgxState S, int panel) {
@@ -55,7 +47,7 @@ __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields
   const int f = blockIdx.x;
   const int s = (src ? src[i] : i) + src_off, d = (dst ? dst[i] : i) + dst_off;
   if (f >= n_fields) {
-    if (panel) copy_panel_part(S, s, d, f - n_fields);
+    if (panel) copy_panel_part(S, s, d, f - n_fields, panel);
     return;
   }
   // (one workgroup for ALL the fields of a few bytes per instance was measured: 21.4 against 17.8 us - seven dependent round trips)
@@ -484,12 +476,12 @@ void drlgx_launch_cov_array(const DrlgxState &S, hipStream_t st, double *length,
 }
 void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t st, int n, const int32_t *src,
                        const int32_t *dst, int src_off, int dst_off, int skip_mask, const int *cnt, const DrlgxState *panel,
-                       int only_cls) {
+                       int only_cls, int panel_mode) {
   if (n <= 0) return;
   const bool with_panel = panel && panel->jc;
   const dim3 cgrid(n_fields + (with_panel ? kCopySplit : 0), n);
   hipLaunchKernelGGL(k_copy_instances, cgrid, dim3(256), 0, st, fields_dev, n_fields, src, dst,
-                     src_off, dst_off, skip_mask, only_cls, cnt, with_panel ? *panel : DrlgxState{}, with_panel ? 1 : 0);
+                     src_off, dst_off, skip_mask, only_cls, cnt, with_panel ? *panel : DrlgxState{}, with_panel ? panel_mode : 0);
 }
 void drlgx_launch_fetch_pack(const DrlgxState &S, hipStream_t st, const void *src, size_t bytes, void *out) {
   const size_t head = drlgx_fetch_head_bytes(S.n_envs);

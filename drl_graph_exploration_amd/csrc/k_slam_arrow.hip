@@ -1155,6 +1155,7 @@ __device__ __forceinline__ void arrow_body(const DrlgxState &S, const LaunchSel 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int tid = drlgx_tid();
   const int bi = drlgx_bid();
+  inc_settle(S, sel);  // (a panel body a lazy restore left in the snapshot: also of an instance this launch leaves alone)
   if (!sel.on(bi)) return;
   if (S.prof && tid == 0 && bi < 448) S.prof[128 + 2 * bi] = wall_clock64();  // (dev aid: per-workgroup start / end, as k_step)
   if (inc_stage<ISNT>(S, sel, lds_bytes, 0)) {  // between relinearisations: the rank-k covariance update (k_inc.hip)

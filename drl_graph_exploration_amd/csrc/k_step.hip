@@ -57,6 +57,8 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
   bool pre = false, accepted = false, inc_try = false;
   double od3[3] = {0, 0, 0};
   int P0 = 0, L0 = 0, M0 = 0, isam = 0, pan_L0 = -1, pan_M0 = -1;
+  // the panel of the snapshot instance that still holds this instance's body after a lazy restore (kPanelInSrc), else null
+  const double *pan_src = nullptr;
   // (what the simulator wave reads that does not depend on the pose count is requested with the prelude's loads: ksim::SimPre)
   ksim::SimPre spre;
   spre.have = tid < 64 && !sel.simlog && sel.on(bi);
@@ -68,7 +70,8 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     int meta0 = 0, meta1 = 0;
     if (S.jc) {
       const int4 mv = *reinterpret_cast<const int4 *>(kslam::inc_meta(S, inst));  // {valid, poses, landmarks, factors}
-      meta0 = mv.x & 0x7fffffff;
+      meta0 = mv.x & ~kPanelInSrc;
+      if ((mv.x & kPanelInSrc) && sel.vm_from >= 0) pan_src = S.jc + (size_t)(sel.vm_from + bi) * S.jc_stride;
       meta1 = mv.y;
       pan_L0 = mv.z;
       pan_M0 = mv.w;
@@ -85,6 +88,12 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     const int Lb = min(S.L_max, L0 + 48), Mb = min(S.M_max, M0 + 48);
     pre = accepted && !inc_try && (3 * (P0 + 1) + 1 + 15) / 16 <= kslam::kDenseTiles && kslam::SlamCtx::big_fits(sim_bytes, lds_bytes, P0 + 1, Lb, Mb);
     if (pre) ctx.setup<true>(S, step_smem, sim_bytes, lds_bytes, inst, P0 + 1, Lb, Mb);
+  }
+  // Only the incremental update reads a panel body where a lazy restore left it.  An instance switched off, a rejected move and every
+  // step that starts with the full solve bring it over first.
+  if (!inc_try) {
+    kslam::inc_settle(S, sel);
+    pan_src = nullptr;
   }
   if (tid == 0) {
     sub_cnt[0] = 0;
@@ -110,8 +119,8 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     bool inc_lds = false;
     if (kslam::inc_plan(S, sel.base + bi, P0 + 1, lds_bytes, sim_bytes, ix, inc_lds, pc, pan_L0, pan_M0)) {
       const kslam::SubBarrier sb{sub_cnt, kslam::kThreads / 64 - 1, 0};
-      if (inc_lds) kslam::inc_pre<true, true>(S, ix, tid, od3, sb);
-      else kslam::inc_pre<false, true>(S, ix, tid, od3, sb);
+      if (inc_lds) kslam::inc_pre<true, true>(S, ix, tid, od3, sb, pan_src);
+      else kslam::inc_pre<false, true>(S, ix, tid, od3, sb, pan_src);
     }
   }
   __syncthreads();
@@ -139,11 +148,13 @@ __device__ __forceinline__ void step_once(const DrlgxState &S, const LaunchSel &
     bool inc_lds = false;
     if (kslam::inc_plan(S, sel.base + bi, P0 + 1, lds_bytes, sim_bytes, ix, inc_lds, pc, pan_L0, pan_M0)) {
       double *hp = hand ? reinterpret_cast<double *>(step_smem) : nullptr;
-      inc_done = inc_lds ? kslam::inc_post<true, 0>(S, ix, sub_cnt[2], sub_cnt[3], box, tid, hp, pc)
-                         : kslam::inc_post<false, 0>(S, ix, sub_cnt[2], sub_cnt[3], box, tid, hp, pc);
+      inc_done = inc_lds ? kslam::inc_post<true, 0>(S, ix, sub_cnt[2], sub_cnt[3], box, tid, hp, pc, pan_src)
+                         : kslam::inc_post<false, 0>(S, ix, sub_cnt[2], sub_cnt[3], box, tid, hp, pc, pan_src);
       if (inc_done) lm_lds = ix.thl;  // (the map stage's inputs are in LDS, as after slam_finish)
       else __syncthreads();
     }
+    // (no room for the update, or inc_post refused the step with the panel staged in LDS: the header still carries the mark)
+    if (!inc_done) kslam::inc_settle(S, sel);
   }
   if (!inc_done)
     kslam::slam_finish<FT>(S, sel, lds_bytes, sim_bytes, ctx, pre, sub_cnt + 1, hand ? reinterpret_cast<double *>(step_smem) : nullptr, &lm_lds, box, pc);

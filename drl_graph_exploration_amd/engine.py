@@ -588,6 +588,22 @@ class Engine(object):
         self._chk(self.L.drlgx_inc_stats_host(self.h, out, 1 if reset else 0))
         return int(out[0]), int(out[1])
 
+    def panel(self, inst):
+        """Development aid: (meta [valid, P, L, M], the covariance panel's live extent [3 P + 2 L, 3 + 2 L] or None when it is not
+        valid) of instance `inst` - an env, a look-ahead copy or a snapshot instance (snapshot_instance)."""
+        meta = np.zeros(4, dtype=np.int32)
+        ipt, dpt = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._chk(self.L.drlgx_debug_panel_host(self.h, inst, meta.ctypes.data_as(ipt), None, 0))
+        if meta[0] != 1:
+            return meta, None
+        body = np.zeros((3 * meta[1] + 2 * meta[2], 3 + 2 * meta[2]))
+        self._chk(self.L.drlgx_debug_panel_host(self.h, inst, meta.ctypes.data_as(ipt), body.ctypes.data_as(dpt), body.size))
+        return meta, body
+
+    def snapshot_instance(self, slot, env):
+        """Instance index of env `env` in snapshot slot `slot` (the getters take any instance)."""
+        return 2 * self.n_envs + self.n_rollouts + slot * self.n_envs + env
+
     def timing_enable(self, on=True):
         """on: False / True (spans around what is launched, fused step = 'step') / 2 (per-stage kernels)."""
         self._chk(self.L.drlgx_timing_enable(self.h, int(on)))

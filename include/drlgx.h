@@ -592,6 +592,10 @@ int drlgx_debug_disc_cells_bound(double radius_cells);
  * panel memory need beyond DRLGX_INC_MAX_GB (default 32).  out[0] = updates served by the rank-k path, out[1] = full
  * solves, since creation or the last call with reset != 0; both -1 when the path is disabled. */
 int drlgx_inc_stats_host(drlgx_engine *e, int64_t out[2], int reset);
+/* Development aid: the covariance panel of instance `inst` (an env, a look-ahead copy or a snapshot instance).  meta[4] = {valid, P,
+ * L, M}; when valid == 1 and panel != NULL, panel receives the live extent, (3 P + 2 L) rows x (3 + 2 L) columns, row-major (pose
+ * rows first); panel_cap: doubles the buffer holds.  Like every getter it first settles what a lazy restore owes. */
+int drlgx_debug_panel_host(drlgx_engine *e, int inst, int32_t meta[4], double *panel, size_t panel_cap);
 
 /* ---- GCN policy (scripts/Networks.py:12-70 over PyG GCNConv(improved=True)) ------------------- */
 
