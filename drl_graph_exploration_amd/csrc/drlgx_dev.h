@@ -779,7 +779,11 @@ void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, con
 void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
                              const double *actions, const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride,
                              double *scratch, size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride,
-                             int32_t *n_out);
+                             int32_t *n_out, double *lm_out = nullptr, int lm_stride = 0);
+// lm_out ([nc][lm_stride][3], or null = the kernel without them): the landmarks' updated 2x2 blocks (xx, xy, yy per slot) as well.
+// drlgx_launch_fm2_prior_ordered: drlgx_launch_fm2_prior for every environment with a fixed summation order (no atomics) - the same
+// belief gives the same bits (drlgx_slam_og_cost).
+void drlgx_launch_fm2_prior_ordered(const DrlgxState &S, hipStream_t st, double *sig, size_t sig_stride, int n_max);
 // Leaf evaluation of candidate plans (k_em.hip): nc candidates, one workgroup each; cov = what drlgx_launch_fm2_update left for the
 // same nc candidates ([nc][cov_stride][9]); the candidate arrays and the outputs (any of them null) start at the first of them.
 // core ([nc][max_actions] or null): only the core steps enter the leaf's map; distance ([nc] or null): the leaf's distance instead
@@ -794,7 +798,15 @@ void drlgx_launch_em_cost(const DrlgxState &S, hipStream_t st, int nc, const int
 size_t drlgx_og_lds_bytes(const DrlgxState &S);
 void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const int32_t *n_actions, int *flag);
 void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
-                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out);
+                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out, double *dist_out = nullptr);
+// dist_out ([nc][2] or null): the plan's distance and the distance weight, the factors of the cost's second term.
+// The SLAM-OG-Shannon cost (k_og.hip): the root's weights [n_envs][2] = w1, w2 from the live belief; then, per candidate, the blend of
+// the entropy that drlgx_launch_og_cost left (h_leaf [nc], dist [nc][2]) with sum_l sqrt(det) of the landmark blocks that
+// drlgx_launch_fm2_update left (lm_cov [nc][lm_stride][3]); distance ([nc] or null): the caller's distance instead of the plan's own.
+void drlgx_launch_slam_og_weights(const DrlgxState &S, hipStream_t st, double alpha, double *weights);
+void drlgx_launch_slam_og_blend(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *lm_cov, int lm_stride,
+                                const double *h_leaf, const double *dist, const double *distance, const double *weights, double *unc_out,
+                                double *cost_out, double *terms_out);
 // The EM planner's tree sampler (k_em_tree.hip): one tree per selected environment, grown from its live belief, which is only read.
 // The Dubins path library (drlgx_set_dubins_library_host) on the device, SoA in library order.  max_steps: the largest num_steps
 // (the bound of the step loops); reach: (the largest |end| + tol)(1 + 2^-30), beyond which no entry can match (+inf: never skip a

@@ -88,6 +88,10 @@ struct drlgx_engine {
   int32_t *em_nout = nullptr;
   int *em_flag = nullptr;
   int *og_flag = nullptr;  // drlgx_og_cost's argument check (allocated on first use)
+  // drlgx_slam_og_cost (allocated on first use / grown on demand): the root weights [n_envs][2], one chunk's landmark blocks
+  // [kFm2Chunk][L_max][3]; per candidate the leaf entropy [cap] and the cost's distance factors [cap][2]
+  double *sog_weights = nullptr, *sog_lm = nullptr, *sog_h = nullptr, *sog_dist = nullptr;
+  size_t sog_cap = 0;
   // drlgx_em_plan / drlgx_rrt_plan (grown on demand): the trees' tables (edge odometry, parent and depth, leaf list, per-tree
   // results), the leaves as candidates of drlgx_em_cost with their costs; the sampler's own planner parameters
   double *tree_act = nullptr, *tree_cand_act = nullptr, *tree_cost = nullptr;
@@ -1058,13 +1062,30 @@ int drlgx_stage_update_map(drlgx_engine *e, const uint8_t *active_dev, int rebui
   return check_launch(e);
 }
 
+// a scratch array of at least `count` elements: kept while it is large enough, replaced (behind the stream's work) when it is not
+extern "C++" {
+template <typename T>
+static int scratch_reserve(drlgx_engine *e, T **p, size_t count) {
+  if (*p) {
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void *)*p), e->allocs.end());
+    HIPCHK(e, hipFree(*p));
+    *p = nullptr;
+  }
+  return dev_alloc(e, p, count);
+}
+}
+
 // FastMarginals2::update for candidate action lists (k_fm2.hip)
 static const int kFm2Chunk = 128, kFm2MaxMeas = 256;
 // What both entries below do with their candidates: the workspaces on first use, the prior covariance of every environment, then
 // one update launch per kFm2Chunk candidates.  cov_out / n_out hold all n_cand candidates - or, chunk_out, only the chunk at hand,
-// which after(c0, nc) consumes on the engine's stream before the next chunk's launch overwrites it.
+// which after(c0, nc) consumes on the engine's stream before the next chunk's launch overwrites it.  lm_out (null: the kernels as
+// they were without it): the landmark blocks as well, [.][L_max][3], all candidates or (lm_chunk) the chunk at hand; the prior is
+// then summed in a fixed order (k_fm2_prior_ordered), so that such a call gives the same bits whenever it is repeated.
 static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                   const uint8_t *core_dev, double *cov_out, int out_stride_poses, int32_t *n_out, bool chunk_out, const std::function<void(int, int)> &after) {
+                   const uint8_t *core_dev, double *cov_out, int out_stride_poses, int32_t *n_out, bool chunk_out, const std::function<void(int, int)> &after,
+                   double *lm_out = nullptr, bool lm_chunk = false) {
   const DrlgxState &S = e->S;
   if (!e->fm2_sig) {
     const size_t nmax = (size_t)3 * S.P_max + 2 * S.L_max;
@@ -1080,14 +1101,17 @@ static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, con
     HIPCHK(e, hipMemcpyAsync(e->fm2_slot, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
   }
-  drlgx_launch_fm2_prior(S, e->stream, nullptr, S.n_envs, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
+  if (lm_out)
+    drlgx_launch_fm2_prior_ordered(S, e->stream, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
+  else
+    drlgx_launch_fm2_prior(S, e->stream, nullptr, S.n_envs, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
   for (int c0 = 0; c0 < n_cand; c0 += kFm2Chunk) {
     const int nc = std::min(kFm2Chunk, n_cand - c0);
     // (the launch's first candidate through the pointers: the kernel's own offset stays 0)
     drlgx_launch_fm2_update(S, e->stream, 0, nc, cand_env_dev + c0, e->fm2_slot, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
                             core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_scratch_stride, e->fm2_iscratch, kFm2MaxMeas,
                             chunk_out ? cov_out : cov_out + (size_t)c0 * out_stride_poses * 9, out_stride_poses,
-                            chunk_out ? n_out : n_out + c0);
+                            chunk_out ? n_out : n_out + c0, (!lm_out || lm_chunk) ? lm_out : lm_out + (size_t)c0 * S.L_max * 3, S.L_max);
     after(c0, nc);
   }
   return check_launch(e);
@@ -1122,10 +1146,11 @@ int drlgx_fm2_update_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_
 // launch and one read of its flag), so that such a call returns its code and leaves the status word alone.  core_dev / distance_dev
 // (either may be null): the leaves of a tree whose edges have non-core steps - only core poses predict measurements and enter the
 // leaf's map, the cost takes the tree's distance.
-static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                       const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+// The chunk workspaces of em_cost_run (on first use) and its check of the candidates: the smallest DRLGX_E_* code a candidate earns,
+// 0 if none does (one small launch, one read of its flag: the call's single synchronisation).
+static int em_cost_check(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                         const uint8_t *core_dev) {
   const DrlgxState &S = e->S;
-  if (drlgx_em_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
   const int stride = S.P_max + S.A_max;
   if (!e->em_cov) {
     int r;
@@ -1138,7 +1163,15 @@ static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev,
   drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, kFm2MaxMeas, e->em_flag);
   HIPCHK(e, hipMemcpyAsync(&flag, e->em_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (flag) return flag;
+  return flag;
+}
+
+static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                       const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+  const DrlgxState &S = e->S;
+  if (drlgx_em_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
+  const int stride = S.P_max + S.A_max;
+  if (int flag = em_cost_check(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev)) return flag;
   return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, e->em_cov, stride, e->em_nout, true, [&](int c0, int nc) {
     drlgx_launch_em_cost(S, e->stream, nc, cand_env_dev + c0, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
                          core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, distance_dev ? distance_dev + c0 : nullptr, e->em_cov, stride,
@@ -1195,6 +1228,42 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
   return check_launch(e);
 }
 
+// calculateUncertainty_SLAM_OG_SHANNON + costFunction for candidate action lists: the root's weights from the live belief, the leaf
+// entropy of every candidate (k_og.hip, one launch, as drlgx_og_cost), then the fm2 update with its landmark blocks a chunk at a time
+// and the blend on each chunk.  The candidates are checked first exactly as em_cost_run checks them - the call's one synchronisation.
+int drlgx_slam_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                       const uint8_t *core_dev, const double *distance_dev, double alpha, double *uncertainty_out_dev, double *cost_out_dev,
+                       double *terms_out_dev, double *weights_out_dev, double *lm_cov_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand <= 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !uncertainty_out_dev || !cost_out_dev ||
+      !(alpha >= 0.0 && alpha <= 1.0))
+    return DRLGX_E_INVALID;
+  const DrlgxState &S = e->S;
+  if (drlgx_og_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
+  int r;
+  if (!e->sog_weights) {
+    if ((r = dev_alloc(e, &e->sog_weights, (size_t)2 * S.n_envs))) return r;
+    if ((r = dev_alloc(e, &e->sog_lm, (size_t)kFm2Chunk * S.L_max * 3))) return r;
+  }
+  if ((size_t)n_cand > e->sog_cap) {
+    if ((r = scratch_reserve(e, &e->sog_h, (size_t)n_cand))) return r;
+    if ((r = scratch_reserve(e, &e->sog_dist, (size_t)2 * n_cand))) return r;
+    e->sog_cap = (size_t)n_cand;
+  }
+  if (int flag = em_cost_check(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev)) return flag;
+  double *weights = weights_out_dev ? weights_out_dev : e->sog_weights;
+  drlgx_launch_slam_og_weights(S, e->stream, alpha, weights);
+  drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->sog_h, nullptr, nullptr, e->sog_dist);
+  return fm2_run(
+      e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, e->em_cov, S.P_max + S.A_max, e->em_nout, true,
+      [&](int c0, int nc) {
+        drlgx_launch_slam_og_blend(S, e->stream, nc, cand_env_dev + c0, lm_cov_out_dev ? lm_cov_out_dev + (size_t)c0 * S.L_max * 3 : e->sog_lm,
+                                   S.L_max, e->sog_h + c0, e->sog_dist + (size_t)2 * c0, distance_dev ? distance_dev + c0 : nullptr, weights,
+                                   uncertainty_out_dev + c0, cost_out_dev + c0, terms_out_dev ? terms_out_dev + (size_t)2 * c0 : nullptr);
+      },
+      lm_cov_out_dev ? lm_cov_out_dev : e->sog_lm, lm_cov_out_dev == nullptr);
+}
+
 // ---- the EM planner's tree sampler (k_em_tree.hip) ----
 static const int kTreeMaxNodes = 2048, kTreeMeta = 4;
 
@@ -1219,20 +1288,6 @@ int drlgx_set_dubins_leaf_scoring(drlgx_engine *e, int enabled) {
   if (!e) return DRLGX_E_INVALID;
   e->dubins_leaf_scoring = enabled ? 1 : 0;
   return DRLGX_OK;
-}
-
-// a scratch array of at least `count` elements: kept while it is large enough, replaced (behind the stream's work) when it is not
-extern "C++" {
-template <typename T>
-static int scratch_reserve(drlgx_engine *e, T **p, size_t count) {
-  if (*p) {
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->allocs.erase(std::remove(e->allocs.begin(), e->allocs.end(), (void *)*p), e->allocs.end());
-    HIPCHK(e, hipFree(*p));
-    *p = nullptr;
-  }
-  return dev_alloc(e, p, count);
-}
 }
 
 // ---- the Dubins path library (EMPlanner2D::initializeDubinsPathLibrary, Planner2D.cpp:1359-1414) ----

@@ -149,6 +149,125 @@ __global__ __launch_bounds__(kT) void k_fm2_prior(DrlgxState S, const int32_t *e
   if (tid == 0 && bad) atomicMin(S.status, DRLGX_E_NUMERIC);
 }
 
+// The whitened information blocks of odometry factor i (poses i, i + 1) and of one bearing-range factor, as k_fm2_prior forms them
+// (k_fm2_prior keeps its own copy of these expressions: its code is left as it is).  B12 is the (i, i + 1) block; (i + 1, i) is its
+// transpose.  Bxl is the (pose, landmark) block 3x2; (landmark, pose) is its transpose.
+__device__ inline void odo_info(const DrlgxState &S, int inst, const double *thp, int i, const double *wo, double *B11, double *B12,
+                                double *B22) {
+  const double *oo = S.odo + ((size_t)inst * S.P_max + i) * 4;
+  const Pose ti{thp[4 * i], thp[4 * i + 1], thp[4 * i + 2], thp[4 * i + 3]};
+  const Pose tn{thp[4 * (i + 1)], thp[4 * (i + 1) + 1], thp[4 * (i + 1) + 2], thp[4 * (i + 1) + 3]};
+  double H1[9];
+  const Pose hx = between(ti, tn, H1);
+  const Pose h = between(Pose{oo[0], oo[1], oo[2], oo[3]}, hx, nullptr);
+  const double J2[9] = {h.c, h.s, 0, -h.s, h.c, 0, 0, 0, 1};
+  double J1[9];
+  mat3_mul(J2, H1, J1);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double s11 = 0, s12 = 0, s22 = 0;
+      for (int k = 0; k < 3; ++k) {
+        s11 += J1[k * 3 + r] * wo[k] * J1[k * 3 + c];
+        s12 += J1[k * 3 + r] * wo[k] * J2[k * 3 + c];
+        s22 += J2[k * 3 + r] * wo[k] * J2[k * 3 + c];
+      }
+      B11[r * 3 + c] = s11; B12[r * 3 + c] = s12; B22[r * 3 + c] = s22;
+    }
+}
+__device__ inline void br_info(const Pose &ps, const P2 &lm, double wb, double wr, double *Bxx, double *Bxl, double *Bll) {
+  double Jx[6], Jl[4];
+  br_jac(ps, lm, Jx, Jl);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Bxx[r * 3 + c] = Jx[r] * wb * Jx[c] + Jx[3 + r] * wr * Jx[3 + c];
+    for (int c = 0; c < 2; ++c) Bxl[r * 2 + c] = Jx[r] * wb * Jl[c] + Jx[3 + r] * wr * Jl[2 + c];
+  }
+  for (int r = 0; r < 2; ++r)
+    for (int c = 0; c < 2; ++c) Bll[r * 2 + c] = Jl[r] * wb * Jl[c] + Jl[2 + r] * wr * Jl[2 + c];
+}
+
+// k_fm2_prior with a FIXED summation order, for the caller that promises the same bits from the same belief (drlgx_slam_og_cost):
+// no atomics - every block of the information matrix has one owner that adds its contributions in factor order.  Owner of pose i:
+// its diagonal block (the prior, odometry factor i - 1, odometry factor i, then its measurements in list order) and the blocks
+// (i, i + 1), (i + 1, i).  Owner of landmark j: its diagonal block and every (pose, j), (j, pose) block, measurements in list order.
+// One workgroup per environment; sig as k_fm2_prior's.
+__global__ __launch_bounds__(kT) void k_fm2_prior_ordered(DrlgxState S, double *sig, size_t sig_stride) {
+  __shared__ int bad;
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, inst = blockIdx.x;
+  const int *cnt = S.cnt + (size_t)inst * DRLGX_CNT_STRIDE;
+  const int P = cnt[C_P], L = cnt[C_L], M = cnt[C_M], n = 3 * P + 2 * L;
+  const drlgx_config &cfg = S.cfg;
+  double *A = sig + (size_t)blockIdx.x * sig_stride;
+  const double *thp = S.th_pose + (size_t)inst * S.P_max * 4;
+  const double *thl = S.th_lm + (size_t)inst * S.L_max * 2;
+  const int *mp = S.meas_pose + (size_t)inst * S.M_max, *ml = S.meas_lm + (size_t)inst * S.M_max;
+  if (tid == 0) bad = 0;
+  for (size_t e = tid; e < (size_t)n * n; e += kT) A[e] = 0.0;
+  __syncthreads();
+  const double wo[3] = {1.0 / (cfg.translation_noise * cfg.translation_noise), 1.0 / (cfg.translation_noise * cfg.translation_noise),
+                        1.0 / (cfg.rotation_noise * cfg.rotation_noise)};
+  const double wb = 1.0 / (cfg.bearing_noise * cfg.bearing_noise), wr = 1.0 / (cfg.range_noise * cfg.range_noise);
+  for (int o = tid; o < P + L; o += kT) {
+    if (o < P) {
+      const int i = o;
+      const Pose ti{thp[4 * i], thp[4 * i + 1], thp[4 * i + 2], thp[4 * i + 3]};
+      double D[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, B11[9], B12[9], B22[9];
+      if (i == 0) {  // prior: J = diag(R_h^T, 1), W = the prior information
+        const double *pr = S.prior + (size_t)inst * DRLGX_PRIOR_STRIDE;
+        const Pose h = between(Pose{pr[0], pr[1], pr[2], pr[3]}, ti, nullptr);
+        const double J[9] = {h.c, h.s, 0, -h.s, h.c, 0, 0, 0, 1};
+        double WJ[9];
+        mat3_mul(pr + 4, J, WJ);
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) D[r * 3 + c] += J[r] * WJ[c] + J[3 + r] * WJ[3 + c] + J[6 + r] * WJ[6 + c];
+      }
+      if (i > 0) {
+        odo_info(S, inst, thp, i - 1, wo, B11, B12, B22);
+        for (int q = 0; q < 9; ++q) D[q] += B22[q];
+      }
+      if (i + 1 < P) {
+        odo_info(S, inst, thp, i, wo, B11, B12, B22);
+        for (int q = 0; q < 9; ++q) D[q] += B11[q];
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) {
+            A[(size_t)(3 * i + r) * n + 3 * i + 3 + c] = B12[r * 3 + c];
+            A[(size_t)(3 * i + 3 + c) * n + 3 * i + r] = B12[r * 3 + c];
+          }
+      }
+      for (int m = 0; m < M; ++m) {
+        if (mp[m] != i) continue;
+        const int j = ml[m];
+        double Bxx[9], Bxl[6], Bll[4];
+        br_info(ti, P2{thl[2 * j], thl[2 * j + 1]}, wb, wr, Bxx, Bxl, Bll);
+        for (int q = 0; q < 9; ++q) D[q] += Bxx[q];
+      }
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) A[(size_t)(3 * i + r) * n + 3 * i + c] = D[r * 3 + c];
+    } else {
+      const int j = o - P, cj = 3 * P + 2 * j;
+      const P2 lm{thl[2 * j], thl[2 * j + 1]};
+      double D[4] = {0, 0, 0, 0};
+      for (int m = 0; m < M; ++m) {
+        if (ml[m] != j) continue;
+        const int p = mp[m];
+        double Bxx[9], Bxl[6], Bll[4];
+        br_info(Pose{thp[4 * p], thp[4 * p + 1], thp[4 * p + 2], thp[4 * p + 3]}, lm, wb, wr, Bxx, Bxl, Bll);
+        for (int q = 0; q < 4; ++q) D[q] += Bll[q];
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 2; ++c) {  // (only this thread touches column / row block j: plain read-modify-write)
+            A[(size_t)(3 * p + r) * n + cj + c] += Bxl[r * 2 + c];
+            A[(size_t)(cj + c) * n + 3 * p + r] += Bxl[r * 2 + c];
+          }
+      }
+      for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 2; ++c) A[(size_t)(cj + r) * n + cj + c] = D[r * 2 + c];
+    }
+  }
+  __syncthreads();
+  spd_inverse(A, n, n, lds, lds + n, &bad);
+  if (tid == 0 && bad) atomicMin(S.status, DRLGX_E_NUMERIC);
+}
+
 struct Cand {
   int P, L, K, nm;            // old poses, landmarks, new poses, measurements
   const double *Sig;          // prior covariance of the candidate's environment, ld = n
@@ -183,11 +302,16 @@ __device__ inline void cov_old_new(const Cand &c, int r0, int nr, int b, double 
 // kMask: `core` ([candidate][max_actions], the launch's first candidate first) marks the actions that are core poses; a non-core
 // step - an intermediate pose of a Dubins edge (Planner2D.cpp:659-682) - gets its pose and its odometry factor like every action,
 // and predicts no measurement.  kMask = false never reads `core`: every action is a core pose.
-template <bool kMask>
+// kLm: the LANDMARK blocks as well (updateTrajectory_SLAM_OG_SHANNON, Planner2D.cpp:608-611, reads every landmark's marginal after
+// the same update): lm_out [candidate][lm_stride][3] (xx, xy, yy per slot, the launch's first candidate first) gets
+// Sigma'(l, l) = Sigma(l, l) - U_l^T T^-1 U_l, U_l = A Sigma(., l) (2 nm x 2), for the L slots of the candidate's environment; with no
+// predicted measurement that is the prior block, bit for bit.  kLm = false never reads `lm_out` and is the kernel without them.
+template <bool kMask, bool kLm>
 __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const int32_t *cand_env, const int32_t *env_slot,
                                                    const double *actions, const int32_t *n_actions, const double *sig,
                                                    size_t sig_stride, double *scratch, size_t scratch_stride, int *iscratch,
-                                                   int nm_max, double *cov_out, int out_stride, int32_t *n_out, const uint8_t *core) {
+                                                   int nm_max, double *cov_out, int out_stride, int32_t *n_out, const uint8_t *core,
+                                                   double *lm_out, int lm_stride) {
   __shared__ int nm_s, bad;
   __shared__ int wcount[kT / 64];
   __shared__ double gj[2 * 512];  // Gauss-Jordan row / column of T: dim = 2 nm <= 512
@@ -401,6 +525,48 @@ __global__ __launch_bounds__(kT) void k_fm2_update(DrlgxState S, int c0, const i
     }
     __builtin_amdgcn_wave_barrier();
   }
+  // ---- every landmark l: U_l = A Sigma(., l) (dim x 2), Sigma'_ll = Sigma_ll - U_l^T T^-1 U_l.  One wave per landmark, the pose
+  // loop's slab and its summation order (lanes stride the rows, then the shuffle tree): the same candidate, the same bits.
+  if (kLm) {
+    double *lo = lm_out + (size_t)ci * lm_stride * 3;
+    for (int l = wave; l < L; l += nw) {
+      double *Ul = U + (size_t)wave * 6 * nm_max;
+      const int cl = 3 * P + 2 * l;
+      for (int r = lane; r < nm; r += 64) {
+        const double *jr = J + (size_t)10 * r;
+        const int kr = mk[r], lr = mj[r];
+        double t[6], ll[4];  // Sigma(l, x_new kr) 2x3 (its transpose is Sigma(x_new kr, l)), Sigma(l_lr, l) 2x2
+        cov_old_new(c, cl, 2, kr, t);
+        for (int a = 0; a < 2; ++a)
+          for (int b = 0; b < 2; ++b) ll[a * 2 + b] = Sig[(size_t)(3 * P + 2 * lr + a) * n + cl + b];
+        for (int a = 0; a < 2; ++a)
+          for (int b = 0; b < 2; ++b)
+            Ul[(size_t)(2 * r + a) * 2 + b] = jr[3 * a] * t[b * 3] + jr[3 * a + 1] * t[b * 3 + 1] + jr[3 * a + 2] * t[b * 3 + 2] + jr[6 + 2 * a] * ll[b] + jr[7 + 2 * a] * ll[2 + b];
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      double acc[3] = {0, 0, 0};  // U^T T^-1 U, symmetric: xx, xy, yy
+      for (int r = lane; r < dim; r += 64) {
+        double w0 = 0, w1 = 0;  // (T^-1 U)[r][:]
+        const double *tr = T + (size_t)r * dim;
+        for (int s = 0; s < dim; ++s) {
+          w0 += tr[s] * Ul[2 * s];
+          w1 += tr[s] * Ul[2 * s + 1];
+        }
+        const double u0 = Ul[2 * r], u1 = Ul[2 * r + 1];
+        acc[0] += u0 * w0; acc[1] += u0 * w1; acc[2] += u1 * w1;
+      }
+      for (int q = 0; q < 3; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o);
+      if (lane == 0) {
+        lo[3 * l] = Sig[(size_t)cl * n + cl] - acc[0];
+        lo[3 * l + 1] = Sig[(size_t)cl * n + cl + 1] - acc[1];
+        lo[3 * l + 2] = Sig[(size_t)(cl + 1) * n + cl + 1] - acc[2];
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
   if (tid == 0 && bad) atomicMin(S.status, DRLGX_E_NUMERIC);
 }
 
@@ -460,14 +626,19 @@ size_t drlgx_fm2_scratch_doubles(const DrlgxState &S, int nm_max) {
   return (size_t)27 * S.A_max + (size_t)9 * S.A_max * S.A_max + (size_t)10 * nm_max + (size_t)4 * nm_max * nm_max +
          (size_t)(kfm2::kT / 64) * 6 * nm_max + (size_t)4 * S.A_max + 64;
 }
+void drlgx_launch_fm2_prior_ordered(const DrlgxState &S, hipStream_t st, double *sig, size_t sig_stride, int n_max) {
+  hipLaunchKernelGGL(kfm2::k_fm2_prior_ordered, dim3(S.n_envs), dim3(kfm2::kT), 2 * (size_t)n_max * sizeof(double), st, S, sig, sig_stride);
+}
 void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
                              const double *actions, const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride,
                              double *scratch, size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride,
-                             int32_t *n_out) {
-  if (core)
-    hipLaunchKernelGGL(kfm2::k_fm2_update<true>, dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig,
-                       sig_stride, scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out, core);
-  else
-    hipLaunchKernelGGL(kfm2::k_fm2_update<false>, dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig,
-                       sig_stride, scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out, core);
+                             int32_t *n_out, double *lm_out, int lm_stride) {
+#define DRLGX_FM2_UPDATE(kMask, kLm)                                                                                                    \
+  hipLaunchKernelGGL((kfm2::k_fm2_update<kMask, kLm>), dim3(nc), dim3(kfm2::kT), 0, st, S, c0, cand_env, env_slot, actions, n_actions, sig, \
+                     sig_stride, scratch, scratch_stride, iscratch, nm_max, cov_out, out_stride, n_out, core, lm_out, lm_stride)
+  if (core && lm_out) DRLGX_FM2_UPDATE(true, true);
+  else if (core) DRLGX_FM2_UPDATE(true, false);
+  else if (lm_out) DRLGX_FM2_UPDATE(false, true);
+  else DRLGX_FM2_UPDATE(false, false);
+#undef DRLGX_FM2_UPDATE
 }

@@ -39,9 +39,10 @@ __global__ void k_og_check(DRLGX_KS_PARAM, int n_cand, const int32_t *cand_env, 
 }
 
 // cand_env / actions / n_actions: [gridDim.x] candidates in drlgx_em_cost's layout; ent_out / cost_out [gridDim.x], prob_out
-// [gridDim.x][V], any of them null
+// [gridDim.x][V], dist_out [gridDim.x][2] (the two factors of the cost's second term: the plan's distance, the distance weight), any
+// of them null
 __global__ __launch_bounds__(kT) void k_og_cost(DRLGX_KS_PARAM, const int32_t *cand_env, const double *actions, const int32_t *n_actions,
-                                                double *ent_out, double *cost_out, double *prob_out) {
+                                                double *ent_out, double *cost_out, double *prob_out, double *dist_out) {
   const DrlgxState &S = DRLGX_KS_REF;
   extern __shared__ __attribute__((aligned(16))) double og_smem[];
   const drlgx_config &cfg = S.cfg;
@@ -131,10 +132,85 @@ __global__ __launch_bounds__(kT) void k_og_cost(DRLGX_KS_PARAM, const int32_t *c
       known += red[kWaves + w];
     }
     if (ent_out) ent_out[ci] = h;
-    if (cost_out) {
+    if (cost_out || dist_out) {
       const double pk = known / (double)V;
       const double dw = cfg.distance_weight0 - (cfg.distance_weight0 - cfg.distance_weight1) * pk;
-      cost_out[ci] = h + *sdist * dw;
+      if (cost_out) cost_out[ci] = h + *sdist * dw;
+      if (dist_out) {
+        dist_out[2 * ci] = *sdist;
+        dist_out[2 * ci + 1] = dw;
+      }
+    }
+  }
+}
+
+// ---- the SLAM-OG-Shannon cost (calculateUncertainty_SLAM_OG_SHANNON, Planner2D.cpp:394-416): the entropy above weighed against the
+// landmarks' uncertainty.  sqrt(det) of a landmark's 2x2 covariance given as (xx, xy, yy):
+__device__ inline double sqrt_det2(double xx, double xy, double yy) { return sqrt(xx * yy - xy * xy); }
+
+// The root's two weights (EMPlanner2D::initialize, Planner2D.cpp:1341-1354), one workgroup per environment, from the LIVE belief:
+//   w2 = (1 - alpha) / sum_v -p_v ln p_v - (1 - p_v) ln(1 - p_v)     (the live virtual map's probabilities)
+//   w1 = alpha / sum_l sqrt(det(inverse(information_l)))             (the live landmark marginals, in slot order)
+// Both sums: a thread strides its terms, then the waves' sums in wave order.  The divisions are plain IEEE (no landmark: w1 = inf).
+// weights [n_envs][2] = w1, w2.
+__global__ __launch_bounds__(kT) void k_slam_og_weights(DRLGX_KS_PARAM, double alpha, double *weights) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  __shared__ double red[2 * kWaves];
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6, env = blockIdx.x;
+  const int L = S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_L], V = S.V;
+  const double *live = S.vm_prob + (size_t)env * V;
+  const double *li = S.lm_info + (size_t)env * S.L_max * 3;
+  double s_h = 0.0, s_l = 0.0;
+  for (int v = tid; v < V; v += kT) {
+    const double pv = live[v];
+    s_h += -pv * log(pv) - (1.0 - pv) * log(1.0 - pv);
+  }
+  for (int j = tid; j < L; j += kT) {
+    const double a = li[3 * j], b = li[3 * j + 1], d = li[3 * j + 2], det = a * d - b * b;
+    s_l += sqrt_det2(d / det, -b / det, a / det);  // covariance() = inverse(information)
+  }
+  s_h = kmap::wave_sum63(s_h);
+  s_l = kmap::wave_sum63(s_l);
+  if (lane == 63) {
+    red[wave] = s_h;
+    red[kWaves + wave] = s_l;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double h = 0.0, sl = 0.0;
+    for (int w = 0; w < kWaves; ++w) {
+      h += red[w];
+      sl += red[kWaves + w];
+    }
+    weights[2 * env] = alpha / sl;
+    weights[2 * env + 1] = (1.0 - alpha) / h;
+  }
+}
+
+// The blend (Planner2D.cpp:407-413, :418-420), one wave per candidate:
+//   slam_uncertainty = sum_l sqrt(det Sigma'(l, l))   over the L slots of the candidate's environment: lane q takes slots q, q + 64, ...
+//     in rising order, then the wave's sum - a fixed order, the same candidate gives the same bits;
+//   uncertainty = w2 H_leaf + w1 slam_uncertainty;   cost = uncertainty + distance * distance_weight.
+// lm_cov [nc][lm_stride][3]: what k_fm2_update left; h_leaf [nc], dist [nc][2]: what k_og_cost left; distance [nc] or null: the
+// caller's distance instead of the plan's own; weights [n_envs][2].  unc_out / cost_out [nc], terms_out [nc][2] (H_leaf,
+// slam_uncertainty): any of them null.  All arrays start at the launch's first candidate.
+__global__ __launch_bounds__(64) void k_slam_og_blend(DRLGX_KS_PARAM, const int32_t *cand_env, const double *lm_cov, int lm_stride,
+                                                      const double *h_leaf, const double *dist, const double *distance,
+                                                      const double *weights, double *unc_out, double *cost_out, double *terms_out) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  const int lane = drlgx_tid(), ci = blockIdx.x, env = cand_env[ci];
+  const int L = S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_L];
+  const double *lc = lm_cov + (size_t)ci * lm_stride * 3;
+  double s = 0.0;
+  for (int l = lane; l < L; l += 64) s += sqrt_det2(lc[3 * l], lc[3 * l + 1], lc[3 * l + 2]);
+  s = kmap::wave_sum63(s);
+  if (lane == 63) {
+    const double h = h_leaf[ci], unc = weights[2 * env + 1] * h + weights[2 * env] * s;
+    if (unc_out) unc_out[ci] = unc;
+    if (cost_out) cost_out[ci] = unc + (distance ? distance[ci] : dist[2 * ci]) * dist[2 * ci + 1];
+    if (terms_out) {
+      terms_out[2 * ci] = h;
+      terms_out[2 * ci + 1] = s;
     }
   }
 }
@@ -148,10 +224,21 @@ void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, cons
 }
 
 void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
-                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out) {
+                          const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out, double *dist_out) {
   static bool attr_set[32] = {false};
   const void *fns[] = {reinterpret_cast<const void *>(&kog::k_og_cost)};
   drlgx_ensure_lds_attr(attr_set, fns, 1, (int)kmap::kLdsBudget);
   hipLaunchKernelGGL(kog::k_og_cost, dim3(nc), dim3(kog::kT), drlgx_og_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions, n_actions,
-                     ent_out, cost_out, prob_out);
+                     ent_out, cost_out, prob_out, dist_out);
+}
+
+void drlgx_launch_slam_og_weights(const DrlgxState &S, hipStream_t st, double alpha, double *weights) {
+  hipLaunchKernelGGL(kog::k_slam_og_weights, dim3(S.n_envs), dim3(kog::kT), 0, st, DRLGX_KS_ARG(S), alpha, weights);
+}
+
+void drlgx_launch_slam_og_blend(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *lm_cov, int lm_stride,
+                                const double *h_leaf, const double *dist, const double *distance, const double *weights, double *unc_out,
+                                double *cost_out, double *terms_out) {
+  hipLaunchKernelGGL(kog::k_slam_og_blend, dim3(nc), dim3(64), 0, st, DRLGX_KS_ARG(S), cand_env, lm_cov, lm_stride, h_leaf, dist, distance,
+                     weights, unc_out, cost_out, terms_out);
 }

@@ -337,6 +337,38 @@ class Engine(object):
         self._chk(self.L.drlgx_og_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(ent), _p(cost), _p(prob)))
         return (ent, cost, prob) if want_prob else (ent, cost)
 
+    def slam_og_cost(self, cand_env, actions, n_actions, alpha, core=None, distance=None, want_terms=False, want_lm_cov=False):
+        """SLAM-OG-Shannon cost of candidate plans (drlgx_slam_og_cost: calculateUncertainty_SLAM_OG_SHANNON and costFunction,
+        without simulating or re-solving): the expected map entropy of `og_cost` weighed against the landmarks' uncertainty after the
+        covariance update of `fm2_update` - uncertainty = w2 H_leaf + w1 sum_l sqrt(det Sigma'(l, l)), w2 = (1 - alpha) / H_root and
+        w1 = alpha / sum_l sqrt(det cov_l) from the live belief (an environment without a landmark has w1 = inf and NaN
+        uncertainties, as the reference's plain divisions give).  Returns (uncertainty [C], cost [C]) float64 and, with
+        `want_terms`, terms [C, 2] (H_leaf, slam_uncertainty) and weights [n_envs, 2] (w1, w2); with `want_lm_cov` the landmarks'
+        updated blocks [C, max_landmarks, 3] (xx, xy, yy per slot; rows beyond the environment's landmark count are NaN).
+        Candidates as in `em_cost`: cand_env [C] i32, actions [C, max_actions, 3] f64, n_actions [C] i32 on the device, C >= 1;
+        alpha in [0, 1]; `core` (uint8 [C, max_actions]) / `distance` (f64 [C]), device tensors or None, as `em_cost`'s."""
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError("alpha must lie in [0, 1], not %r" % (alpha,))
+        self.use_torch_stream()
+        n = cand_env.numel()
+        if core is not None:
+            core = self._core_mask(core, n)
+        if distance is not None and (distance.dtype != torch.float64 or distance.numel() != n or not distance.is_contiguous()):
+            raise ValueError("distance: a contiguous float64 tensor [C] expected")
+        unc = torch.empty(n, dtype=torch.float64, device=self.device)
+        cost = torch.empty(n, dtype=torch.float64, device=self.device)
+        terms = torch.empty(n, 2, dtype=torch.float64, device=self.device) if want_terms else None
+        weights = torch.empty(self.n_envs, 2, dtype=torch.float64, device=self.device) if want_terms else None
+        lm_cov = torch.full((n, self.cfg.max_landmarks, 3), float("nan"), dtype=torch.float64, device=self.device) if want_lm_cov else None
+        self._chk(self.L.drlgx_slam_og_cost(self.h, n, _p(cand_env), _p(actions), _p(n_actions), _p(core), _p(distance), float(alpha),
+                                            _p(unc), _p(cost), _p(terms), _p(weights), _p(lm_cov)))
+        out = (unc, cost)
+        if want_terms:
+            out += (terms, weights)
+        if want_lm_cov:
+            out += (lm_cov,)
+        return out
+
     def set_sampler_parameter(self, max_nodes, safe_distance=0.0, dubins_control_model_enabled=False):
         """The planner parameters only the tree sampler reads (drlgx_set_sampler_parameter); a non-zero safe_distance or the Dubins
         control model is stored and then refused by em_plan / rrt_plan (a safe_distance >= 0 is served once

@@ -96,7 +96,7 @@ class EMPlanner2D(object):
     """`EMPlanner2D(parameter, sensor_model, control_model)` (src/Planner2D.cpp:73-91) over the engine that the models'
     simulation owns: the calls the DRL scripts make - `calculate_utility` (static), `line_planner`, `simulations_reward` -
     run `drlgx_utility` / `drlgx_line_plan` / `drlgx_lookahead`; `leaf_cost` is the leaf evaluation of `optimize2`
-    (`drlgx_em_cost`) for an action list the caller supplies, `leaf_entropy` the OG-Shannon cost of one (`drlgx_og_cost`); `optimize2` and `rrt_planner` grow the sampler's tree on the device
+    (`drlgx_em_cost`) for an action list the caller supplies, `leaf_entropy` the OG-Shannon cost of one (`drlgx_og_cost`), `leaf_slam_entropy` its SLAM-OG-Shannon cost (`drlgx_slam_og_cost`); `optimize2` and `rrt_planner` grow the sampler's tree on the device
     (`drlgx_em_plan` / `drlgx_rrt_plan`: non-Dubins control model, safe_distance 0 - or, with the attribute `obstacle_logic` set,
     any safe_distance >= 0 with the reference's isSafe / retry / shrink logic; it is an opt-in because the default refusal is what
     existing callers and tests rely on) and `iter_solution` walks the best path as the reference binding does.  The Halton index starts where the reference's constructor starts it and carries on from call to
@@ -206,6 +206,18 @@ class EMPlanner2D(object):
         ent, cost = e.og_cost(ce, acts, n)
         e.check_status()
         return (float(ent[0]), float(cost[0])) if return_cost else float(ent[0])
+
+    def leaf_slam_entropy(self, slam, virtual_map, actions, return_cost=False):
+        """calculateUncertainty_SLAM_OG_SHANNON (Planner2D.cpp:394-416) for ONE action list of the wrapped simulation:
+        w2 * (the entropy of `leaf_entropy`) + w1 * sum_l sqrt(det cov_l) over the landmarks after the plan's noise-free odometry
+        and predicted measurements have updated their marginals (`drlgx_slam_og_cost`), with the root's weights w1 = alpha / (the
+        same sum now), w2 = (1 - alpha) / (the entropy of the live map) and the parameter's `alpha`; with `return_cost` also
+        costFunction = uncertainty + distance * distance_weight.  No simulation, no re-solve; the live objects are not modified.
+        The tree planners under the OG algorithms stay out of scope."""
+        e, ce, acts, n = self._one_candidate(actions)
+        unc, cost = e.slam_og_cost(ce, acts, n, self._parameter.alpha)
+        e.check_status()
+        return (float(unc[0]), float(cost[0])) if return_cost else float(unc[0])
 
     def _one_candidate(self, actions):
         """(engine, cand_env, actions, n_actions) of one action list (Pose2 or (x, y, theta) entries) in the candidate layout."""

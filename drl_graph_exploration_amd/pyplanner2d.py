@@ -58,7 +58,7 @@ def config_from_ini(cp, max_poses=256, max_actions=None, max_snapshots=1):
     pp = planner2d.EMPlannerParameter()
     if cp.has_section("Planner"):
         for k in ("angle_weight", "distance_weight0", "distance_weight1", "d_weight", "max_edge_length", "occupancy_threshold",
-                  "safe_distance", "max_nodes"):
+                  "safe_distance", "max_nodes", "alpha"):
             if cp.has_option("Planner", k):
                 setattr(pp, k, cp.getfloat("Planner", k))
         pp.seed = cp.getint("Planner", "seed")

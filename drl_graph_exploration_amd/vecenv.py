@@ -59,8 +59,11 @@ def normalise_rewards(raw, cand_env, cand_first, n_envs, n_frontier=None):
 
 class VecExplorationEnv(object):
     def __init__(self, map_size, n_envs, env_index=0, test=True, num_landmarks=None, algorithm=0, device=0,
-                 n_rollouts=None, max_poses=None, starts=None, seed=None):
+                 n_rollouts=None, max_poses=None, starts=None, seed=None, alpha=None):
         self.map_size = map_size
+        # the planner parameter alpha (SLAM_OG_SHANNON's weight of the landmark term; None: EMPlannerParameter's default)
+        from .planner2d import EMPlannerParameter
+        self.alpha = EMPlannerParameter().alpha if alpha is None else float(alpha)
         self.n_envs = n_envs
         self.test = test
         if max_poses is None:
@@ -268,16 +271,18 @@ class VecExplorationEnv(object):
         expected cost instead - raw = the root's uncertainty (Engine.uncertainty_em) minus the leaf's cost (Engine.em_cost, the
         leaf evaluation of optimize2) with the planner parameter's algorithm: the sign convention of U_before - U_after.  "og":
         the expected map entropy (Engine.og_cost, calculateUncertainty_OG_SHANNON) in the same convention - raw = the entropy of
-        the candidate's environment with no action (one extra candidate per env in the same call) minus the candidate's cost."""
-        if lookahead not in ("sim", "em", "og"):
-            raise ValueError("lookahead must be 'sim', 'em' or 'og', not %r" % (lookahead,))
+        the candidate's environment with no action (one extra candidate per env in the same call) minus the candidate's cost.
+        "slam_og": the SLAM-OG-Shannon cost (Engine.slam_og_cost, calculateUncertainty_SLAM_OG_SHANNON) exactly as "og" - raw = the
+        uncertainty of the environment with no action minus the candidate's cost - with the planner parameter `alpha` (self.alpha)."""
+        if lookahead not in ("sim", "em", "og", "slam_og"):
+            raise ValueError("lookahead must be 'sim', 'em', 'og' or 'slam_og', not %r" % (lookahead,))
         actions, n_act = all_actions if all_actions is not None else (self._actions, self._n_act)
-        if lookahead == "og":
+        if lookahead in ("og", "slam_og"):
             nc = self._cand_env.numel()
             roots = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
-            ent, cost = self.engine.og_cost(torch.cat([self._cand_env, roots]),
-                                            torch.cat([actions, actions.new_zeros((self.n_envs,) + tuple(actions.shape[1:]))]),
-                                            torch.cat([n_act, torch.zeros_like(roots)]))
+            cands = (torch.cat([self._cand_env, roots]), torch.cat([actions, actions.new_zeros((self.n_envs,) + tuple(actions.shape[1:]))]),
+                     torch.cat([n_act, torch.zeros_like(roots)]))
+            ent, cost = self.engine.og_cost(*cands) if lookahead == "og" else self.engine.slam_og_cost(*cands, self.alpha)
             raw = ent[nc:][self._cand_env.long()] - cost[:nc]
             r, self.loop_clo = normalise_rewards(raw, self._cand_env.long(), self._cand_first, self.n_envs, self._graph["n_frontier"])
             return (r, raw) if return_raw else r

@@ -288,6 +288,39 @@ int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev
 int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                   double *entropy_out_dev, double *cost_out_dev, double *prob_out_dev);
 
+/* calculateUncertainty_SLAM_OG_SHANNON (src/em_exploration/Planner2D.cpp:394-416) and costFunction (:418-420) for n_cand candidates
+ * (environment, action list) the caller supplies - the fourth OptimizationAlgorithm (include/em_exploration/Planner2D.h:32-37), the
+ * one that weighs map entropy against landmark uncertainty:
+ *   updateTrajectory_SLAM_OG_SHANNON (:584-618) adds the plan's noise-free odometry and predicted bearing-range factors to a copy of
+ *     the root's iSAM2 and reads every landmark's marginal covariance (:608-611).  With zero residuals and no relinearisation that is
+ *     the linear update of drlgx_fm2_update, Sigma' = Sigma - Sigma A^T (I + A Sigma A^T)^-1 A Sigma, read on the LANDMARK diagonal
+ *     blocks (the one deviation: iSAM2's update may relinearise variables past its threshold, the linear update does not);
+ *   slam_uncertainty = sum_l sqrt(det Sigma'(l, l)) over the environment's landmarks in slot order (:409-413);
+ *   H_leaf = drlgx_og_cost's entropy of the same candidate (:397-407; the same kernel, the same bits);
+ *   the root's weights, once per call and environment from the LIVE belief (EMPlanner2D::initialize, :1341-1354):
+ *     w2 = (1 - alpha) / H_root, H_root the Shannon entropy of the live virtual map's probabilities;
+ *     w1 = alpha / sum_l sqrt(det(inverse(information_l))) over the live landmark marginals (what drlgx_get_landmarks_host returns);
+ *     both divisions are plain IEEE as in the reference: an environment without a landmark has w1 = inf (alpha > 0) or NaN
+ *     (alpha = 0), and its candidates' uncertainty is inf * 0 = NaN - nothing is special-cased;
+ *   uncertainty = w2 H_leaf + w1 slam_uncertainty (:407, :413); cost = uncertainty + distance * distance_weight, distance and
+ *     distance_weight exactly drlgx_og_cost's.
+ * Candidates as drlgx_em_cost_steps: cand_env_dev int32[n_cand], actions_dev double[n_cand*max_actions*3], n_actions_dev
+ * int32[n_cand]; core_dev uint8[n_cand*max_actions] or NULL (= every action is a core pose): only core poses predict measurements
+ * (the entropy sweep still takes every pose, as drlgx_og_cost does); distance_dev double[n_cand] or NULL (= the plan's own distance,
+ * as drlgx_og_cost computes it).  alpha in [0, 1] (EMPlanner2D::Parameter::alpha, Planner2D.h:75).
+ * uncertainty_out_dev / cost_out_dev: DEVICE double[n_cand], both required.  Optional (NULL = not wanted): terms_out_dev
+ * double[n_cand*2] (H_leaf, slam_uncertainty); weights_out_dev double[n_envs*2] (w1, w2); lm_cov_out_dev
+ * double[n_cand*max_landmarks*3] (xx, xy, yy of Sigma'(l, l) per slot; slots beyond the environment's landmark count are not written).
+ * A candidate that predicts no measurement gets the prior blocks unchanged.  The same call on the same belief returns the same bits
+ * (the prior covariance is summed in a fixed order here, unlike drlgx_fm2_update's).
+ * DRLGX_E_INVALID: a NULL required pointer, n_cand <= 0, alpha outside [0, 1], a candidate that names no environment or has more than
+ * max_actions actions; DRLGX_E_CAPACITY: more than 256 predicted measurements in one candidate (of core poses, with a mask).  The
+ * candidates are checked before anything else is launched, as drlgx_em_cost checks them (this call synchronises once); a refused call
+ * leaves the outputs, the status word and the live state alone.  Candidates go through the update in chunks of 128. */
+int drlgx_slam_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                       const uint8_t *core_dev, const double *distance_dev, double alpha, double *uncertainty_out_dev,
+                       double *cost_out_dev, double *terms_out_dev, double *weights_out_dev, double *lm_cov_out_dev);
+
 /* The planner parameters only the tree sampler reads (EMPlanner2D::Parameter, scripts/envs/pyplanner2d.py:29, :35, :50): max_nodes
  * (the fraction of the known cells that optimize2's tree may hold; >= 0), safe_distance and dubins_control_model_enabled.  The
  * sampler serves safe_distance = 0 and the non-Dubins control model only: other values are stored here and refused by
