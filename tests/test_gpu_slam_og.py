@@ -27,9 +27,9 @@ pytestmark = pytest.mark.gpu
 import og_ref  # noqa: E402
 import slam_og_cases as K  # noqa: E402
 import slam_og_ref as R  # noqa: E402
+from slam_og_check import SUM_RTOL, bits as _bits, check_case, check_nothing_else_moved  # noqa: E402
 
 DRLGX_E_INVALID, DRLGX_E_CAPACITY = -1, -3
-SUM_RTOL = 1e-12
 NAMES = sorted(K.CASES)
 
 
@@ -81,37 +81,11 @@ def ctx():
     c.eng.close()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _blocks3(ref_blocks):
-    return np.stack([ref_blocks[:, 0, 0], ref_blocks[:, 0, 1], ref_blocks[:, 1, 1]], axis=1)
-
-
 def _check_case(ctx, name, out, i, distance=None):
+    """slam_og_check.check_case (shared with tests/test_gpu_slam_og_wrap.py) on a named case of this world."""
     ref = ctx.ref(name) if distance is None else K.reference(ctx.world, name, distance=distance)
     e = K.CASES[name][0]
-    L = ctx.sims[e].num_landmarks()
-    got, want = out["lm_cov"][i], _blocks3(ref["lm_cov"])
-    gap = (np.abs(got[:L] - want) / (K.LM_RTOL * np.abs(want) + K.LM_ATOL)).max()
-    s_tol = K.sqrt_det_sum_tol(ref["lm_cov"])
-    root_cov = [np.linalg.inv(m) for m in ctx.sims[e].landmarks()[2]]
-    root_rel = K.sqrt_det_sum_tol(root_cov) / R.sum_sqrt_det(root_cov)
-    h, s = out["terms"][i]
-    w1, w2 = out["weights"][e]
-    print("%s: nm %d  blocks gap / tolerance %.3e  H_leaf %.2e  slam_uncertainty %.3e of its bound  w1 %.2e  w2 %.2e  unc %.2e  cost %.2e" % (
-        name, ref["nm"], gap, abs(h / ref["h_leaf"] - 1), abs(s - ref["slam_uncertainty"]) / s_tol, abs(w1 / ref["w1"] - 1),
-        abs(w2 / ref["w2"] - 1), abs(out["unc"][i] / ref["uncertainty"] - 1), abs(out["cost"][i] / ref["cost"] - 1)))
-    assert np.isnan(got[L:]).all(), name  # slots beyond the environment's landmarks are not written
-    np.testing.assert_allclose(got[:L], want, rtol=K.LM_RTOL, atol=K.LM_ATOL, err_msg=name)
-    assert h == pytest.approx(ref["h_leaf"], rel=SUM_RTOL), name
-    assert abs(s - ref["slam_uncertainty"]) <= s_tol, name
-    assert out["unc"][i] == w2 * h + w1 * s, name
-    unc_tol = SUM_RTOL * 2 * abs(ref["w2"] * ref["h_leaf"]) + abs(ref["w1"]) * s_tol + abs(ref["w1"] * ref["slam_uncertainty"]) * root_rel
-    assert abs(out["unc"][i] - ref["uncertainty"]) <= unc_tol, name
-    dterm = ref["cost"] - ref["uncertainty"]
-    assert abs(out["cost"][i] - ref["cost"]) <= unc_tol + 4e-16 * abs(dterm) + 2e-16 * abs(ref["cost"]), name
+    check_case(ctx.sims[e], e, name, ref, out, i, sum_rtol=SUM_RTOL)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -239,23 +213,12 @@ def test_over_the_cap_and_bad_arguments(ctx):
 
 
 def test_nothing_else_moved(ctx):
-    """drlgx_fm2_update_steps / drlgx_em_cost_steps before and after drlgx_slam_og_cost: the same bits, so the call leaves the live
-    state and the workspaces they read alone."""
+    """drlgx_fm2_update_steps / drlgx_em_cost_steps before and after drlgx_slam_og_cost, and the getters: the call leaves the live
+    state (the same bits through the getters) and the workspaces they read alone (slam_og_check.check_nothing_else_moved: the
+    same bits where those entries repeat their own, otherwise their restatements at their tests' tolerances)."""
     cases = [K.CASES[n] for n in NAMES]
-    ce, acts, nact, core = ctx.candidates(cases, masked=True)
-    cov0, n0 = ctx.eng.fm2_update(ce, acts, nact, core=core)
-    em0 = ctx.eng.em_cost(ce, acts, nact, 1, core=core)
-    ctx.run(cases)
-    cov1, n1 = ctx.eng.fm2_update(ce, acts, nact, core=core)
-    ctx.run(cases)
-    em1 = ctx.eng.em_cost(ce, acts, nact, 1, core=core)
-    assert ctx.eng.status() == 0
-    n0, n1 = n0.cpu().numpy(), n1.cpu().numpy()
-    np.testing.assert_array_equal(n0, n1)
-    for c in range(len(cases)):
-        np.testing.assert_array_equal(_bits(cov0[c, :n0[c]].cpu().numpy()), _bits(cov1[c, :n1[c]].cpu().numpy()))
-    for a, b in zip(em0, em1):
-        np.testing.assert_array_equal(_bits(a.cpu().numpy()), _bits(b.cpu().numpy()))
+    check_nothing_else_moved(ctx, NAMES, cases, [lambda: ctx.run(cases), lambda: ctx.run(cases)],
+                             [n for n in NAMES if K.CASES[n][2] is None], "walked_K9")
 
 
 def test_the_same_call_twice_gives_the_same_bits(ctx):
