@@ -759,6 +759,11 @@ void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t s
                        const DrlgxState *panel = nullptr,  // &S: the same launch copies the instances' covariance panels too
                        int only_cls = -1,  // >= 0: the fields of this class only (a class-0 field cannot be skipped by the mask)
                        int panel_mode = 1);  // 1: whole panels; 2: a lazy restore leaves valid bodies behind; 3: those bodies (k_misc.hip)
+// a lazy restore (skip_mask 1, panel mode 2) of envs 0 .. n - 1 from instances src_off + i, one workgroup per env; tab_dev: the
+// device copy of drlgx_restore_table (drlgx_fields.h), jc_meta: null for an engine without panels
+void drlgx_launch_restore_compact(const DrlgxField *tab_dev, int n_tab, int n16, hipStream_t st, int n, int src_off, const int *cnt,
+                                  int *jc_meta);
+int drlgx_restore_items_per_trip();  // 16-byte items a workgroup of it moves per trip of its loop: threads x loads in flight (words: half as many)
 void drlgx_launch_rebase(const DrlgxState &S, hipStream_t st, int base0, int n);
 // head of a packed status read: the status word + n_envs pose counts, rounded up to 16 bytes (k_fetch_pack)
 inline size_t drlgx_fetch_head_bytes(int n_envs) { return ((size_t)(n_envs + 1) * sizeof(int) + 15) & ~(size_t)15; }

@@ -42,6 +42,10 @@ struct drlgx_engine {
   unsigned char state_shadow[sizeof(DrlgxState)];
   std::vector<DrlgxField> fields;       // per-instance fields (n_inst instances)
   DrlgxField *fields_dev = nullptr;
+  // the compact restore's table (drlgx_restore_table): the first restore_n16 entries are moved as 16-byte items
+  std::vector<DrlgxField> restore_tab;
+  DrlgxField *restore_tab_dev = nullptr;
+  int restore_n16 = 0;
   std::vector<int> lm_order;
   // staging
   int32_t *stage_i32 = nullptr;
@@ -128,6 +132,8 @@ struct drlgx_engine {
   // Any other entry point settles the debt first (settle: one copy of planes and bodies).  DRLGX_RESTORE_EAGER=1: the full copy.
   int owed_slot = -1;
   bool restore_eager = false;
+  // DRLGX_RESTORE_COMPACT=0: a lazy restore runs the generic copy kernel, not k_restore_compact (the A/B of the compact restore)
+  bool restore_compact = true;
 };
 
 // every entry point makes the engine's device current (a process may drive several engines on several devices) and - all but
@@ -277,6 +283,7 @@ static void read_env_switches(drlgx_engine *e) {
   e->la_presim = env_flag("DRLGX_LOOKAHEAD_PRESIM", true);  // 0: every rollout action simulates inside its belief step (the A/B of the parity test)
   e->la_loop = env_flag("DRLGX_LOOKAHEAD_LOOP", true);  // 0: one launch per action index (the A/B of the look-ahead tests)
   e->restore_eager = env_flag("DRLGX_RESTORE_EAGER", false);  // 1: a restore copies the virtual-map planes and panel bodies too (the A/B of the lazy restore)
+  e->restore_compact = env_flag("DRLGX_RESTORE_COMPACT", true);  // 0: a lazy restore by the generic copy kernel (the A/B of the compact restore)
 }
 
 static double p2l(double p) { return std::log(p / (1.0 - p)); }
@@ -549,6 +556,9 @@ static int alloc_staging(drlgx_engine *e) {
   });
   TRY(dev_alloc(e, &e->fields_dev, e->fields.size()));
   HIPCHK(e, hipMemcpyAsync(e->fields_dev, e->fields.data(), e->fields.size() * sizeof(DrlgxField), hipMemcpyHostToDevice, e->stream));
+  e->restore_tab = drlgx_restore_table(e->fields, S.jd, S.P_max, &e->restore_n16);
+  TRY(dev_alloc(e, &e->restore_tab_dev, e->restore_tab.size()));
+  HIPCHK(e, hipMemcpyAsync(e->restore_tab_dev, e->restore_tab.data(), e->restore_tab.size() * sizeof(DrlgxField), hipMemcpyHostToDevice, e->stream));
   TRY(dev_alloc(e, &e->stage_i32, (size_t)n_envs));
   TRY(dev_alloc(e, &e->stage_u32, (size_t)n_envs));
   TRY(dev_alloc(e, &e->stage_f64, (size_t)n_envs * 3));
@@ -753,6 +763,7 @@ static int status_fetch(drlgx_engine *e, const void *src_dev, size_t bytes, void
     e->fetch_cap = cap;
   }
   drlgx_launch_fetch_pack(e->S, e->stream, src_dev, bytes, e->fetch_dev);
+  if (int r = check_launch(e)) return r;
   HIPCHK(e, hipMemcpyAsync(e->fetch_host, e->fetch_dev, head + bytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, stream_wait(e));
   const int32_t *h = reinterpret_cast<const int32_t *>(e->fetch_host);
@@ -1965,6 +1976,10 @@ int drlgx_snapshot(drlgx_engine *e, int slot) {
   return check_launch(e);
 }
 
+static bool restore_is_compact(const drlgx_engine *e) {
+  return e->restore_compact && !e->restore_eager && (int)e->restore_tab.size() <= kRestoreMaxEntries;
+}
+
 int drlgx_restore(drlgx_engine *e, int slot) {
   DRLGX_ENTER_OWING(e);  // (a debt of an earlier restore is void: this one replaces every plane it covered)
   if (!e || slot < 0 || slot >= e->S.cfg.max_snapshots) return DRLGX_E_INVALID;
@@ -1973,8 +1988,13 @@ int drlgx_restore(drlgx_engine *e, int slot) {
   // lazy: everything but the virtual-map planes (43 % of an instance's live bytes at the bench state), which the next belief step
   // rebuilds without reading them, and the bodies of the valid covariance panels, which it reads where they are - or settle() copies
   // both before anything else touches the envs
-  drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, snapshot_base(e, slot), 0,
-                    e->restore_eager ? 0 : 1, e->S.cnt, &S, -1, e->restore_eager ? 1 : 2);
+  // (the lazy form by one workgroup per env over its own table, k_restore_compact; the generic kernel's is the A/B)
+  if (restore_is_compact(e))
+    drlgx_launch_restore_compact(e->restore_tab_dev, (int)e->restore_tab.size(), e->restore_n16, e->stream, S.n_envs, snapshot_base(e, slot),
+                                 S.cnt, S.jc ? S.jc_meta : nullptr);
+  else
+    drlgx_launch_copy(e->fields_dev, (int)e->fields.size(), e->stream, S.n_envs, nullptr, nullptr, snapshot_base(e, slot), 0,
+                      e->restore_eager ? 0 : 1, e->S.cnt, &S, -1, e->restore_eager ? 1 : 2);
   e->owed_slot = e->restore_eager ? -1 : slot;
   e->pbound = e->snap_pbound[slot];
   return check_launch(e);
@@ -2041,6 +2061,29 @@ int drlgx_debug_panel_host(drlgx_engine *e, int inst, int32_t meta[4], double *p
                                2 * (size_t)L, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return DRLGX_OK;
+}
+
+// ---- development aid: the compact restore's table ----------------------------------------------------------------
+int drlgx_debug_restore_table_host(const drlgx_engine *e, int32_t info[4], int64_t *rows, int rows_cap) {
+  if (!e || !info) return DRLGX_E_INVALID;
+  const int n = (int)e->restore_tab.size();
+  info[0] = n;
+  info[1] = e->restore_n16;
+  info[2] = restore_is_compact(e) ? 1 : 0;
+  info[3] = drlgx_restore_items_per_trip();
+  for (int k = 0; rows && k < n && k < rows_cap; ++k) {
+    const DrlgxField &f = e->restore_tab[k];
+    rows[4 * k] = (int64_t)f.stride;
+    rows[4 * k + 1] = f.unit;
+    rows[4 * k + 2] = f.unit_bytes;
+    rows[4 * k + 3] = f.pad;
+  }
+  return DRLGX_OK;
+}
+
+int64_t drlgx_debug_field_live_bytes(int64_t stride, int unit, int unit_bytes, int pad, int count) {
+  if (stride < 0 || unit < 0 || unit_bytes < 0) return -1;
+  return (int64_t)drlgx_field_live_bytes((size_t)stride, unit, unit_bytes, pad, count);
 }
 
 // ---- timing ------------------------------------------------------------------------------------

@@ -56,14 +56,15 @@ __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields
   const char *sb = fields[f].base + (size_t)s * stride;
   char *db = fields[f].base + (size_t)d * stride;
   // the live part: per-pose / per-landmark / per-factor arrays end at the source instance's counts
-  size_t live = fields[f].pad > 0 ? (size_t)fields[f].pad : stride;  // (pad: a sub-slice of the instance's slice - one plane of the virtual map's information)
-  if (fields[f].unit && cnt) {
+  // (pad: a sub-slice of the instance's slice - one plane of the virtual map's information)
+  const int unit = cnt ? fields[f].unit : 0;
+  int count = 0;
+  if (unit) {
     const int *c = cnt + (size_t)s * DRLGX_CNT_STRIDE;
-    const int k = fields[f].unit == 1 ? c[C_P] : fields[f].unit == 2 ? c[C_L] : c[C_M];
-    const size_t b = ((size_t)(k > 0 ? k : 0) * (size_t)fields[f].unit_bytes + 15) & ~(size_t)15;
-    live = b < stride ? b : stride;
+    count = unit == 1 ? c[C_P] : unit == 2 ? c[C_L] : c[C_M];
   }
-  if ((stride & 15) == 0) {
+  const size_t live = drlgx_field_live_bytes(stride, unit, fields[f].unit_bytes, fields[f].pad, count);
+  if (!drlgx_field_by_words(stride)) {
     const uint4 *sp = reinterpret_cast<const uint4 *>(sb);
     uint4 *dp = reinterpret_cast<uint4 *>(db);
     const size_t nq = live / 16;
@@ -78,6 +79,112 @@ __global__ __launch_bounds__(256) void k_copy_instances(const DrlgxField *fields
     uint32_t *dp = reinterpret_cast<uint32_t *>(db);
     const size_t nw = (live < stride ? live : stride) / 4;
     for (size_t k = threadIdx.x; k < nw; k += 256) dp[k] = sp[k];
+  }
+}
+
+// A lazy restore (snapshot instance src_off + i -> env i: k_copy_instances with skip_mask 1 and copy_panel_part's mode 2) by ONE
+// workgroup per env.  The generic kernel's grid is (31 fields + 8 panel parts) x envs - about 10 000 workgroups at 256 envs, most of
+// which return at once or move a few bytes behind two dependent reads - for the 23 KB per env a lazy restore still moves at the
+// bench state.  Here the first wave reads the source's counts, its panel header and the table (drlgx_restore_table: n_tab <=
+// kRestoreMaxEntries entries, the first n16 moved as 16-byte items, the others as words) in one round trip, lane k computes entry k's
+// live items (drlgx_field_live_bytes: the byte ranges are the generic kernel's) and a wave scan leaves their prefix in LDS.  The items
+// of all entries form one index space; thread t serves items t, t + T, ... of either kind, finds (entry, offset) by a five-step
+// search of the prefix, and has kRestoreDepth + kRestoreWordDepth loads in flight before its first store.
+constexpr int kRestoreDepth = 4, kRestoreWordDepth = 2;
+#ifndef DRLGX_RESTORE_THREADS
+// (headline, M env-steps/s: 256 threads 4.30-4.35, 512 threads 4.36-4.42, 1024 threads 4.43-4.46 in three runs - ahead of 512 by
+// about one run's spread, not separated from it; the generic kernel 4.17-4.20; profiles/restore_compact_ab.txt)
+#define DRLGX_RESTORE_THREADS 512
+#endif
+constexpr int kRestoreThreads = DRLGX_RESTORE_THREADS;
+
+// (its slices are addressed as global memory, not through flat pointers read back from LDS: plain vector types in that address space)
+typedef unsigned int restore_q __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) restore_q restore_gq;
+typedef __attribute__((address_space(1))) uint32_t restore_gw;
+
+// the entry that holds item i: the largest k with pre[k] <= i (empty entries share their successor's prefix; pre[n_tab ..] = all items)
+__device__ __forceinline__ int restore_entry_of(const unsigned *pre, unsigned i) {
+  int k = 0;
+#pragma unroll
+  for (int step = kRestoreMaxEntries / 2; step; step >>= 1)
+    if (pre[k + step] <= i) k += step;
+  return k;
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void k_restore_compact(const DrlgxField *__restrict__ tab, int n_tab, int n16, int src_off,
+                                                       const int *__restrict__ cnt, int *jc_meta) {
+  __shared__ unsigned pre[kRestoreMaxEntries + 1];  // pre[k]: items in front of entry k
+  __shared__ uintptr_t src_of[kRestoreMaxEntries], dst_of[kRestoreMaxEntries];  // the instances' slices of entry k
+  const int d = blockIdx.x, s = d + src_off, tid = threadIdx.x;
+  if (tid < 64) {
+    // one round trip: the lane's table entry, the source's counts and its panel header are requested together, by lane-indexed
+    // loads that are handed round afterwards (left as uniform loads they are sunk into the branches that use them, each behind
+    // the table's; an engine without panels reads the counts' row in the header's place - no branch between the loads)
+    const DrlgxField f = tab[tid < n_tab ? tid : n_tab - 1];
+    const int *c = cnt + (size_t)s * DRLGX_CNT_STRIDE;
+    const int *ms = jc_meta ? jc_meta + (size_t)s * 4 : c;
+    static_assert(DRLGX_CNT_STRIDE == 8, "the lanes read the counts' row by tid & 7");
+    const int cv = c[tid & 7], hv = ms[tid & 3];
+    const int cP = __shfl(cv, C_P), cL = __shfl(cv, C_L), cM = __shfl(cv, C_M);
+    const int valid = jc_meta ? __shfl(hv, 0) & ~kPanelInSrc : 0, mP = __shfl(hv, 1), mL = __shfl(hv, 2), mM = __shfl(hv, 3);
+    unsigned items = 0;
+    if (tid < n_tab) {
+      const int count = f.unit == 1 ? cP : f.unit == 2 ? cL : f.unit == 3 ? cM : valid == 1 ? mP : 0;
+      items = (unsigned)drlgx_field_items(f.stride, drlgx_field_live_bytes(f.stride, f.unit, f.unit_bytes, f.pad, count));
+      src_of[tid] = reinterpret_cast<uintptr_t>(f.base + (size_t)s * f.stride);
+      dst_of[tid] = reinterpret_cast<uintptr_t>(f.base + (size_t)d * f.stride);
+    }
+    unsigned incl = items;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_up(incl, o);
+      if (tid >= o) incl += up;
+    }
+    if (tid <= kRestoreMaxEntries) pre[tid] = incl - items;  // (lanes behind the table hold no items: their prefix is the total)
+    if (tid == 0 && jc_meta) {  // copy_panel_part's mode 2: a valid panel's body stays in s, and the header says so
+      int *md = jc_meta + (size_t)d * 4;
+      md[0] = valid == 1 ? (valid | kPanelInSrc) : valid; md[1] = mP; md[2] = mL; md[3] = mM;
+    }
+  }
+  __syncthreads();
+  const unsigned N16 = pre[n16], N = pre[kRestoreMaxEntries];
+  for (unsigned a = tid, b = N16 + tid; a < N16 || b < N; a += T * kRestoreDepth, b += T * kRestoreWordDepth) {
+    // (the searches of a trip are independent and unguarded, so that their LDS reads overlap; the values stay in registers)
+    int kv[kRestoreDepth], kw[kRestoreWordDepth];
+#pragma unroll
+    for (int j = 0; j < kRestoreDepth; ++j) kv[j] = restore_entry_of(pre, a + j * T);
+#pragma unroll
+    for (int j = 0; j < kRestoreWordDepth; ++j) kw[j] = restore_entry_of(pre, b + j * T);
+    restore_q v[kRestoreDepth];
+    restore_gq *vp[kRestoreDepth];
+    uint32_t w[kRestoreWordDepth];
+    restore_gw *wp[kRestoreWordDepth];
+#pragma unroll
+    for (int j = 0; j < kRestoreDepth; ++j) {
+      const unsigned i = a + j * T;
+      const size_t off = i - pre[kv[j]];
+      const restore_gq *sp = (const restore_gq *)src_of[kv[j]] + off;
+      vp[j] = (restore_gq *)dst_of[kv[j]] + off;
+      v[j] = restore_q{0, 0, 0, 0};
+      if (i < N16) v[j] = *sp;
+    }
+#pragma unroll
+    for (int j = 0; j < kRestoreWordDepth; ++j) {
+      const unsigned i = b + j * T;
+      const size_t off = i - pre[kw[j]];
+      const restore_gw *sp = (const restore_gw *)src_of[kw[j]] + off;
+      wp[j] = (restore_gw *)dst_of[kw[j]] + off;
+      w[j] = 0;
+      if (i < N) w[j] = *sp;
+    }
+#pragma unroll
+    for (int j = 0; j < kRestoreDepth; ++j)
+      if (a + j * T < N16) *vp[j] = v[j];
+#pragma unroll
+    for (int j = 0; j < kRestoreWordDepth; ++j)
+      if (b + j * T < N) *wp[j] = w[j];
   }
 }
 
@@ -483,6 +590,12 @@ void drlgx_launch_copy(const DrlgxField *fields_dev, int n_fields, hipStream_t s
   hipLaunchKernelGGL(k_copy_instances, cgrid, dim3(256), 0, st, fields_dev, n_fields, src, dst,
                      src_off, dst_off, skip_mask, only_cls, cnt, with_panel ? *panel : DrlgxState{}, with_panel ? panel_mode : 0);
 }
+void drlgx_launch_restore_compact(const DrlgxField *tab_dev, int n_tab, int n16, hipStream_t st, int n, int src_off, const int *cnt,
+                                  int *jc_meta) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_restore_compact<kRestoreThreads>, dim3(n), dim3(kRestoreThreads), 0, st, tab_dev, n_tab, n16, src_off, cnt, jc_meta);
+}
+int drlgx_restore_items_per_trip() { return kRestoreThreads * kRestoreDepth; }
 void drlgx_launch_fetch_pack(const DrlgxState &S, hipStream_t st, const void *src, size_t bytes, void *out) {
   const size_t head = drlgx_fetch_head_bytes(S.n_envs);
   const int blocks = (int)std::min<size_t>(256, (head + bytes + 4095) / 4096);

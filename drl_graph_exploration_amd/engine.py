@@ -632,6 +632,16 @@ class Engine(object):
         self._chk(self.L.drlgx_debug_panel_host(self.h, inst, meta.ctypes.data_as(ipt), body.ctypes.data_as(dpt), body.size))
         return meta, body
 
+    def restore_table(self):
+        """Development aid: (info, rows) of the compact restore's table - info = dict(entries, entries_16, in_use, items_per_trip),
+        rows [entries][4] = (bytes per instance, unit, bytes per unit, sub-slice bytes) as drlgx_debug_restore_table_host lists them."""
+        info = np.zeros(4, dtype=np.int32)
+        ipt, lpt = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(self.L.drlgx_debug_restore_table_host(self.h, info.ctypes.data_as(ipt), None, 0))
+        rows = np.zeros((int(info[0]), 4), dtype=np.int64)
+        self._chk(self.L.drlgx_debug_restore_table_host(self.h, info.ctypes.data_as(ipt), rows.ctypes.data_as(lpt), rows.shape[0]))
+        return dict(entries=int(info[0]), entries_16=int(info[1]), in_use=bool(info[2]), items_per_trip=int(info[3])), rows
+
     def snapshot_instance(self, slot, env):
         """Instance index of env `env` in snapshot slot `slot` (the getters take any instance)."""
         return 2 * self.n_envs + self.n_rollouts + slot * self.n_envs + env

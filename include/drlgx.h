@@ -630,6 +630,18 @@ int drlgx_inc_stats_host(drlgx_engine *e, int64_t out[2], int reset);
  * rows first); panel_cap: doubles the buffer holds.  Like every getter it first settles what a lazy restore owes. */
 int drlgx_debug_panel_host(drlgx_engine *e, int inst, int32_t meta[4], double *panel, size_t panel_cap);
 
+/* The compact restore (csrc/k_misc.hip: k_restore_compact): a lazy drlgx_restore by one workgroup per environment over a table of
+ * the entries it copies.  On by default; DRLGX_RESTORE_COMPACT=0 in the environment of drlgx_create selects the generic
+ * instance-copy kernel (both are bit-equal), as does DRLGX_RESTORE_EAGER=1.
+ * Development aid: the table.  info[4] = {entries, how many of them (the first) are moved as 16-byte items - the others as 4-byte
+ * words, 1 when drlgx_restore launches the compact kernel, items a workgroup moves per trip of its loop (threads x loads in
+ * flight, the 16-byte kind)}; rows (may be NULL; rows_cap: entries it holds) receives per entry {bytes per instance, unit (0 whole
+ * slice, 1 / 2 / 3 per pose / landmark / factor, 4 per pose of a valid covariance panel), bytes per unit, sub-slice bytes or 0}. */
+int drlgx_debug_restore_table_host(const drlgx_engine *e, int32_t info[4], int64_t *rows, int rows_cap);
+/* Development aid, stateless and host-only: the bytes of a table entry's slice an instance copy moves when the source instance
+ * counts `count` of the entry's unit (the formula every copy kernel uses), so that a CPU test can hold it against its own. */
+int64_t drlgx_debug_field_live_bytes(int64_t stride, int unit, int unit_bytes, int pad, int count);
+
 /* ---- GCN policy (scripts/Networks.py:12-70 over PyG GCNConv(improved=True)) ------------------- */
 
 /* Forward of GCN / PolicyGCN trunk: H1 = relu(Â X W1 + b1), H2 = relu(Â H1 W2 + b2) [* dropout mask],
