@@ -772,19 +772,20 @@ void drlgx_launch_fix_rollouts(const DrlgxState &S, hipStream_t st, int n_cand, 
 void drlgx_launch_rewards(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, int roll0,
                           double *rewards);
 void drlgx_launch_utility(const DrlgxState &S, hipStream_t st, const double *dist, double *out, int mode);
-// FastMarginals2 (k_fm2.hip): dense prior covariance per environment, then the per-candidate update
-void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, const int32_t *env_ids, int n_env, double *sig, size_t sig_stride,
-                            int n_max);
-size_t drlgx_fm2_scratch_doubles(const DrlgxState &S, int nm_max);
+// FastMarginals2 (k_fm2.hip): dense prior covariance of every environment (sig [n_envs][sig_stride], one workgroup each), then the
+// per-candidate update.  The measurement cap kFm2MaxMeas and the layout of a candidate's scratch are fm2_carve.h's.
+void drlgx_launch_fm2_prior(const DrlgxState &S, hipStream_t st, double *sig, size_t sig_stride, int n_max);
+size_t drlgx_fm2_scratch_doubles(const DrlgxState &S);  // doubles of one candidate's scratch (Fm2Scratch::total at the cap)
 // flag[0] (zeroed by the caller) = DRLGX_E_INVALID / DRLGX_E_CAPACITY if a candidate names no environment, has more than max_actions
-// actions or more than nm_max predicted measurements.  core ([candidate][max_actions] or null = every action): the actions that are
-// core poses - a non-core step extends the chain and predicts no measurement (null launches the kernel without the mask)
+// actions or more than kFm2MaxMeas predicted measurements.  core ([candidate][max_actions] or null = every action): the actions that
+// are core poses - a non-core step extends the chain and predicts no measurement (null launches the kernel without the mask)
 void drlgx_launch_fm2_check(const DrlgxState &S, hipStream_t st, int n_cand, const int32_t *cand_env, const double *actions,
-                            const int32_t *n_actions, const uint8_t *core, int nm_max, int *flag);
-void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int c0, int nc, const int32_t *cand_env, const int32_t *env_slot,
-                             const double *actions, const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride,
-                             double *scratch, size_t scratch_stride, int *iscratch, int nm_max, double *cov_out, int out_stride,
-                             int32_t *n_out, double *lm_out = nullptr, int lm_stride = 0);
+                            const int32_t *n_actions, const uint8_t *core, int *flag);
+// nc candidates, one workgroup each; every candidate array and output starts at the launch's first candidate.  scratch / iscratch:
+// nc x Fm2Scratch::total doubles / ::itotal ints at the cap.
+void drlgx_launch_fm2_update(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
+                             const int32_t *n_actions, const uint8_t *core, const double *sig, size_t sig_stride, double *scratch,
+                             int *iscratch, double *cov_out, int out_stride, int32_t *n_out, double *lm_out = nullptr, int lm_stride = 0);
 // lm_out ([nc][lm_stride][3], or null = the kernel without them): the landmarks' updated 2x2 blocks (xx, xy, yy per slot) as well.
 // drlgx_launch_fm2_prior_ordered: drlgx_launch_fm2_prior for every environment with a fixed summation order (no atomics) - the same
 // belief gives the same bits (drlgx_slam_og_cost).

@@ -16,6 +16,7 @@
 
 #include "drlgx_dev.h"
 #include "drlgx_fields.h"
+#include "fm2_carve.h"
 
 #define HIPCHK(e, call)                                                                       \
   do {                                                                                        \
@@ -85,13 +86,11 @@ struct drlgx_engine {
   // FastMarginals2 workspaces (allocated on first use): dense prior covariances, per-candidate scratch
   double *fm2_sig = nullptr, *fm2_scratch = nullptr;
   int *fm2_iscratch = nullptr;
-  int32_t *fm2_slot = nullptr;
-  size_t fm2_sig_stride = 0, fm2_scratch_stride = 0;
-  // drlgx_em_cost (allocated on first use): the covariances and pose counts of one chunk of candidates, the argument check's flag
+  size_t fm2_sig_stride = 0;
+  // drlgx_em_cost (allocated on first use): the covariances and pose counts of one chunk of candidates
   double *em_cov = nullptr;
   int32_t *em_nout = nullptr;
-  int *em_flag = nullptr;
-  int *og_flag = nullptr;  // drlgx_og_cost's argument check (allocated on first use)
+  int *check_flag = nullptr;  // the argument checks' flag word (run_check; allocated on first use)
   // drlgx_slam_og_cost (allocated on first use / grown on demand): the root weights [n_envs][2], one chunk's landmark blocks
   // [kFm2Chunk][L_max][3]; per candidate the leaf entropy [cap] and the cost's distance factors [cap][2]
   double *sog_weights = nullptr, *sog_lm = nullptr, *sog_h = nullptr, *sog_dist = nullptr;
@@ -1088,8 +1087,9 @@ static int scratch_reserve(drlgx_engine *e, T **p, size_t count) {
 }
 
 // FastMarginals2::update for candidate action lists (k_fm2.hip)
-static const int kFm2Chunk = 128, kFm2MaxMeas = 256;
-// What both entries below do with their candidates: the workspaces on first use, the prior covariance of every environment, then
+static const int kFm2Chunk = 128;
+using kfm2::kFm2MaxMeas;
+// What the entries below do with their candidates: the workspaces on first use, the prior covariance of every environment, then
 // one update launch per kFm2Chunk candidates.  cov_out / n_out hold all n_cand candidates - or, chunk_out, only the chunk at hand,
 // which after(c0, nc) consumes on the engine's stream before the next chunk's launch overwrites it.  lm_out (null: the kernels as
 // they were without it): the landmark blocks as well, [.][L_max][3], all candidates or (lm_chunk) the chunk at hand; the prior is
@@ -1101,26 +1101,19 @@ static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, con
   if (!e->fm2_sig) {
     const size_t nmax = (size_t)3 * S.P_max + 2 * S.L_max;
     e->fm2_sig_stride = nmax * nmax;
-    e->fm2_scratch_stride = drlgx_fm2_scratch_doubles(S, kFm2MaxMeas);
     int r;
     if ((r = dev_alloc(e, &e->fm2_sig, e->fm2_sig_stride * (size_t)S.n_envs))) return r;
-    if ((r = dev_alloc(e, &e->fm2_scratch, e->fm2_scratch_stride * (size_t)kFm2Chunk))) return r;
-    if ((r = dev_alloc(e, &e->fm2_iscratch, (size_t)2 * kFm2MaxMeas * kFm2Chunk))) return r;
-    if ((r = dev_alloc(e, &e->fm2_slot, (size_t)S.n_envs))) return r;
-    std::vector<int32_t> ident(S.n_envs);
-    for (int i = 0; i < S.n_envs; ++i) ident[i] = i;
-    HIPCHK(e, hipMemcpyAsync(e->fm2_slot, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((r = dev_alloc(e, &e->fm2_scratch, drlgx_fm2_scratch_doubles(S) * (size_t)kFm2Chunk))) return r;
+    if ((r = dev_alloc(e, &e->fm2_iscratch, kfm2::Fm2Scratch(S.A_max, kFm2MaxMeas).itotal * (size_t)kFm2Chunk))) return r;
   }
   if (lm_out)
     drlgx_launch_fm2_prior_ordered(S, e->stream, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
   else
-    drlgx_launch_fm2_prior(S, e->stream, nullptr, S.n_envs, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
+    drlgx_launch_fm2_prior(S, e->stream, e->fm2_sig, e->fm2_sig_stride, 3 * S.P_max + 2 * S.L_max);
   for (int c0 = 0; c0 < n_cand; c0 += kFm2Chunk) {
     const int nc = std::min(kFm2Chunk, n_cand - c0);
-    // (the launch's first candidate through the pointers: the kernel's own offset stays 0)
-    drlgx_launch_fm2_update(S, e->stream, 0, nc, cand_env_dev + c0, e->fm2_slot, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
-                            core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_scratch_stride, e->fm2_iscratch, kFm2MaxMeas,
+    drlgx_launch_fm2_update(S, e->stream, nc, cand_env_dev + c0, actions_dev + (size_t)c0 * S.A_max * 3, n_actions_dev + c0,
+                            core_dev ? core_dev + (size_t)c0 * S.A_max : nullptr, e->fm2_sig, e->fm2_sig_stride, e->fm2_scratch, e->fm2_iscratch,
                             chunk_out ? cov_out : cov_out + (size_t)c0 * out_stride_poses * 9, out_stride_poses,
                             chunk_out ? n_out : n_out + c0, (!lm_out || lm_chunk) ? lm_out : lm_out + (size_t)c0 * S.L_max * 3, S.L_max);
     after(c0, nc);
@@ -1128,18 +1121,7 @@ static int fm2_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, con
   return check_launch(e);
 }
 
-int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                     double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
-  DRLGX_ENTER(e);
-  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !cov_out_dev || !n_out_dev ||
-      out_stride_poses < e->S.P_max + e->S.A_max)
-    return DRLGX_E_INVALID;
-  if (n_cand == 0) return DRLGX_OK;
-  return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, cov_out_dev, out_stride_poses, n_out_dev, false,
-                 [](int, int) {});
-}
-
-// drlgx_fm2_update with a core mask: a non-core step gets its pose and its odometry factor and predicts no measurement
+// core_dev (null: every action is a core pose): a non-core step gets its pose and its odometry factor and predicts no measurement
 int drlgx_fm2_update_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                            const uint8_t *core_dev, double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
   DRLGX_ENTER(e);
@@ -1150,31 +1132,41 @@ int drlgx_fm2_update_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_
   return fm2_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, cov_out_dev, out_stride_poses, n_out_dev, false,
                  [](int, int) {});
 }
+int drlgx_fm2_update(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                     double *cov_out_dev, int out_stride_poses, int32_t *n_out_dev) {
+  return drlgx_fm2_update_steps(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, cov_out_dev, out_stride_poses, n_out_dev);
+}
+
+// One check launch and its answer: the flag word zeroed, launch(flag) on the engine's stream, the flag read back - the smallest
+// DRLGX_E_* code a candidate earns, 0 if none does.  The read is a call's single synchronisation.
+static int run_check(drlgx_engine *e, const std::function<void(int *)> &launch) {
+  if (!e->check_flag) {
+    if (int r = dev_alloc(e, &e->check_flag, (size_t)1)) return r;
+  }
+  int flag = 0;
+  HIPCHK(e, hipMemsetAsync(e->check_flag, 0, sizeof(int), e->stream));
+  launch(e->check_flag);
+  HIPCHK(e, hipMemcpyAsync(&flag, e->check_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return flag;
+}
 
 // The leaf evaluation of EMPlanner2D::optimize2 for candidate action lists: the covariance update above into the engine's scratch,
 // a chunk at a time, and k_em.hip on each chunk.  What the kernels could only report through the status word - a candidate that
-// names no environment, a plan beyond max_actions, more than kFm2MaxMeas predicted measurements - is found out first (one small
-// launch and one read of its flag), so that such a call returns its code and leaves the status word alone.  core_dev / distance_dev
-// (either may be null): the leaves of a tree whose edges have non-core steps - only core poses predict measurements and enter the
-// leaf's map, the cost takes the tree's distance.
-// The chunk workspaces of em_cost_run (on first use) and its check of the candidates: the smallest DRLGX_E_* code a candidate earns,
-// 0 if none does (one small launch, one read of its flag: the call's single synchronisation).
+// names no environment, a plan beyond max_actions, more than kFm2MaxMeas predicted measurements - is found out first (run_check),
+// so that such a call returns its code and leaves the status word alone.  core_dev / distance_dev (either may be null): the leaves
+// of a tree whose edges have non-core steps - only core poses predict measurements and enter the leaf's map, the cost takes the
+// tree's distance.
+// The chunk workspaces of em_cost_run (on first use) and its check of the candidates.
 static int em_cost_check(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                          const uint8_t *core_dev) {
   const DrlgxState &S = e->S;
-  const int stride = S.P_max + S.A_max;
   if (!e->em_cov) {
     int r;
-    if ((r = dev_alloc(e, &e->em_cov, (size_t)kFm2Chunk * stride * 9))) return r;
+    if ((r = dev_alloc(e, &e->em_cov, (size_t)kFm2Chunk * (S.P_max + S.A_max) * 9))) return r;
     if ((r = dev_alloc(e, &e->em_nout, (size_t)kFm2Chunk))) return r;
-    if ((r = dev_alloc(e, &e->em_flag, (size_t)1))) return r;
   }
-  int flag = 0;
-  HIPCHK(e, hipMemsetAsync(e->em_flag, 0, sizeof(int), e->stream));
-  drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, kFm2MaxMeas, e->em_flag);
-  HIPCHK(e, hipMemcpyAsync(&flag, e->em_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  return flag;
+  return run_check(e, [&](int *flag) { drlgx_launch_fm2_check(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, flag); });
 }
 
 static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
@@ -1191,17 +1183,6 @@ static int em_cost_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev,
   });
 }
 
-int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
-                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
-  DRLGX_ENTER(e);
-  if (!e || n_cand < 0 || !cand_env_dev || !actions_dev || !n_actions_dev || (!uncertainty_out_dev && !cost_out_dev) ||
-      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
-    return DRLGX_E_INVALID;
-  if (n_cand == 0) return DRLGX_OK;
-  return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, nullptr, algorithm, uncertainty_out_dev, cost_out_dev,
-                     info_out_dev);
-}
-
 int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                         const uint8_t *core_dev, const double *distance_dev, int algorithm, double *uncertainty_out_dev,
                         double *cost_out_dev, double *info_out_dev) {
@@ -1212,6 +1193,11 @@ int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev
   if (n_cand == 0) return DRLGX_OK;
   return em_cost_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, distance_dev, algorithm, uncertainty_out_dev,
                      cost_out_dev, info_out_dev);
+}
+int drlgx_em_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                  int algorithm, double *uncertainty_out_dev, double *cost_out_dev, double *info_out_dev) {
+  return drlgx_em_cost_steps(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, nullptr, nullptr, algorithm, uncertainty_out_dev,
+                             cost_out_dev, info_out_dev);
 }
 
 // calculateUncertainty_OG_SHANNON + costFunction for candidate action lists (k_og.hip).  The candidates are checked first, as in
@@ -1225,16 +1211,7 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
   if (!cand_env_dev || !actions_dev || !n_actions_dev || (!entropy_out_dev && !cost_out_dev)) return DRLGX_E_INVALID;
   const DrlgxState &S = e->S;
   if (drlgx_og_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
-  if (!e->og_flag) {
-    int r;
-    if ((r = dev_alloc(e, &e->og_flag, (size_t)1))) return r;
-  }
-  int flag = 0;
-  HIPCHK(e, hipMemsetAsync(e->og_flag, 0, sizeof(int), e->stream));
-  drlgx_launch_og_check(S, e->stream, n_cand, cand_env_dev, n_actions_dev, e->og_flag);
-  HIPCHK(e, hipMemcpyAsync(&flag, e->og_flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  if (flag) return flag;
+  if (int flag = run_check(e, [&](int *f) { drlgx_launch_og_check(S, e->stream, n_cand, cand_env_dev, n_actions_dev, f); })) return flag;
   drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, entropy_out_dev, cost_out_dev, prob_out_dev);
   return check_launch(e);
 }
