@@ -421,8 +421,12 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
     }
     __syncthreads();
     if (b0 == 0) DRLGX_PROF(S, 36);
-    // B2. T = R + A Y (symmetric by construction), v = -e - A delta, W' = -T^-1: one wave
-    if (wave == 0) {
+    // B2. T = R + A Y (symmetric by construction), v = -e - A delta: every thread one or two entries; W' = -T^-1: one wave
+    const int kA = kWide ? 16 : k;
+    // T in 16 x 16 tiles [A B; B^T D], staged row-major (stride 16) where W' goes afterwards: A (lower triangle) at wks, B at
+    // wks + 256 (row = row of A, column = column of D), D (lower triangle) at wks + 512.  Wave 0 has all three in registers before it
+    // stores the first operand image, and the previous batch's tile pass - the images' last reader - ended at a barrier.
+    {
       // entry (i, j), i >= j, of T: row i = (factor i / 2, bearing or range), column j of Y (in the half j / 16)
       auto tent = [&](int i, int j) -> double {
         const int t = fre[b0 + (i >> 1)], u = i & 1;
@@ -434,22 +438,38 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
         if (i == j) sv += u ? Rr : Rb;
         return sv;
       };
-      if (lane < (kWide ? 32 : 16)) {
-        double v = 0.0;
-        if (lane < k) {
-          const int t = fre[b0 + (lane >> 1)], u = lane & 1;
-          const double *rc = recs + (size_t)REC * t;
-          const double *dp = dl + 3 * pn, *dq = dl + 3 * P + 2 * fslot[t];
-          v = -rc[10 + u] - (rc[3 * u] * dp[0] + rc[3 * u + 1] * dp[1] + rc[3 * u + 2] * dp[2] + rc[6 + 2 * u] * dq[0] + rc[7 + 2 * u] * dq[1]);
+      // threads 0 .. 255: entry (ti, tj) of A, then of D; threads 256 .. 511: of B (wide), the first of them v
+      static_assert(kThreads == 512, "B2 deals the entries of T over 2 x 256 threads");
+      const int ti = (tid >> 4) & 15, tj = tid & 15;
+      if (tid < 256) {
+        if (ti >= tj && ti < kA) wks[tid] = tent(ti, tj);
+        if constexpr (kWide) {
+          if (ti >= tj && ti < kD) wks[512 + tid] = tent(16 + ti, 16 + tj);
         }
-        vvec[(lane & 16) + ks16(lane & 15)] = v;  // (ks16 order per half, like the rows of Y)
+      } else {
+        if constexpr (kWide) {
+          if (tj < kD) wks[tid] = tent(16 + tj, ti);  // B[ti][tj] = T[ti][16 + tj]
+        }
+        const int l = tid - 256;
+        if (l < (kWide ? 32 : 16)) {
+          double v = 0.0;
+          if (l < k) {
+            const int t = fre[b0 + (l >> 1)], u = l & 1;
+            const double *rc = recs + (size_t)REC * t;
+            const double *dp = dl + 3 * pn, *dq = dl + 3 * P + 2 * fslot[t];
+            v = -rc[10 + u] - (rc[3 * u] * dp[0] + rc[3 * u + 1] * dp[1] + rc[3 * u + 2] * dp[2] + rc[6 + 2 * u] * dq[0] + rc[7 + 2 * u] * dq[1]);
+          }
+          vvec[(l & 16) + ks16(l & 15)] = v;  // (ks16 order per half, like the rows of Y)
+        }
       }
-      const int kA = kWide ? 16 : k;
+    }
+    __syncthreads();
+    if (wave == 0) {
       v4d d = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lr + 4 * r, hi = max(i, lc), lo = min(i, lc);
-        if (hi < kA) d[r] = tent(hi, lo);
+        if (hi < kA) d[r] = wks[16 * hi + lo];
       }
       const SweepCtx sx{0, lane, lc, lr, kA, 16, true, true, ictl + 1, nullptr};
       if constexpr (!kWide) {
@@ -467,8 +487,8 @@ __device__ __forceinline__ bool inc_post(const DrlgxState &S, const IncCtx &x, i
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = lr + 4 * r, hi = max(i, lc), lo = min(i, lc);
-          if (lc < kD) tb[r] = tent(16 + lc, i);          // B[i][lc] = T[i][16 + lc]
-          if (hi < kD) td[r] = tent(16 + hi, 16 + lo);    // D
+          if (lc < kD) tb[r] = wks[256 + 16 * i + lc];    // B[i][lc] = T[i][16 + lc]
+          if (hi < kD) td[r] = wks[512 + 16 * hi + lo];   // D
         }
         inv16_blk<false>(sx, 16, d);  // A'
         double a4[4] = {d[0], d[1], d[2], d[3]}, b4[4] = {tb[0], tb[1], tb[2], tb[3]};
