@@ -33,7 +33,7 @@ SYMBOLS = [
     "drlgx_create", "drlgx_destroy", "drlgx_set_stream", "drlgx_synchronize", "drlgx_strerror", "drlgx_last_error",
     "drlgx_status_host", "drlgx_status_fetch_host", "drlgx_reset_host", "drlgx_step", "drlgx_utility", "drlgx_uncertainty_em", "drlgx_explored", "drlgx_metrics", "drlgx_cov_array",
     "drlgx_stage_reset_host", "drlgx_stage_set_prior_information_host", "drlgx_stage_set_prior_pose_host", "drlgx_stage_move", "drlgx_stage_measure", "drlgx_stage_add_measurements", "drlgx_stage_optimize",
-    "drlgx_stage_update_map", "drlgx_set_planner_parameter", "drlgx_set_fixed_landmarks_host", "drlgx_fm2_update", "drlgx_fm2_update_steps", "drlgx_em_cost", "drlgx_em_cost_steps", "drlgx_set_dubins_leaf_scoring", "drlgx_em_plan_leaves", "drlgx_og_cost", "drlgx_slam_og_cost", "drlgx_set_sampler_parameter", "drlgx_set_sampler_obstacles", "drlgx_set_dubins_library_host", "drlgx_dubins_library", "drlgx_set_dubins_prefilter", "drlgx_em_plan", "drlgx_rrt_plan", "drlgx_step_plan", "drlgx_step_plans", "drlgx_step_plans_traced",
+    "drlgx_stage_update_map", "drlgx_set_planner_parameter", "drlgx_set_fixed_landmarks_host", "drlgx_fm2_update", "drlgx_fm2_update_steps", "drlgx_em_cost", "drlgx_em_cost_steps", "drlgx_set_dubins_leaf_scoring", "drlgx_em_plan_leaves", "drlgx_og_cost", "drlgx_slam_og_cost", "drlgx_set_sampler_parameter", "drlgx_set_sampler_obstacles", "drlgx_set_dubins_library_host", "drlgx_dubins_library", "drlgx_set_dubins_prefilter", "drlgx_em_plan", "drlgx_og_plan", "drlgx_rrt_plan", "drlgx_step_plan", "drlgx_step_plans", "drlgx_step_plans_traced",
     "drlgx_line_plan", "drlgx_lookahead", "drlgx_lookahead_bounded", "drlgx_graph_capacity", "drlgx_graph", "drlgx_get_counts_host", "drlgx_counts",
     "drlgx_get_poses_host", "drlgx_get_landmarks_host", "drlgx_get_cov_traces_host", "drlgx_vm_shape",
     "drlgx_get_virtual_map_host", "drlgx_get_ground_truth_host", "drlgx_get_adjacency_host", "drlgx_get_factors_host",
@@ -108,6 +108,7 @@ def lib():
     L.drlgx_dubins_library.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
     L.drlgx_set_dubins_prefilter.argtypes = [vp, C.c_int]
     L.drlgx_em_plan.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int] + [vp] * 8
+    L.drlgx_og_plan.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_double] + [vp] * 8
     L.drlgx_rrt_plan.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int] + [vp] * 6
     L.drlgx_utility.argtypes = [vp, vp, vp]
     L.drlgx_uncertainty_em.argtypes = [vp, C.c_int, vp]

@@ -806,6 +806,12 @@ void drlgx_launch_og_check(const DrlgxState &S, hipStream_t st, int n_cand, cons
 void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int32_t *cand_env, const double *actions,
                           const int32_t *n_actions, double *ent_out, double *cost_out, double *prob_out, double *dist_out = nullptr);
 // dist_out ([nc][2] or null): the plan's distance and the distance weight, the factors of the cost's second term.
+// The same outputs for the leaves of sampling trees, bit for bit (k_og_tree_base + k_og_tree_cost): env_sel [n_sel] the trees'
+// environments - every candidate's environment is among them -, whose shared part (landmarks, old poses, known cells) is walked once
+// into base [n_envs][Vu] / known [n_envs]; then one workgroup per leaf over its new poses.  Needs drlgx_og_lds_bytes within the LDS.
+void drlgx_launch_og_tree_cost(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, int nc, const int32_t *cand_env,
+                               const double *actions, const int32_t *n_actions, uint8_t *base, int32_t *known, double *ent_out,
+                               double *cost_out, double *dist_out);
 // The SLAM-OG-Shannon cost (k_og.hip): the root's weights [n_envs][2] = w1, w2 from the live belief; then, per candidate, the blend of
 // the entropy that drlgx_launch_og_cost left (h_leaf [nc], dist [nc][2]) with sum_l sqrt(det) of the landmark blocks that
 // drlgx_launch_fm2_update left (lm_cov [nc][lm_stride][3]); distance ([nc] or null): the caller's distance instead of the plan's own.

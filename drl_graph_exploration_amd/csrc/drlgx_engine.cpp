@@ -95,6 +95,12 @@ struct drlgx_engine {
   // [kFm2Chunk][L_max][3]; per candidate the leaf entropy [cap] and the cost's distance factors [cap][2]
   double *sog_weights = nullptr, *sog_lm = nullptr, *sog_h = nullptr, *sog_dist = nullptr;
   size_t sog_cap = 0;
+  // drlgx_og_plan (allocated on first use): what the leaves of a tree share - per environment the ladder state of every cell after
+  // the landmarks and the old poses [n_envs][Vu], and the known cells of the live map [n_envs] (k_og_tree_base).
+  // DRLGX_OG_TREE_SHARED=0: the leaves are scored by k_og_cost, each from the untouched map (the A/B of the shared base)
+  uint8_t *og_base = nullptr;
+  int32_t *og_known = nullptr;
+  bool og_tree_shared = true;
   // drlgx_em_plan / drlgx_rrt_plan (grown on demand): the trees' tables (edge odometry, parent and depth, leaf list, per-tree
   // results), the leaves as candidates of drlgx_em_cost with their costs; the sampler's own planner parameters
   double *tree_act = nullptr, *tree_cand_act = nullptr, *tree_cost = nullptr;
@@ -283,6 +289,7 @@ static void read_env_switches(drlgx_engine *e) {
   e->la_loop = env_flag("DRLGX_LOOKAHEAD_LOOP", true);  // 0: one launch per action index (the A/B of the look-ahead tests)
   e->restore_eager = env_flag("DRLGX_RESTORE_EAGER", false);  // 1: a restore copies the virtual-map planes and panel bodies too (the A/B of the lazy restore)
   e->restore_compact = env_flag("DRLGX_RESTORE_COMPACT", true);  // 0: a lazy restore by the generic copy kernel (the A/B of the compact restore)
+  e->og_tree_shared = env_flag("DRLGX_OG_TREE_SHARED", true);  // 0: drlgx_og_plan scores its leaves with k_og_cost (the A/B of the shared base)
 }
 
 static double p2l(double p) { return std::log(p / (1.0 - p)); }
@@ -1219,13 +1226,32 @@ int drlgx_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, cons
 // calculateUncertainty_SLAM_OG_SHANNON + costFunction for candidate action lists: the root's weights from the live belief, the leaf
 // entropy of every candidate (k_og.hip, one launch, as drlgx_og_cost), then the fm2 update with its landmark blocks a chunk at a time
 // and the blend on each chunk.  The candidates are checked first exactly as em_cost_run checks them - the call's one synchronisation.
-int drlgx_slam_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+// The entropy, cost and distance factors (any of them null) of candidates that are the leaves of sampling trees over env_sel [n_sel]:
+// the part the leaves of a tree share once per environment, then the leaves (k_og_tree_base + k_og_tree_cost) - or, under
+// DRLGX_OG_TREE_SHARED=0, k_og_cost on every leaf.  The same bits either way.
+static int og_tree_leaves(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, int n_cand, const int32_t *cand_env_dev,
+                          const double *actions_dev, const int32_t *n_actions_dev, double *ent_out, double *cost_out, double *dist_out) {
+  const DrlgxState &S = e->S;
+  if (e->og_tree_shared && !e->og_base) {
+    int r;
+    if ((r = dev_alloc(e, &e->og_base, (size_t)S.n_envs * S.Vu))) return r;
+    if ((r = dev_alloc(e, &e->og_known, (size_t)S.n_envs))) return r;
+  }
+  ScopedTimer t(e, 6);  // (the A/B of profiles/og_plan_shared_vs_unshared.txt)
+  if (!e->og_tree_shared) {
+    drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, ent_out, cost_out, nullptr, dist_out);
+    return DRLGX_OK;
+  }
+  drlgx_launch_og_tree_cost(S, e->stream, n_sel, env_sel_dev, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->og_base, e->og_known,
+                            ent_out, cost_out, dist_out);
+  return DRLGX_OK;
+}
+
+// The body of drlgx_slam_og_cost.  tree_sel_dev [n_tree_sel] (or null): the candidates are the leaves of trees over these
+// environments (drlgx_og_plan) - their entropy comes from og_tree_leaves.
+static int slam_og_run(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
                        const uint8_t *core_dev, const double *distance_dev, double alpha, double *uncertainty_out_dev, double *cost_out_dev,
-                       double *terms_out_dev, double *weights_out_dev, double *lm_cov_out_dev) {
-  DRLGX_ENTER(e);
-  if (!e || n_cand <= 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !uncertainty_out_dev || !cost_out_dev ||
-      !(alpha >= 0.0 && alpha <= 1.0))
-    return DRLGX_E_INVALID;
+                       double *terms_out_dev, double *weights_out_dev, double *lm_cov_out_dev, int n_tree_sel, const int32_t *tree_sel_dev) {
   const DrlgxState &S = e->S;
   if (drlgx_og_lds_bytes(S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
   int r;
@@ -1241,15 +1267,30 @@ int drlgx_slam_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev,
   if (int flag = em_cost_check(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev)) return flag;
   double *weights = weights_out_dev ? weights_out_dev : e->sog_weights;
   drlgx_launch_slam_og_weights(S, e->stream, alpha, weights);
-  drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->sog_h, nullptr, nullptr, e->sog_dist);
+  if (!tree_sel_dev)
+    drlgx_launch_og_cost(S, e->stream, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->sog_h, nullptr, nullptr, e->sog_dist);
+  else if ((r = og_tree_leaves(e, n_tree_sel, tree_sel_dev, n_cand, cand_env_dev, actions_dev, n_actions_dev, e->sog_h, nullptr, e->sog_dist)))
+    return r;
   return fm2_run(
       e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, e->em_cov, S.P_max + S.A_max, e->em_nout, true,
       [&](int c0, int nc) {
         drlgx_launch_slam_og_blend(S, e->stream, nc, cand_env_dev + c0, lm_cov_out_dev ? lm_cov_out_dev + (size_t)c0 * S.L_max * 3 : e->sog_lm,
                                    S.L_max, e->sog_h + c0, e->sog_dist + (size_t)2 * c0, distance_dev ? distance_dev + c0 : nullptr, weights,
-                                   uncertainty_out_dev + c0, cost_out_dev + c0, terms_out_dev ? terms_out_dev + (size_t)2 * c0 : nullptr);
+                                   uncertainty_out_dev ? uncertainty_out_dev + c0 : nullptr, cost_out_dev + c0,
+                                   terms_out_dev ? terms_out_dev + (size_t)2 * c0 : nullptr);
       },
       lm_cov_out_dev ? lm_cov_out_dev : e->sog_lm, lm_cov_out_dev == nullptr);
+}
+
+int drlgx_slam_og_cost(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev, const double *actions_dev, const int32_t *n_actions_dev,
+                       const uint8_t *core_dev, const double *distance_dev, double alpha, double *uncertainty_out_dev, double *cost_out_dev,
+                       double *terms_out_dev, double *weights_out_dev, double *lm_cov_out_dev) {
+  DRLGX_ENTER(e);
+  if (!e || n_cand <= 0 || !cand_env_dev || !actions_dev || !n_actions_dev || !uncertainty_out_dev || !cost_out_dev ||
+      !(alpha >= 0.0 && alpha <= 1.0))
+    return DRLGX_E_INVALID;
+  return slam_og_run(e, n_cand, cand_env_dev, actions_dev, n_actions_dev, core_dev, distance_dev, alpha, uncertainty_out_dev, cost_out_dev,
+                     terms_out_dev, weights_out_dev, lm_cov_out_dev, 0, nullptr);
 }
 
 // ---- the EM planner's tree sampler (k_em_tree.hip) ----
@@ -1421,18 +1462,21 @@ static bool tree_args_ok(const drlgx_engine *e, int n_sel, const void *env_sel, 
          (!e->sampler_dubins || (e->dubins.n > 0 && (rrt || e->dubins_leaf_scoring)));
 }
 
-int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
-                  int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
-                  int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
-  DRLGX_ENTER(e);
-  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev, false) ||
-      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
-    return DRLGX_E_INVALID;
-  if (n_sel == 0) return DRLGX_OK;
+// What the outputs of a tree call point to (drlgx_em_plan's argument list)
+struct TreePlanOut {
+  double *plan, *cost, *nodes;
+  int32_t *n_actions, *result, *n_leaves, *halton_next, *n_nodes;
+};
+
+// optimize2 behind the entries' own argument checks: the trees (tree_grow: the call's first synchronisation), their leaves as
+// candidates in the engine's tables (k_em_leaves, or its Dubins form under the sampler's flag), score(n_cand, steps) - which leaves
+// every candidate's cost in e->tree_cost - and the pick.  What the entries differ in is `score` alone.
+static int tree_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                     const TreePlanOut &o, const std::function<int(int, bool)> &score) {
   const DrlgxState &S = e->S;
   std::vector<int> meta;
-  int r = tree_grow(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, 0, nullptr, nullptr, nodes_out_dev, n_nodes_out_dev,
-                    result_out_dev, halton_next_out_dev, meta);
+  int r = tree_grow(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, 0, nullptr, nullptr, o.nodes, o.n_nodes, o.result,
+                    o.halton_next, meta);
   if (r) return r;
   size_t n_cand = 0;
   for (int i = 0; i < n_sel; ++i) n_cand += (size_t)meta[(size_t)i * kTreeMeta + 1];
@@ -1460,19 +1504,59 @@ int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const 
       drlgx_launch_em_leaves(e->stream, n_sel, env_sel_dev, max_tree_nodes, S.A_max, e->tree_act, e->tree_link, e->tree_leaf, e->tree_meta,
                              0, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n);
     if ((r = check_launch(e))) return r;
-    if ((r = em_cost_run(e, (int)n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, steps ? e->tree_cand_core : nullptr,
-                         steps ? e->tree_cand_dist : nullptr, algorithm, nullptr, e->tree_cost, nullptr)))
-      return r;
+    if ((r = score((int)n_cand, steps))) return r;
     e->tree_cand_last = n_cand;
     e->tree_cand_last_steps = steps;
   }
-  drlgx_launch_em_pick(e->stream, n_sel, S.A_max, e->tree_meta, e->tree_cost, e->tree_cand_act, e->tree_cand_n, plan_out_dev,
-                       n_actions_out_dev, cost_out_dev, n_leaves_out_dev);
+  drlgx_launch_em_pick(e->stream, n_sel, S.A_max, e->tree_meta, e->tree_cost, e->tree_cand_act, e->tree_cand_n, o.plan, o.n_actions, o.cost,
+                       o.n_leaves);
   return check_launch(e);
 }
 
-// The leaves the last served drlgx_em_plan scored, as it handed them to the body of drlgx_em_cost_steps: device-to-device copies on
-// the engine's stream.
+int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                  int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
+                  int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev) {
+  DRLGX_ENTER(e);
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev, false) ||
+      (algorithm != DRLGX_ALG_EM_AOPT && algorithm != DRLGX_ALG_EM_DOPT))
+    return DRLGX_E_INVALID;
+  if (n_sel == 0) return DRLGX_OK;
+  const TreePlanOut out = {plan_out_dev, cost_out_dev, nodes_out_dev, n_actions_out_dev, result_out_dev, n_leaves_out_dev,
+                           halton_next_out_dev, n_nodes_out_dev};
+  return tree_plan(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, out, [&](int n_cand, bool steps) {
+    return em_cost_run(e, n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, steps ? e->tree_cand_core : nullptr,
+                       steps ? e->tree_cand_dist : nullptr, algorithm, nullptr, e->tree_cost, nullptr);
+  });
+}
+
+// optimize2 under OG_SHANNON / SLAM_OG_SHANNON: drlgx_em_plan's tree, leaves and pick (tree_plan), the leaves scored by og_tree_leaves
+// (algorithm 2: no check of the candidates - the tree's own flag has refused a leaf deeper than max_actions - and so no second
+// synchronisation) or by the body of drlgx_slam_og_cost (algorithm 3: its candidate check is the second one).
+int drlgx_og_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                  int algorithm, double alpha, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev,
+                  int32_t *result_out_dev, int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev,
+                  int32_t *n_nodes_out_dev) {
+  DRLGX_ENTER(e);
+  if (!tree_args_ok(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, plan_out_dev, n_actions_out_dev, false) ||
+      (algorithm != DRLGX_ALG_OG_SHANNON && algorithm != DRLGX_ALG_SLAM_OG_SHANNON) || e->sampler_dubins ||
+      (algorithm == DRLGX_ALG_SLAM_OG_SHANNON && !(alpha >= 0.0 && alpha <= 1.0)))
+    return DRLGX_E_INVALID;
+  if (n_sel == 0) return DRLGX_OK;
+  if (drlgx_og_lds_bytes(e->S) > (size_t)160 * 1024) return DRLGX_E_CAPACITY;
+  const TreePlanOut out = {plan_out_dev, cost_out_dev, nodes_out_dev, n_actions_out_dev, result_out_dev, n_leaves_out_dev,
+                           halton_next_out_dev, n_nodes_out_dev};
+  return tree_plan(e, n_sel, env_sel_dev, halton_start_dev, max_tree_nodes, out, [&](int n_cand, bool) {
+    if (algorithm == DRLGX_ALG_SLAM_OG_SHANNON)
+      return slam_og_run(e, n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, nullptr, nullptr, alpha, nullptr, e->tree_cost,
+                         nullptr, nullptr, nullptr, n_sel, env_sel_dev);
+    if (int r = og_tree_leaves(e, n_sel, env_sel_dev, n_cand, e->tree_cand_env, e->tree_cand_act, e->tree_cand_n, nullptr, e->tree_cost, nullptr))
+      return r;
+    return check_launch(e);
+  });
+}
+
+// The leaves the last served drlgx_em_plan or drlgx_og_plan scored, as it handed them to the body of drlgx_em_cost_steps (of
+// drlgx_og_cost / drlgx_slam_og_cost), with the costs that call computed: device-to-device copies on the engine's stream.
 int drlgx_em_plan_leaves(drlgx_engine *e, int capacity, int32_t *n_out_host, int32_t *has_steps_out_host, int32_t *cand_env_out_dev,
                          double *actions_out_dev, int32_t *n_actions_out_dev, uint8_t *core_out_dev, double *distance_out_dev,
                          double *cost_out_dev) {

@@ -144,6 +144,186 @@ __global__ __launch_bounds__(kT) void k_og_cost(DRLGX_KS_PARAM, const int32_t *c
   }
 }
 
+// ---- the leaves of a sampling tree (drlgx_og_plan): every leaf of a tree starts from the same landmarks and the same P old poses, so
+// k_og_tree_base walks those once per environment and k_og_tree_cost walks a leaf's K new poses only.  The ladder is a state machine
+// over the pose sequence: the state k_og_cost holds in `st` when it reaches pose index P is what the base leaves in its byte plane
+// (a walk k_og_cost ended early at an old pose stands in a state that maps to itself: the leaf's walk ends at its first pose that
+// sees the cell, in the same state).  The entropy term depends on the state only (a table built with k_og_cost's expression), the
+// lanes add their tiles' terms in k_og_cost's order and the waves' sums meet in wave order: the same bits as k_og_cost.
+//
+// LDS of the base: doubles poses [P_max][4]; ints bbox [P_max][4] | landmarks per cell [V] | known cells of the waves [kWaves] (all
+// dynamic: a static array on top of the 160 KB the launcher may ask for would make that request invalid).  Of a leaf: doubles poses [A_max][4] |
+// sums of the waves [kWaves] | the plan's distance | entropy per ladder state [DRLGX_LO_TAB]; ints bbox [A_max][4].
+__host__ __device__ inline size_t tree_base_lds_bytes(int P_max, int V) {
+  return (size_t)P_max * 4 * sizeof(double) + ((size_t)P_max * 4 + (size_t)V + kWaves) * sizeof(int);
+}
+__host__ __device__ inline size_t tree_leaf_lds_bytes(int A_max) {
+  return ((size_t)A_max * 4 + kWaves + 1 + DRLGX_LO_TAB) * sizeof(double) + (size_t)A_max * 4 * sizeof(int);
+}
+
+// One workgroup per selected environment.  base [n_envs][Vu] (row env_sel[blockIdx.x]): per cell the ladder state after the landmark
+// updates and the P old poses; known [n_envs]: the cells of the LIVE map below the occupancy threshold (Planner2D.cpp:1322-1325) - a
+// count, exact in any order.  An environment listed twice is written twice with the same values.
+__global__ __launch_bounds__(kT) void k_og_tree_base(DRLGX_KS_PARAM, const int32_t *env_sel, uint8_t *base, int32_t *known) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  extern __shared__ __attribute__((aligned(16))) double og_smem[];
+  const drlgx_config &cfg = S.cfg;
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6;
+  const int env = env_sel[blockIdx.x];
+  const bool env_ok = env >= 0 && env < S.n_envs;
+  const int P = env_ok ? S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_P] : 0, L = env_ok ? S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_L] : 0;
+  const int V = S.V;
+  if (!env_ok || P < 1 || P > S.P_max || L < 0 || L > S.L_max) {  // (the tree's kernel refused such a call: flag it, touch nothing)
+    if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+    return;
+  }
+  kmap::MapCtx c;
+  c.sp = og_smem;
+  c.bbox = reinterpret_cast<int *>(c.sp + (size_t)S.P_max * 4);
+  c.P = P;
+  int *lmc = c.bbox + (size_t)S.P_max * 4, *kred = lmc + V;
+  const double *ep = S.est_pose + (size_t)env * S.P_max * 4;
+  const double *el = S.est_lm + (size_t)env * S.L_max * 2;
+  for (int i = tid; i < P; i += kT) {
+    const double x = ep[4 * i], y = ep[4 * i + 1];
+    c.sp[4 * i] = x; c.sp[4 * i + 1] = y; c.sp[4 * i + 2] = ep[4 * i + 2]; c.sp[4 * i + 3] = ep[4 * i + 3];
+    kmap::bbox_origin(S, c.bbox + 4 * i, x, y);
+  }
+  for (int v = tid; v < V; v += kT) lmc[v] = 0;
+  __syncthreads();
+  for (int j = tid; j < L; j += kT) {
+    const int v = kmap::landmark_cell(S, el[2 * j], el[2 * j + 1]);
+    if (v >= 0) atomicAdd(&lmc[v], 1);
+  }
+  const bool use_bbox = !S.bbox_noop;
+  if (use_bbox) kmap::bbox_sweep(S, c);
+  __syncthreads();
+
+  const int cols = S.cols, rows = S.rows;
+  const int tiles_c = (cols + 7) >> 3, ntiles = ((rows + 7) >> 3) * tiles_c;
+  const kmap::LadderFsm fsm{S.lo_tocc, S.lo_tfree, S.lo_tflag};
+  const double *live = S.vm_prob + (size_t)env * V;
+  uint8_t *plane = base + (size_t)env * S.Vu;
+  int n_known = 0;  // (of the wave: the same in every lane)
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int trow = t / tiles_c, tcol = t - trow * tiles_c;
+    const int row = 8 * trow + (lane >> 3), col = 8 * tcol + (lane & 7);
+    const bool in = row < rows && col < cols;
+    bool is_known = false;
+    if (in) {
+      const int v = row * cols + col;
+      const P2 pt = kmap::cell_centre(cfg, row, col);
+      int st = 0;  // LOGODDS_UNKNOWN
+      for (int n = lmc[v]; n > 0; --n) st = fsm.landmark(st);
+      for (int i = 0; i < P; ++i) {  // (k_og_cost's walk, up to pose index P)
+        if (use_bbox && (row < c.bbox[4 * i] || row > c.bbox[4 * i + 1] || col < c.bbox[4 * i + 2] || col > c.bbox[4 * i + 3])) continue;
+        const Pose ps{c.sp[4 * i], c.sp[4 * i + 1], c.sp[4 * i + 2], c.sp[4 * i + 3]};
+        const double gx = ps.x - pt.x, gy = ps.y - pt.y;
+        if (!(gx * gx + gy * gy < S.r2_max_lt)) continue;
+        if (!kmap::in_fov(S, ps, pt)) continue;
+        const int nst = fsm.seen(st);
+        if (nst == st) break;
+        st = nst;
+      }
+      plane[v] = (uint8_t)st;
+      is_known = live[v] < cfg.occupancy_threshold;
+    }
+    n_known += __popcll(__ballot(is_known));
+  }
+  if (lane == 0) kred[wave] = n_known;
+  __syncthreads();
+  if (tid == 0) {
+    int k = 0;
+    for (int w = 0; w < kWaves; ++w) k += kred[w];
+    known[env] = k;
+  }
+}
+
+// One workgroup per leaf: candidates in k_og_cost's layout, base / known as k_og_tree_base left them for the leaf's environment;
+// ent_out / cost_out [gridDim.x], dist_out [gridDim.x][2], any of them null - what k_og_cost writes there, bit for bit.
+__global__ __launch_bounds__(kT) void k_og_tree_cost(DRLGX_KS_PARAM, const int32_t *cand_env, const double *actions,
+                                                     const int32_t *n_actions, const uint8_t *base, const int32_t *known, double *ent_out,
+                                                     double *cost_out, double *dist_out) {
+  const DrlgxState &S = DRLGX_KS_REF;
+  extern __shared__ __attribute__((aligned(16))) double og_smem[];
+  const drlgx_config &cfg = S.cfg;
+  const int tid = drlgx_tid(), lane = tid & 63, wave = tid >> 6, ci = blockIdx.x;
+  const int env = cand_env[ci];
+  const int K = n_actions[ci];
+  const bool env_ok = env >= 0 && env < S.n_envs;
+  const int P = env_ok ? S.cnt[(size_t)env * DRLGX_CNT_STRIDE + C_P] : 0;
+  const int V = S.V;
+  if (!env_ok || K < 0 || K > S.A_max || P < 1 || P > S.P_max) {  // (the tree's kernel refused such a call: flag it, touch nothing)
+    if (tid == 0) atomicMin(S.status, DRLGX_E_CAPACITY);
+    return;
+  }
+  kmap::MapCtx c;  // (the leaf's K new poses only)
+  c.sp = og_smem;
+  double *red = c.sp + (size_t)S.A_max * 4, *sdist = red + kWaves, *hs = sdist + 1;
+  c.bbox = reinterpret_cast<int *>(hs + DRLGX_LO_TAB);
+  c.P = K;
+  const double *ep = S.est_pose + (size_t)env * S.P_max * 4;
+  const double *act = actions + (size_t)ci * S.A_max * 3;
+
+  // ---- staging: one lane per new pose (the first lanes); the plan's distance and the entropy table on the last ones ----
+  for (int b = tid; b < K; b += kT) {
+    const Pose ps = kem::leaf_pose(ep, P, act, P + b);
+    c.sp[4 * b] = ps.x; c.sp[4 * b + 1] = ps.y; c.sp[4 * b + 2] = ps.c; c.sp[4 * b + 3] = ps.s;
+    kmap::bbox_origin(S, c.bbox + 4 * b, ps.x, ps.y);
+  }
+  if (tid == kT - 1) *sdist = kem::plan_distance(cfg, act, K);
+  const int hst = kT - 2 - tid;  // (lo_ntab <= DRLGX_LO_TAB < kT - 1)
+  if (hst >= 0 && hst < S.lo_ntab) {
+    const double pv = S.lo_pv[hst];
+    hs[hst] = -pv * log(pv) - (1.0 - pv) * log(1.0 - pv);
+  }
+  __syncthreads();
+  const bool use_bbox = !S.bbox_noop;
+  if (use_bbox) kmap::bbox_sweep(S, c);
+
+  // ---- cell pass: k_og_cost's tiles on k_og_cost's waves and lanes ----
+  const int cols = S.cols, rows = S.rows;
+  const int tiles_c = (cols + 7) >> 3, ntiles = ((rows + 7) >> 3) * tiles_c;
+  const kmap::LadderFsm fsm{S.lo_tocc, S.lo_tfree, S.lo_tflag};
+  const uint8_t *plane = base + (size_t)env * S.Vu;
+  double s_h = 0.0;
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int trow = t / tiles_c, tcol = t - trow * tiles_c;
+    const int row = 8 * trow + (lane >> 3), col = 8 * tcol + (lane & 7);
+    if (!(row < rows && col < cols)) continue;
+    const P2 pt = kmap::cell_centre(cfg, row, col);
+    int st = plane[row * cols + col];
+    for (int i = 0; i < K; ++i) {
+      if (use_bbox && (row < c.bbox[4 * i] || row > c.bbox[4 * i + 1] || col < c.bbox[4 * i + 2] || col > c.bbox[4 * i + 3])) continue;
+      const Pose ps{c.sp[4 * i], c.sp[4 * i + 1], c.sp[4 * i + 2], c.sp[4 * i + 3]};
+      const double gx = ps.x - pt.x, gy = ps.y - pt.y;
+      if (!(gx * gx + gy * gy < S.r2_max_lt)) continue;
+      if (!kmap::in_fov(S, ps, pt)) continue;
+      const int nst = fsm.seen(st);
+      if (nst == st) break;
+      st = nst;
+    }
+    s_h += hs[st];
+  }
+  s_h = kmap::wave_sum63(s_h);
+  if (lane == 63) red[wave] = s_h;
+  __syncthreads();
+  if (tid == 0) {
+    double h = 0.0;
+    for (int w = 0; w < kWaves; ++w) h += red[w];
+    if (ent_out) ent_out[ci] = h;
+    if (cost_out || dist_out) {
+      const double pk = (double)known[env] / (double)V;
+      const double dw = cfg.distance_weight0 - (cfg.distance_weight0 - cfg.distance_weight1) * pk;
+      if (cost_out) cost_out[ci] = h + *sdist * dw;
+      if (dist_out) {
+        dist_out[2 * ci] = *sdist;
+        dist_out[2 * ci + 1] = dw;
+      }
+    }
+  }
+}
+
 // ---- the SLAM-OG-Shannon cost (calculateUncertainty_SLAM_OG_SHANNON, Planner2D.cpp:394-416): the entropy above weighed against the
 // landmarks' uncertainty.  sqrt(det) of a landmark's 2x2 covariance given as (xx, xy, yy):
 __device__ inline double sqrt_det2(double xx, double xy, double yy) { return sqrt(xx * yy - xy * xy); }
@@ -230,6 +410,18 @@ void drlgx_launch_og_cost(const DrlgxState &S, hipStream_t st, int nc, const int
   drlgx_ensure_lds_attr(attr_set, fns, 1, (int)kmap::kLdsBudget);
   hipLaunchKernelGGL(kog::k_og_cost, dim3(nc), dim3(kog::kT), drlgx_og_lds_bytes(S), st, DRLGX_KS_ARG(S), cand_env, actions, n_actions,
                      ent_out, cost_out, prob_out, dist_out);
+}
+
+void drlgx_launch_og_tree_cost(const DrlgxState &S, hipStream_t st, int n_sel, const int32_t *env_sel, int nc, const int32_t *cand_env,
+                               const double *actions, const int32_t *n_actions, uint8_t *base, int32_t *known, double *ent_out,
+                               double *cost_out, double *dist_out) {
+  static bool attr_set[32] = {false};
+  const void *fns[] = {reinterpret_cast<const void *>(&kog::k_og_tree_base), reinterpret_cast<const void *>(&kog::k_og_tree_cost)};
+  drlgx_ensure_lds_attr(attr_set, fns, 2, (int)kmap::kLdsBudget);
+  hipLaunchKernelGGL(kog::k_og_tree_base, dim3(n_sel), dim3(kog::kT), kog::tree_base_lds_bytes(S.P_max, S.V), st, DRLGX_KS_ARG(S), env_sel,
+                     base, known);
+  hipLaunchKernelGGL(kog::k_og_tree_cost, dim3(nc), dim3(kog::kT), kog::tree_leaf_lds_bytes(S.A_max), st, DRLGX_KS_ARG(S), cand_env, actions,
+                     n_actions, base, known, ent_out, cost_out, dist_out);
 }
 
 void drlgx_launch_slam_og_weights(const DrlgxState &S, hipStream_t st, double alpha, double *weights) {

@@ -394,7 +394,7 @@ class Engine(object):
         self.dubins_leaf_scoring = bool(enabled)
 
     def em_plan_leaves(self):
-        """The leaves the last served em_plan scored (drlgx_em_plan_leaves), in candidate order: a dict of device tensors cand_env
+        """The leaves the last served em_plan or og_plan scored (drlgx_em_plan_leaves), in candidate order: a dict of device tensors cand_env
         [C] i32, actions [C, max_actions, 3] f64, n_actions [C] i32, core [C, max_actions] u8, cost [C] f64 and, when that call ran
         the Dubins control model (whatever the sampler's flag says now), distance [C] f64 (else None)."""
         self.use_torch_stream()
@@ -480,6 +480,21 @@ class Engine(object):
         self._chk(self.L.drlgx_em_plan(self.h, n, _p(env_sel), _p(halton_start), int(max_tree_nodes), int(algorithm), _p(o["plan"]),
                                        _p(o["n_actions"]), _p(o["cost"]), _p(o["result"]), _p(o["n_leaves"]), _p(o["halton_next"]),
                                        _p(o["nodes"]), _p(o["n_nodes"])))
+        return o
+
+    def og_plan(self, env_sel, halton_start, max_tree_nodes=1024, algorithm=2, alpha=0.0, want_nodes=False):
+        """EMPlanner2D::optimize2 under OG_SHANNON (algorithm 2) or SLAM_OG_SHANNON (algorithm 3) for the listed environments
+        (drlgx_og_plan): em_plan's tree, leaves and pick, the leaves scored with the cost of `og_cost` or of `slam_og_cost(alpha)` -
+        the same bits as those calls on the same leaves.  `alpha` (in [0, 1]) is read under algorithm 3 only.  Returns the dict of
+        em_plan; em_plan_leaves() reads back what was scored.  The Dubins control model is refused."""
+        self.use_torch_stream()
+        n = env_sel.numel()
+        o = self._tree_outputs(n, max_tree_nodes, want_nodes)
+        o["cost"] = torch.empty(n, dtype=torch.float64, device=self.device)
+        o["n_leaves"] = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._chk(self.L.drlgx_og_plan(self.h, n, _p(env_sel), _p(halton_start), int(max_tree_nodes), int(algorithm), float(alpha),
+                                       _p(o["plan"]), _p(o["n_actions"]), _p(o["cost"]), _p(o["result"]), _p(o["n_leaves"]),
+                                       _p(o["halton_next"]), _p(o["nodes"]), _p(o["n_nodes"])))
         return o
 
     def rrt_plan(self, env_sel, goal_key, goal_xy, halton_start, max_tree_nodes=1024, want_nodes=False):
@@ -654,7 +669,7 @@ class Engine(object):
         ms = (C.c_double * _lib.N_TIMERS)()
         n = (C.c_int64 * _lib.N_TIMERS)()
         self._chk(self.L.drlgx_timing_read_host(self.h, ms, n))
-        names = ["sim", "slam", "map", "copy", "graph", "step", "t6", "t7"]
+        names = ["sim", "slam", "map", "copy", "graph", "step", "t6", "t7"]  # (t6: og_plan's leaf scoring, t7: an empty span)
         return {names[i]: (ms[i], n[i]) for i in range(_lib.N_TIMERS)}
 
     # ---- getters (host)

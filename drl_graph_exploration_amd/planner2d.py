@@ -200,8 +200,8 @@ class EMPlanner2D(object):
         """calculateUncertainty_OG_SHANNON (Planner2D.cpp:368-392) for ONE action list of the wrapped simulation: the Shannon
         entropy of the occupancy map after the estimated landmarks, the trajectory and the plan's noise-free predicted poses have
         swept it (`drlgx_og_cost`); with `return_cost` also costFunction = entropy + distance * distance_weight.  No covariance,
-        no simulation; the live objects are not modified.  The tree planners under the OG algorithms stay out of scope (the
-        reference leaves their nodes' map a null pointer)."""
+        no simulation; the live objects are not modified.  `optimize2` under OptimizationAlgorithm.OG_SHANNON scores the leaves
+        of its tree with this cost (`drlgx_og_plan`)."""
         e, ce, acts, n = self._one_candidate(actions)
         ent, cost = e.og_cost(ce, acts, n)
         e.check_status()
@@ -213,7 +213,7 @@ class EMPlanner2D(object):
         and predicted measurements have updated their marginals (`drlgx_slam_og_cost`), with the root's weights w1 = alpha / (the
         same sum now), w2 = (1 - alpha) / (the entropy of the live map) and the parameter's `alpha`; with `return_cost` also
         costFunction = uncertainty + distance * distance_weight.  No simulation, no re-solve; the live objects are not modified.
-        The tree planners under the OG algorithms stay out of scope."""
+        `optimize2` under OptimizationAlgorithm.SLAM_OG_SHANNON scores the leaves of its tree with this cost (`drlgx_og_plan`)."""
         e, ce, acts, n = self._one_candidate(actions)
         unc, cost = e.slam_og_cost(ce, acts, n, self._parameter.alpha)
         e.check_status()
@@ -251,9 +251,10 @@ class EMPlanner2D(object):
         return OptimizationResult(int(result[0]))
 
     def optimize2(self, slam, virtual_map):
-        """EMPlanner2D::optimize2 (Planner2D.cpp:1043-1128) for the wrapped simulation (`drlgx_em_plan`)."""
-        alg = int(self._parameter.algorithm)
-        return self._tree_call(lambda e, sel, start: e.em_plan(sel, start, self.MAX_TREE_NODES, alg, want_nodes=True))
+        """EMPlanner2D::optimize2 (Planner2D.cpp:1043-1128) for the wrapped simulation: `drlgx_em_plan` under the two EM
+        algorithms, `drlgx_og_plan` with the parameter's `alpha` under OG_SHANNON and SLAM_OG_SHANNON (non-Dubins control model
+        only)."""
+        return self._tree_call(lambda e, sel, start: plan_trees(e, self._parameter, sel, start, self.MAX_TREE_NODES, want_nodes=True))
 
     def rrt_planner(self, slam, virtual_map, n_key, fron_0, fron_1):
         """EMPlanner2D::rrt_planner (Planner2D.cpp:838-935): goal = node `n_key` of the pose graph if it is one, else the frontier
@@ -288,6 +289,17 @@ class EMPlanner2D(object):
         if not self.dubins_paths:
             self._out_of_scope()
         return dubins_library(self._ses.require_engine())[int(index[0])]
+
+
+def plan_trees(engine, parameter, env_sel, halton_start, max_tree_nodes, want_nodes=False):
+    """optimize2's engine call for the parameter's algorithm: Engine.em_plan for EM_AOPT / EM_DOPT, Engine.og_plan with the
+    parameter's alpha for OG_SHANNON / SLAM_OG_SHANNON (where the Dubins control model stays out of scope)."""
+    alg = int(parameter.algorithm)
+    if alg not in (int(OptimizationAlgorithm.OG_SHANNON), int(OptimizationAlgorithm.SLAM_OG_SHANNON)):
+        return engine.em_plan(env_sel, halton_start, max_tree_nodes, alg, want_nodes=want_nodes)
+    if parameter.dubins_control_model_enabled:
+        raise NotImplementedError("optimize2 under OG_SHANNON / SLAM_OG_SHANNON runs the non-Dubins control model only")
+    return engine.og_plan(env_sel, halton_start, max_tree_nodes, alg, float(parameter.alpha), want_nodes=want_nodes)
 
 
 def load_dubins_library(engine, dubins_parameter):

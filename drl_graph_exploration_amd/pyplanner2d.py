@@ -294,7 +294,7 @@ class _Planner(object):
 
     def optimize2(self):
         cap = planner2d.EMPlanner2D.MAX_TREE_NODES
-        return self._call(lambda e, sel, start: e.em_plan(sel, start, cap, int(self._o._planner_params.algorithm), want_nodes=True))
+        return self._call(lambda e, sel, start: planner2d.plan_trees(e, self._o._planner_params, sel, start, cap, want_nodes=True))
 
     def rrt_planner(self, n_key, fron_0, fron_1):
         cap = planner2d.EMPlanner2D.MAX_TREE_NODES

@@ -228,7 +228,8 @@ class VecExplorationEnv(object):
         return wrapped
 
     def em_plan(self, max_nodes=0.5, max_tree_nodes=2048, planner_seed=0, safe_distance=None, dubins=None):
-        """ExplorationEnv.plan for all envs in one call (EMPlanner2D::optimize2, Engine.em_plan): per env the tree, the leaves' expected
+        """ExplorationEnv.plan for all envs in one call (EMPlanner2D::optimize2; Engine.em_plan under the EM algorithms, Engine.og_plan
+        with the planner parameter `alpha` (self.alpha) under OG_SHANNON / SLAM_OG_SHANNON): per env the tree, the leaves' expected
         costs with the configured algorithm, the best leaf's action list.  Returns (actions [n_envs, max_actions, 3] f64 edge
         odometry, n_actions [n_envs] i32, result [n_envs] i32) on the device; every env's Halton index carries on from call to
         call.  `safe_distance` (None: 0, as before): a value runs this call with the sampler's obstacle logic at that planner
@@ -236,10 +237,16 @@ class VecExplorationEnv(object):
         `dubins` (a planner2d.DubinsParameter; None: the non-Dubins control model as before): this call runs optimize2 under the
         Dubins control model with that library - it sets the library, the Dubins flag and the opt-in of the Dubins leaf scoring
         (Engine.set_dubins_leaf_scoring), the actions are then one odometry per step, an env can have result SAMPLING_FAILURE -
-        and the engine's Dubins flag and opt-in come back after it."""
+        and the engine's Dubins flag and opt-in come back after it (EM algorithms only: the OG algorithms refuse `dubins`)."""
         sel = torch.arange(self.n_envs, dtype=torch.int32, device=self.device)
         start = self._halton(planner_seed)
-        run = lambda: self.engine.em_plan(sel, start, max_tree_nodes, int(self.cfg.algorithm))
+        alg = int(self.cfg.algorithm)
+        if alg in (2, 3):  # OG_SHANNON, SLAM_OG_SHANNON
+            if dubins is not None:
+                raise NotImplementedError("optimize2 under OG_SHANNON / SLAM_OG_SHANNON runs the non-Dubins control model only")
+            run = lambda: self.engine.og_plan(sel, start, max_tree_nodes, alg, self.alpha)
+        else:
+            run = lambda: self.engine.em_plan(sel, start, max_tree_nodes, alg)
         if dubins is not None:
             run = self._with_dubins(dubins, True, run)
         o = self._with_safe_distance(max_nodes, safe_distance, run)

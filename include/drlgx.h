@@ -36,6 +36,8 @@ extern "C" {
 
 #define DRLGX_ALG_EM_AOPT 0 /* Planner2D.h OptimizationAlgorithm::EM_AOPT (trace) */
 #define DRLGX_ALG_EM_DOPT 1 /* OptimizationAlgorithm::EM_DOPT (determinant)      */
+#define DRLGX_ALG_OG_SHANNON 2      /* OptimizationAlgorithm::OG_SHANNON (map entropy: drlgx_og_cost, drlgx_og_plan) */
+#define DRLGX_ALG_SLAM_OG_SHANNON 3 /* OptimizationAlgorithm::SLAM_OG_SHANNON (drlgx_slam_og_cost, drlgx_og_plan)    */
 
 /* Parameters of one engine.  Mirrors the ini sections read by scripts/envs/pyss2d.py:10-55 and
  * scripts/envs/pyplanner2d.py:24-54 (values: scripts/envs/exploration_env.ini). Angles in radians,
@@ -278,7 +280,8 @@ int drlgx_em_cost_steps(drlgx_engine *e, int n_cand, const int32_t *cand_env_dev
  *   cost = entropy + distance * distance_weight, both exactly drlgx_em_cost's (the distance weight from the LIVE map's probabilities).
  * No covariance is needed, nothing is simulated or re-solved, live environments are not modified.  (The reference's tree planners
  * cannot run under OG_SHANNON as shipped - Node::map stays a null pointer, Planner2D.h:92, Planner2D.cpp:256, :785 - so this is the
- * cost's arithmetic for caller-supplied plans; drlgx_em_plan and drlgx_em_cost's algorithms are unchanged, SLAM_OG_SHANNON is out.)
+ * cost's arithmetic for caller-supplied plans, which drlgx_og_plan applies to the leaves of optimize2's tree; drlgx_em_plan and
+ * drlgx_em_cost's algorithms are unchanged, SLAM_OG_SHANNON is drlgx_slam_og_cost.)
  * Candidate layout as drlgx_em_cost: cand_env_dev int32[n_cand] (several candidates may name one environment); actions_dev
  * double[n_cand*max_actions*3]; n_actions_dev int32[n_cand], 0 <= n <= max_actions.  entropy_out_dev / cost_out_dev: DEVICE
  * double[n_cand], either may be NULL but not both; prob_out_dev: DEVICE double[n_cand*V] (row-major grid: the leaf map's
@@ -354,9 +357,9 @@ int drlgx_set_sampler_parameter(drlgx_engine *e, double max_nodes, double safe_d
  * that tree at once with SAMPLING_FAILURE, an empty plan and its Halton index unchanged.
  * A tree that ends with SAMPLING_FAILURE reports result 0, n_actions 0, no leaves, the nodes accepted so far in n_nodes / nodes_out,
  * and in halton_next the index after the last drawn point; the other trees of the call are not concerned, it offers no candidate to
- * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  optimize (RRT*) and
- * SLAM_OG_SHANNON stay out of scope; Dubins paths are served for drlgx_rrt_plan, and for drlgx_em_plan behind
- * drlgx_set_dubins_leaf_scoring (below). */
+ * the scoring, and the status word is untouched: a sampling failure is a result, not an error.  optimize (RRT*)
+ * stays out of scope; drlgx_og_plan (optimize2 under OG_SHANNON / SLAM_OG_SHANNON) serves the same obstacle logic.  Dubins paths are served for drlgx_rrt_plan, and for drlgx_em_plan behind
+ * drlgx_set_dubins_leaf_scoring (below) - not for drlgx_og_plan. */
 int drlgx_set_sampler_obstacles(drlgx_engine *e, int enabled);
 /* The Dubins control model's path library (EMPlanner2D::initializeDubinsPathLibrary, Planner2D.cpp:1359-1414), and with it the
  * OPT-IN of that control model: with no library loaded the Dubins flag of drlgx_set_sampler_parameter is refused as before.
@@ -411,14 +414,16 @@ int drlgx_set_dubins_prefilter(drlgx_engine *e, int enabled);
  * with DRLGX_E_CAPACITY before anything is written.  Executing non-core steps (simulate(core = false)) and optimize (RRT*) stay
  * out of scope. */
 int drlgx_set_dubins_leaf_scoring(drlgx_engine *e, int enabled);
-/* The leaves the last served drlgx_em_plan handed to its scoring, in candidate order (tree by tree, each tree's leaves in node
+/* The leaves the last served drlgx_em_plan or drlgx_og_plan handed to its scoring, in candidate order (tree by tree, each tree's leaves in node
  * order): *n_out_host = their number, *has_steps_out_host (may be NULL) = 1 if that call ran the Dubins control model - whatever the
  * sampler's flag says now -, else 0; up to `capacity` of them are copied on the engine's stream into the DEVICE arrays (each may
  * be NULL) cand_env int32[.], actions double[.*max_actions*3], n_actions int32[.], core uint8[.*max_actions] (all ones without the
  * Dubins control model), distance double[.] (only after a call with steps: otherwise DRLGX_E_INVALID before anything is written -
  * the cost then took the plan's own distance), cost double[.].  Part of the facade path: under the Dubins control model the plan's
  * rows are per-step odometries, not node columns, and EMPlanner2D / EMExplorer find the picked leaf's node for iter_solution() by
- * comparing the plan with these rows; feeding the leaves to drlgx_em_cost_steps reproduces the costs bit for bit (the tests do). */
+ * comparing the plan with these rows; feeding the leaves to drlgx_em_cost_steps reproduces the costs bit for bit (the tests do).
+ * After drlgx_og_plan: no steps, core all ones, no distance, and cost is the cost that call computed - feeding the leaves to
+ * drlgx_og_cost (algorithm 2) or to drlgx_slam_og_cost with the same alpha (algorithm 3) reproduces it bit for bit. */
 int drlgx_em_plan_leaves(drlgx_engine *e, int capacity, int32_t *n_out_host, int32_t *has_steps_out_host, int32_t *cand_env_out_dev,
                          double *actions_out_dev, int32_t *n_actions_out_dev, uint8_t *core_out_dev, double *distance_out_dev,
                          double *cost_out_dev);
@@ -453,6 +458,31 @@ int drlgx_em_plan_leaves(drlgx_engine *e, int capacity, int32_t *n_out_host, int
 int drlgx_em_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
                   int algorithm, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev, int32_t *result_out_dev,
                   int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev, int32_t *n_nodes_out_dev);
+/* EMPlanner2D::optimize2 under the two occupancy-grid algorithms (Planner2D.cpp:305-319, :1043-1128): drlgx_em_plan's tree - the same
+ * kernel, so the same Halton start on the same belief gives the same nodes whatever the algorithm, and the sampler's obstacle logic
+ * behind drlgx_set_sampler_obstacles is served in the same way -, drlgx_em_plan's leaves in node order and drlgx_em_plan's pick (the
+ * first leaf is always taken - which is also :1106-1108, "the first leaf replaces the root" -, a later one replaces it only on a
+ * strictly smaller cost, a NaN never replaces), with the leaf cost of
+ *   algorithm DRLGX_ALG_OG_SHANNON: drlgx_og_cost - the same bits as that call on the same leaf.  The leaves of a tree share the
+ *     landmarks' cells and the P old poses, so one kernel walks those once per environment and a second one walks each leaf's own
+ *     poses from there (k_og.hip: k_og_tree_base, k_og_tree_cost; the development switch DRLGX_OG_TREE_SHARED=0 scores every leaf
+ *     with drlgx_og_cost's kernel instead);
+ *   algorithm DRLGX_ALG_SLAM_OG_SHANNON: the body of drlgx_slam_og_cost with `alpha` (read under this algorithm only) - the weights
+ *     from the live belief, the covariance update in chunks of 128, H_leaf as under algorithm 2; the same bits as that call.  An
+ *     environment without a landmark has NaN costs and therefore plans to its first leaf: nothing is special-cased.
+ * (The reference cannot run these paths as shipped - Node::map stays a null pointer, see drlgx_og_cost - so the definition is
+ * optimize2's control flow as written with the leaf costs above.)  Arrays, max_tree_nodes and result as drlgx_em_plan; live
+ * environments are only read.  drlgx_em_plan_leaves reports the scored leaves afterwards.
+ * DRLGX_E_INVALID: another algorithm value, alpha outside [0, 1] under algorithm 3, the Dubins flag of drlgx_set_sampler_parameter set
+ * (the Dubins control model stays out here, with or without a library: plans of per-step rows cannot be executed yet anyway), and
+ * everything drlgx_em_plan refuses as a bad argument.  DRLGX_E_CAPACITY, the outputs then unspecified, live state and the status word
+ * untouched: a tree needs more than max_tree_nodes nodes or is deeper than max_actions, or - algorithm 3 - a leaf predicts more than
+ * 256 measurements.  Synchronisations: one under algorithm 2 (the tree's leaf counts and capacity flag; its leaves need no further
+ * check), two under algorithm 3 (that one and the candidate check of drlgx_slam_og_cost's body). */
+int drlgx_og_plan(drlgx_engine *e, int n_sel, const int32_t *env_sel_dev, const int32_t *halton_start_dev, int max_tree_nodes,
+                  int algorithm, double alpha, double *plan_out_dev, int32_t *n_actions_out_dev, double *cost_out_dev,
+                  int32_t *result_out_dev, int32_t *n_leaves_out_dev, int32_t *halton_next_out_dev, double *nodes_out_dev,
+                  int32_t *n_nodes_out_dev);
 /* EMPlanner2D::rrt_planner (Planner2D.cpp:838-935): the same tree, grown until a new node lies within max_edge_length of the goal
  * (isReached, :88-99: Euclidean distance), to which the goal Pose2(gx, gy, pi) is then connected by connectNode; the plan is the
  * path root -> goal.  The goal of environment i is the position of graph node goal_key[i] if 0 <= goal_key[i] < key_size
@@ -579,7 +609,7 @@ int drlgx_restore(drlgx_engine *e, int slot);
 /* Per-kernel timing (HIP events on the engine stream): enable (on = 1: spans around whatever is launched; on = 2: the
  * belief step is launched as its three stage kernels instead of the fused kernel, so that each stage gets its own span),
  * then read accumulated milliseconds and launch counts.  timer ids: 0 sim, 1 slam, 2 map, 3 copy/prepare, 4 graph,
- * 5 fused belief step (sim + slam + map), 7 = an EMPTY span recorded once per drlgx_step (the event-pair overhead a caller
+ * 5 fused belief step (sim + slam + map), 6 the leaf scoring of drlgx_og_plan (the entropy kernels), 7 = an EMPTY span recorded once per drlgx_step (the event-pair overhead a caller
  * subtracts from the per-launch averages).  */
 #define DRLGX_N_TIMERS 8
 int drlgx_timing_enable(drlgx_engine *e, int on);
