@@ -139,5 +139,16 @@ static_assert(ArrowWs(80, 500, 3600).total == 1399104 && ArrowCarve::min_bytes(8
 static_assert(ArrowWs(41, 8, 492).total == 12032 && ArrowCarve::min_bytes(41, 8) == 37720, "the default engine (41 poses, 40 m map) moved");
 static_assert(ArrowWs(41, 100, 512).total == 91584 && ArrowCarve::min_bytes(41, 100) == 84728, "bench.py's 41-pose engine moved");
 
+// The forms of phase 10, the pose products (ArrowCtx::pose_products, products_staged), as the kernel and the host's
+// drlgx_debug_arrow_form decide them.  np = 2 L pivots in nK = (np + 15) / 16 chunks of the product's K dimension.
+constexpr int kArrowPanelChunks = 8;  // K chunks whose 16-row panel of X a wave holds in registers (products_tiles)
+constexpr int kArrowZG = 3;           // column tiles per group of the staged form, at most
+ARROW_CARVE_FN bool arrow_products_vector(bool c_lds, int np) { return c_lds && np <= 12; }
+ARROW_CARVE_FN bool arrow_products_tiles(int np) { return (np + 15) / 16 <= kArrowPanelChunks; }  // (else staged)
+// staged form: as many column tiles per group as the LDS behind the pose tables holds (one tile = nK x 2 KB); none: one tile,
+// staged in the workspace's sweep panels
+ARROW_CARVE_FN int arrow_zfit(size_t u_free, int nK) { return (int)(u_free / ((size_t)nK * 2048)); }
+ARROW_CARVE_FN int arrow_zg(int zfit) { return zfit >= 1 ? (kArrowZG < zfit ? kArrowZG : zfit) : 1; }
+
 #undef ARROW_CARVE_FN
 }  // namespace kslam

@@ -804,7 +804,7 @@ struct ArrowCtx {
       products_estimates();
       return false;
     }
-    if (c_lds && np <= 12) {
+    if (arrow_products_vector(c_lds, np)) {
       products_vector(S, pan_pose);
       return false;
     }
@@ -818,7 +818,7 @@ struct ArrowCtx {
       __syncthreads();
     }
     DRLGX_PROF(S, 100);
-    if ((np + 15) / 16 <= kPanel) products_tiles(S, pan_pose);
+    if (arrow_products_tiles(np)) products_tiles(S, pan_pose);
     else products_staged(S, pan_pose);
     return mk_panel;  // (the tile forms also form the panel's columns of the newest pose)
   }
@@ -927,7 +927,7 @@ struct ArrowCtx {
 
   // up to 8 column chunks = 127 landmark columns (the LDS-resident systems and the register-tile sweep's): the A operand of a
   // whole tile row (its 16 x np panel of X) is held in registers
-  static constexpr int kPanel = 8;
+  static constexpr int kPanel = kArrowPanelChunks;
   __device__ __forceinline__ void products_tiles(const DrlgxState &S, double *pan_pose) const {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lc = lane & 15, lr = lane >> 4;
     const int nrows = 3 * P, nrt = (nrows + 15) / 16, nK = (np + 15) / 16;
@@ -981,11 +981,11 @@ struct ArrowCtx {
   __device__ __forceinline__ void products_staged(const DrlgxState &S, double *pan_pose) const {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lc = lane & 15, lr = lane >> 4;
     const int nrows = 3 * P, nrt = (nrows + 15) / 16, nK = (np + 15) / 16;
-    constexpr int kZG = 3;
+    constexpr int kZG = kArrowZG;
     // as many column tiles per group as the LDS behind the pose tables holds (one tile = nK x 2 KB); none: one tile, staged in
     // the workspace's sweep panels (dead as well) - the L2 then serves what the LDS would
-    const int zfit = (int)(u_free / ((size_t)nK * 2048));
-    const int zg = zfit >= 1 ? min(kZG, zfit) : 1;
+    const int zfit = arrow_zfit(u_free, nK);
+    const int zg = arrow_zg(zfit);
     double *Bs = this->Bs(zfit);
     // the row sums are accumulated per column group in LDS and go to the workspace / the panel at the end (as
     // read-modify-writes of the workspace they cost 8 us per (row tile, column group): a round trip to L2 each)

@@ -18,6 +18,23 @@ bool drlgx_slam_capacity_ok(int P_max, int L_max, int M_max) {
 // table) lies at its start.  The layout: arrow_carve.h
 size_t drlgx_slam_ws_doubles(int P_max, int L_max, int M_max) { return kslam::ArrowWs(P_max, L_max, M_max).total; }
 
+// register tiles per wave of the pose-chain kernel that serves an engine of up to L_max landmarks (0: its landmark system is
+// always packed in LDS, no register-tile sweep compiled in)
+static int arrow_ntw(int L_max) { return 2 * L_max + 1 <= 16 * kslam::kFastTilesArrow ? 0 : kslam::kArrowRegTiles; }
+
+int drlgx_debug_arrow_form(int P, int L, int M, int L_max, int mk_panel, int32_t out[DRLGX_ARROW_FORM_N]) {
+  if (!out || P < 1 || L < 0 || M < 0 || L > L_max || P > 65535 || L_max > 32767 || M > (1 << 24)) return DRLGX_E_INVALID;
+  const int NTW = arrow_ntw(L_max);
+  const kslam::ArrowCarve ac(P, L, M, NTW, kslam::kLdsBudget, mk_panel != 0);
+  if (!ac.c_lds && NTW == 0) return DRLGX_E_INVALID;  // (ArrowCtx::setup leaves there)
+  const int nK = (ac.np + 15) / 16, zfit = kslam::arrow_zfit(ac.u_free, nK > 0 ? nK : 1);
+  out[0] = ac.c_lds ? 0 : ac.c_reg ? 1 : 2;
+  out[1] = ac.obs_lds; out[2] = ac.xs_lds; out[3] = ac.rec_lds;
+  out[4] = kslam::arrow_products_vector(ac.c_lds, ac.np) ? 0 : kslam::arrow_products_tiles(ac.np) ? 1 : 2;
+  out[5] = zfit; out[6] = kslam::arrow_zg(zfit); out[7] = ac.Tn; out[8] = nK;
+  return DRLGX_OK;
+}
+
 void drlgx_launch_slam(const DrlgxState &S, hipStream_t st, LaunchSel sel, int p_bound) {
   const int Pb = p_bound < S.P_max ? p_bound : S.P_max;
   if (sel.pcap <= 0) sel.pcap = Pb;
@@ -30,7 +47,7 @@ void drlgx_launch_slam(const DrlgxState &S, hipStream_t st, LaunchSel sel, int p
   // (the whole LDS is requested: what the tables and the system leave free holds the factor records and the observation table)
   if (drlgx_slam_in_lds(Pb, S.L_max, S.M_max))
     hipLaunchKernelGGL((kslam::k_slam<kslam::kFastTiles>), grid, block, kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, kslam::kLdsBudget);
-  else if (2 * S.L_max + 1 <= 16 * kslam::kFastTilesArrow)  // landmark system always packed in LDS: no register-tile sweep compiled in
+  else if (arrow_ntw(S.L_max) == 0)
     hipLaunchKernelGGL((kslam::k_slam_arrow<0>), grid, block, kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, kslam::kLdsBudget);
   else
     hipLaunchKernelGGL((kslam::k_slam_arrow<kslam::kArrowRegTiles>), grid, block, kslam::kLdsBudget, st, DRLGX_KS_ARG(S), sel, kslam::kLdsBudget);

@@ -646,6 +646,20 @@ int drlgx_debug_map_compact_ok(const drlgx_engine *e, int p_bound);
  * (radius_cells = max_range / resolution, 0 .. 64), so that a CPU test can hold it against a brute-force lattice count. */
 int drlgx_debug_disc_cells_bound(double radius_cells);
 
+/* Development aid, stateless and host-only: the code paths the pose-chain solver (csrc/k_slam_arrow.hip) takes for a full solve
+ * of an instance with P poses, L landmarks and M factors in an engine whose max_landmarks is L_max - its LDS carve
+ * (csrc/arrow_carve.h) at the kernel instantiation and the LDS request drlgx_launch_slam uses, and the predicates of its pose
+ * products; mk_panel: the solve leaves a covariance panel (the incremental update is on).  out[DRLGX_ARROW_FORM_N]:
+ *   [0] landmark system: 0 packed in LDS, 1 register tiles over the workspace, 2 streamed
+ *   [1] obs_lds  [2] xs_lds  [3] rec_lds: observation table / separator rows / factor records in LDS (1) or workspace (0)
+ *   [4] form of the pose products: 0 vector units, 1 register-panel tiles, 2 staged
+ *   [5] zfit: column tiles of operand images the LDS holds (staged form; 0: the images lie in the streamed sweep's panels)
+ *   [6] zg: column tiles per group (staged form)   [7] Tn: tile rows of the landmark system   [8] nK: K chunks of a product
+ * A CPU test proves with it that a world lands in the cell it claims.  Returns DRLGX_E_INVALID for counts out of range
+ * (P < 1, L < 0, M < 0, L > L_max) and for a landmark system this engine's kernel does not serve. */
+#define DRLGX_ARROW_FORM_N 9
+int drlgx_debug_arrow_form(int P, int L, int M, int L_max, int mk_panel, int32_t out[DRLGX_ARROW_FORM_N]);
+
 /* The incremental belief update (csrc/k_inc.hip): between relinearisations of the iSAM2 policy (SLAM2D.cpp:10-12: every
  * 10th update, |delta| >= 0.1) SLAM2D::optimize (SLAM2D.cpp:374-430) only gains the new pose's odometry factor and the
  * step's bearing-range factors, so the engine applies the covariance-form update of FastMarginals2::propagate / update
