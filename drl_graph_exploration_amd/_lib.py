@@ -38,7 +38,7 @@ SYMBOLS = [
     "drlgx_get_poses_host", "drlgx_get_landmarks_host", "drlgx_get_cov_traces_host", "drlgx_vm_shape",
     "drlgx_get_virtual_map_host", "drlgx_get_ground_truth_host", "drlgx_get_adjacency_host", "drlgx_get_factors_host",
     "drlgx_get_landmark_order_host", "drlgx_snapshot", "drlgx_restore", "drlgx_timing_enable",
-    "drlgx_timing_read_host", "drlgx_debug_phase_clocks_host", "drlgx_debug_gemm_tile_rows", "drlgx_debug_map_form", "drlgx_debug_map_compact_ok", "drlgx_debug_disc_cells_bound", "drlgx_debug_arrow_form", "drlgx_inc_stats_host", "drlgx_debug_panel_host", "drlgx_debug_restore_table_host", "drlgx_debug_field_live_bytes", "drlgx_gcn_workspace_bytes", "drlgx_gcn_forward", "drlgx_gcn_forward_batched", "drlgx_gcn_backward",
+    "drlgx_timing_read_host", "drlgx_debug_phase_clocks_host", "drlgx_debug_gemm_tile_rows", "drlgx_debug_map_form", "drlgx_debug_map_compact_ok", "drlgx_debug_disc_cells_bound", "drlgx_debug_arrow_form", "drlgx_debug_inc_form", "drlgx_inc_stats_host", "drlgx_debug_panel_host", "drlgx_debug_restore_table_host", "drlgx_debug_field_live_bytes", "drlgx_gcn_workspace_bytes", "drlgx_gcn_forward", "drlgx_gcn_forward_batched", "drlgx_gcn_backward",
     "drlgx_replay_collate", "drlgx_replay_collate_pair", "drlgx_dqn_targets", "drlgx_dqn_loss_grad", "drlgx_dqn_arena_bytes", "drlgx_dqn_arena_views", "drlgx_dqn_prepare", "drlgx_dqn_forward_backward", "drlgx_replay_cache_csr", "drlgx_gcn_collate_csr", "drlgx_gcn_forward_prebuilt", "drlgx_adam_step", "drlgx_adam_step_scaled", "drlgx_normalise_rewards",
     "drlgx_segment_softmax", "drlgx_segment_softmax_backward", "drlgx_mean_pool", "drlgx_mean_pool_backward",
     "drlgx_ggnn_workspace_bytes", "drlgx_ggnn_forward", "drlgx_ggnn_backward",
@@ -141,6 +141,7 @@ def lib():
     L.drlgx_debug_map_compact_ok.argtypes = [vp, C.c_int]
     L.drlgx_debug_disc_cells_bound.argtypes = [C.c_double]
     L.drlgx_debug_arrow_form.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    L.drlgx_debug_inc_form.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_int32)]
     L.drlgx_inc_stats_host.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     if os.environ.get("DRLGX_LIB_DEV") is None or hasattr(L, "drlgx_debug_panel_host"):  # (a variant library of an earlier commit lacks it)
         L.drlgx_debug_panel_host.argtypes = [vp, C.c_int, ip, dp, C.c_size_t]

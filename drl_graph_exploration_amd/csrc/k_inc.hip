@@ -33,6 +33,7 @@
 #pragma once
 #include <type_traits>
 #include "k_slam_common.hip"
+#include "inc_carve.h"
 namespace kslam {
 // Contraction is decided in the front end here (a * b + c written in one expression becomes an fma, nothing else does): with
 // contract(fast) the back end fuses differently in the fused step kernel and in the stage kernel, and the two must agree bit
@@ -112,6 +113,10 @@ __device__ __forceinline__ double row_shr_f64(double v) {
 // count L0 of the previous update) plus room for up to INEW landmarks seen for the first time, so that the first half of the
 // update can run beside the simulator wave of the fused step kernel.
 constexpr int INEW = 12;
+// (inc_carve.h states the plan below a second time, in plain C++, for the host's drlgx_debug_inc_form)
+static_assert(IYS == IncCarve::IYS && INF == IncCarve::INF && INEW == IncCarve::INEW && ISNT == IncCarve::ISNT && kStreamKB == IncCarve::kStreamKB &&
+                  REC == IncCarve::kRec && kFastTilesArrow == 8,
+              "inc_carve.h no longer states the constants of inc_plan / inc_post");
 struct IncCtx {
   int inst, P, pn, pp, L0, M0, Lcap, n1, n1p, a0, ldw;
   int *fre, *fnew, *fslot, *ictl;

@@ -35,6 +35,30 @@ int drlgx_debug_arrow_form(int P, int L, int M, int L_max, int mk_panel, int32_t
   return DRLGX_OK;
 }
 
+int drlgx_debug_inc_form(int P, int L0, int n_re, int pc, int P_max, int L_max, int LG, int lds_bytes, int32_t out[DRLGX_INC_FORM_N]) {
+  if (!out || P < 2 || P > P_max || P_max > 65535 || L0 < 0 || L0 > L_max || L_max > 32767 || n_re < 0 || n_re > L0 || n_re > kslam::IncCarve::INF ||
+      pc < 1 || pc > P_max || LG < 1 || LG > (1 << 20) || lds_bytes < 0 || lds_bytes > kslam::kLdsBudget)
+    return DRLGX_E_INVALID;
+  for (int i = 0; i < DRLGX_INC_FORM_N; ++i) out[i] = 0;
+  // (as inc_plan: the simulator's region of the fused step at the launch's pose bound; the decisions do not depend on where the
+  // calling kernel's own carve begins, so the stage kernels' offset 0 stands for all of them)
+  const kslam::IncCarve c(P, L0, L_max, drlgx_sim_lds_bytes(LG, pc), (size_t)lds_bytes, 0);
+  out[0] = c.feasible;
+  if (!c.feasible) return DRLGX_OK;
+  out[1] = c.lds_panel; out[2] = c.wide; out[3] = c.snt;
+  const bool streamed = kslam::inc_streams(c.snt, c.wide, n_re, c.n1, c.a0);
+  out[4] = streamed;
+  int nw = 0;
+  for (int b0 = 0; b0 < n_re; ++nw) {  // (inc_post's two loops)
+    const int left = n_re - b0;
+    const int nt = streamed ? kslam::inc_stream_tiles(c.snt, left) : kslam::inc_batch_wide(c.wide, left) ? 2 : 1;
+    out[6 + nw] = nt;
+    b0 += 8 * nt < left ? 8 * nt : left;
+  }
+  out[5] = nw;
+  return DRLGX_OK;
+}
+
 void drlgx_launch_slam(const DrlgxState &S, hipStream_t st, LaunchSel sel, int p_bound) {
   const int Pb = p_bound < S.P_max ? p_bound : S.P_max;
   if (sel.pcap <= 0) sel.pcap = Pb;

@@ -660,6 +660,25 @@ int drlgx_debug_disc_cells_bound(double radius_cells);
 #define DRLGX_ARROW_FORM_N 9
 int drlgx_debug_arrow_form(int P, int L, int M, int L_max, int mk_panel, int32_t out[DRLGX_ARROW_FORM_N]);
 
+/* Development aid, stateless and host-only: the form the incremental (rank-k) belief update (csrc/k_inc.hip: inc_plan, inc_post)
+ * chooses for the update that brings an instance to P poses, with L0 landmarks in its covariance panel and n_re of them
+ * re-observed - the LDS plan of csrc/inc_carve.h, the header the kernel takes its plan from, evaluated on the host.
+ *   pc         the launch's pose bound (drlgx_step: the largest pose count any env can have after the step, at most max_poses)
+ *   P_max, L_max, LG   max_poses, max_landmarks and max(num_landmarks, 1) of the engine;   lds_bytes   the launch's dynamic LDS (163840)
+ * out[DRLGX_INC_FORM_N]:
+ *   [0] feasible: 0 = the fixed part of the plan misses the LDS, the update is a full solve (everything else is then 0)
+ *   [1] lds_panel: the panel is staged in LDS (1) or updated in place in HBM / L2 (0)
+ *   [2] wide: the second half of Y fits, batches of up to 16 re-observed landmarks (1), or of up to 8 (0)
+ *   [3] snt: factor tiles (of 8 landmarks) per walk the streamed form affords, 1 .. 4 (0: no streamed form - the panel in LDS, or
+ *       an update of at most 53 poses, which the dense solver's kernels serve)
+ *   [4] streamed: this update takes the streamed form (snt > 0 and more landmarks than one batch, or a Y image beyond 512 KB)
+ *   [5] the number of walks (streamed) or batches (otherwise) over the panel, 0 .. 8
+ *   [6 ..] per walk or batch, its tiles of 8 landmarks: 1 .. snt (streamed); 1 = a narrow batch, 2 = a wide one (otherwise)
+ * A test holds its own statement of the form against it, and proves that a world lands in the form it claims.  Returns
+ * DRLGX_E_INVALID for counts out of range (P < 2, P > P_max, L0 > L_max, n_re > L0 or > 64, pc > P_max, lds_bytes > 163840). */
+#define DRLGX_INC_FORM_N 14
+int drlgx_debug_inc_form(int P, int L0, int n_re, int pc, int P_max, int L_max, int LG, int lds_bytes, int32_t out[DRLGX_INC_FORM_N]);
+
 /* The incremental belief update (csrc/k_inc.hip): between relinearisations of the iSAM2 policy (SLAM2D.cpp:10-12: every
  * 10th update, |delta| >= 0.1) SLAM2D::optimize (SLAM2D.cpp:374-430) only gains the new pose's odometry factor and the
  * step's bearing-range factors, so the engine applies the covariance-form update of FastMarginals2::propagate / update

@@ -203,10 +203,11 @@ def _up16(b):
 
 
 def sim_lds_bytes(LG, pc, P_max):
-    """drlgx_sim_lds_bytes (csrc/drlgx_dev.h)."""
+    """drlgx_sim_lds_bytes (csrc/drlgx_dev.h) as inc_plan calls it: with the launch's pose bound pc for its pose argument (so the pose
+    tables count up to pc = 64 whatever max_poses is; P_max is not part of it)."""
     b = 2 * MT_STRIDE * 4 + (2 * LG + 2) * 8 + LG * 4 + 16
     b = ((b + 7) & ~7) + 2 * LG * 8
-    if P_max <= 64:
+    if pc <= 64:
         b = max(b, pc * 19 * 8 + 32)
     return (b + 31) & ~31
 

@@ -147,7 +147,8 @@ def test_form_table_is_the_plan_arithmetic():
     forms = {f for w in S.FORMS.values() for t in w.values() for f in t.values()}
     print("\nforms reached: %s" % sorted(forms))
     # the panel in LDS and in HBM / L2, the wide two-walk form, and the streamed form with 3 and 4 tiles in its first walk and
-    # 1, 2, 3 and 4 in its second (the narrow two-walk form is not reached: the second half of Y fits the LDS in all of them)
+    # 1, 2, 3 and 4 in its second (the narrow forms, first walks of one and two tiles and a plan that misses the LDS are reached by
+    # the worlds of tests/inc_form_cases.py, not by these: here the second half of Y fits the LDS everywhere)
     assert forms >= {"lds wide", "two-walk wide", "streamed 3", "streamed 4", "streamed 4+1", "streamed 4+2", "streamed 4+3", "streamed 4+4"}
     # the fallback edges, one case on either side (csrc/k_inc.hip: INF = 64, INEW = 12)
     assert S.expected_path((64, 64, 52, 12), 5, False) == "inc" and S.expected_path((65, 65, 64, 1), 5, False) == "full"
